@@ -17,14 +17,18 @@ error (exit status 3, no JSON line), never a silently smaller job.
 
 The timed step is the recorded step of multiposenet/pytorch_amd/replay.py (forward, losses, zero_grad, backward on two
 HIP streams, RCCL buckets, Adam — recorded once as a launch list and re-issued per step (replay.py); `--launch eager`
-times the Python tape instead).  Every timed
-step is also bracketed by a pair of HIP events on the launch stream; their median is reported beside the wall-clock
-mean that `value` is computed from.
+times the Python tape instead).  A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+`--dump-outputs DIR` is given, and prints the line; `value` and `ms_per_step` come from the wall clock around the K steps.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel class, timed with HIP events on the launch stream
+Prints ONE JSON line (rank 0).  With `--full` it also carries what takes work beyond the headline: every timed step is
+bracketed by a pair of HIP events on the launch stream (their median beside the wall-clock mean); the host cost of issuing
+one step into an empty queue; `roofline` for the dominant kernel class, timed with HIP events on the launch stream
 in separate instrumented eager steps AFTER the timed region, one kernel on the GPU at a time (top level); the same
 brackets with the weight-gradient side stream on are nested under `overlapped`.  `cpu_baseline` is the oracle's
 torch-CPU restatement of the same step timed on this host (rank 0, N=1 only).
+
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs out/     # loss, loss log, parameter / gradient samples
 """
 import argparse
 import json
@@ -76,6 +80,12 @@ def parse():
                     help="TEST SWITCH, NOT A MEASUREMENT: run the N ranks of --gpus N on ONE device over gloo (RCCL refuses two ranks on one "
                          "GPU), so that the spawn -> rendezvous -> data-parallel step -> one-JSON-line path executes on a 1-GPU box; the line "
                          "carries \"not_a_measurement\": true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures the headline does not need: per-step HIP-event times, the host cost of issuing one step, the "
+                         "per-kernel roofline (instrumented eager steps) and the CPU baseline.  Off: set-up, warm-up, the timed steps, the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: the loss, every loss-log "
+                         "value, and a fixed, seeded sample of the updated trainable parameters and of their gradients")
     return ap.parse_args()
 
 
@@ -216,9 +226,40 @@ def pmc_traffic(kernel_class, tag=""):
         return None, None
 
 
+DUMP_SAMPLE = 4 << 20        # elements per sampled array: 16 MB of float32 each, 32 MB for both
+
+
+def sample_positions(runs, n, seed=0):
+    """Sorted arena positions: every position of the [start, end) runs when they hold at most n, else a fixed seeded sample of n."""
+    starts = np.array([s for s, _ in runs], dtype=np.int64)
+    cum = np.concatenate([[0], np.cumsum([e - s for s, e in runs])]).astype(np.int64)
+    total = int(cum[-1])
+    k = np.arange(total, dtype=np.int64) if total <= n else np.sort(np.random.default_rng(seed).choice(total, n, replace=False))
+    r = np.searchsorted(cum, k, side="right") - 1
+    return starts[r] + (k - cum[r])
+
+
+def dump_outputs(out_dir, loss, log, arena):
+    """What the caller of the timed step holds after its last call: the loss, the loss log, and the trainable parameters after the
+    update with the gradients the step computed (a fixed sample of each; the PRN, not trained here, is left out)."""
+    import re
+    runs = [(o, o + n) for p, o, n in zip(arena.params, arena.offsets, arena.sizes) if p.requires_grad]
+    idx = torch.from_numpy(sample_positions(runs, DUMP_SAMPLE)).to(arena.flat.device)
+    arrays = {"loss": loss.detach().float().reshape(-1).cpu().numpy(),
+              "params_sample": arena.flat[idx].cpu().numpy(),
+              "grads_sample": arena.grad_flat[idx].cpu().numpy()}
+    for k, v in log.items():
+        arrays["log_" + re.sub(r"[^A-Za-z0-9_.-]", "_", k)] = np.array([float(v)], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` with no launcher around it: start the N ranks here (one process per GPU under
-    torch.distributed.run, rendezvous on 127.0.0.1) — the same command line the driver uses for N > 1.  Never returns."""
+    torch.distributed.run, rendezvous on 127.0.0.1) — the same command line the driver uses for N > 1.  Never returns: exits with
+    the launcher's status.  The launcher is a child process, not an exec: counting the devices has initialised the HIP runtime in
+    this process, and a process holding the device must not replace its own program."""
     import socket
     ndev = torch.cuda.device_count() if torch.cuda.is_available() else 0
     if args.shared_device_test and ndev >= 1:
@@ -235,7 +276,9 @@ def spawn_ranks(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC only on this host driver (RCCL needs it)
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    import subprocess
+    rc = subprocess.call(cmd)
+    sys.exit(rc if rc >= 0 else 128 - rc)          # killed by signal s: 128 + s, as a shell reports it
 
 
 def main():
@@ -245,6 +288,8 @@ def main():
         return
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -343,12 +388,14 @@ def main():
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
     t0 = time.perf_counter()
-    marks[0].record()
+    if marks is not None:
+        marks[0].record()
     for i in range(args.steps):
         loss = step()
-        marks[i + 1].record()
+        if marks is not None:
+            marks[i + 1].record()
     t_enq = time.perf_counter() - t0             # host time to enqueue the K steps (the GPU may still be running)
     torch.cuda.synchronize()
     if dist is not None:
@@ -383,25 +430,28 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert torch.isfinite(loss).all()
-    # Host cost of issuing one step, measured with an EMPTY queue (synchronise, enqueue one step, read the clock before the GPU
-    # finishes): the in-region figure above is throttled to the GPU's pace once the queue is full.
-    host_free = []
-    for _ in range(5):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last_log["log"], model._arena)
+    host_free, step_ms, median_ms = [], [], None
+    if args.full:
+        # Host cost of issuing one step, measured with an EMPTY queue (synchronise, enqueue one step, read the clock before the GPU
+        # finishes): the in-region figure above is throttled to the GPU's pace once the queue is full.
+        for _ in range(5):
+            torch.cuda.synchronize()
+            h0 = time.perf_counter()
+            step()
+            host_free.append(time.perf_counter() - h0)
         torch.cuda.synchronize()
-        h0 = time.perf_counter()
-        step()
-        host_free.append(time.perf_counter() - h0)
-    torch.cuda.synchronize()
-    host_free.sort()
-    step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
-    median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
+        host_free.sort()
+        step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+        median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
 
     # Kernel-level roofline: instrumented EAGER steps outside the timed region (per-launch event brackets serialise
     # neighbouring kernels, and events cannot be read out of a graph replay).  First with the weight-gradient side
     # stream off (one kernel on the GPU at a time: the kernel's own quality, comparable with a serial rocprofv3 trace),
     # then with the production schedule (brackets time-share the GPU with the other stream).
     ke, ke_serial, ev_steps, serial_steps = {}, {}, 0, 0
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         def eager():
             return train_step(model, opt, inputs, gts)[0]
         overlap = model._engine.overlap_wgrad
@@ -454,12 +504,14 @@ def main():
         if args.shared_device_test:
             out["not_a_measurement"] = True
             out["config"]["parallelism"] += " (TEST: %d ranks sharing one device over gloo — exercises the launch path, measures nothing)" % world
-        out["ms_per_step_median_hipevent"] = round(median_ms, 3)
-        out["ms_per_step_min_max_hipevent"] = [round(step_ms[0], 3), round(step_ms[-1], 3)]
+        if args.full:
+            out["ms_per_step_median_hipevent"] = round(median_ms, 3)
+            out["ms_per_step_min_max_hipevent"] = [round(step_ms[0], 3), round(step_ms[-1], 3)]
         out["last_step_log"] = {k: round(float(v), 6) for k, v in last_log["log"].items()      # values exist, they were just
                                 if k in ("heatmap_loss", "total_loss", "classification_loss", "regression_loss")}   # not waited for
-        out["host_enqueue_ms_per_step"] = round(host_free[len(host_free) // 2] * 1000.0, 3)      # empty queue, median of 5
-        out["host_enqueue_ms_per_step_in_region"] = round(t_enq / args.steps * 1000.0, 3)       # queue full: follows the GPU
+        if args.full:
+            out["host_enqueue_ms_per_step"] = round(host_free[len(host_free) // 2] * 1000.0, 3)      # empty queue, median of 5
+            out["host_enqueue_ms_per_step_in_region"] = round(t_enq / args.steps * 1000.0, 3)       # queue full: follows the GPU
         gf = GFLOP_PER_IMG_TRAIN.get((args.layers, args.size, args.subnet))
         if gf is not None:
             out["model_tflops_per_gpu"] = round(ips / world * gf / 1000.0, 2)
@@ -482,7 +534,7 @@ def main():
                                                  "how": "same brackets with the production two-stream schedule: the launch time-shares "
                                                         "the GPU with the other stream, so it reads longer than in isolation"}
             out["kernel_classes_ms_per_step"] = {k: round(v["ms"] / serial_steps, 3) for k, v in sorted(ke_serial.items(), key=lambda kv: -kv[1]["ms"])}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)

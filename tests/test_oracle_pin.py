@@ -212,19 +212,46 @@ def test_peak_extraction_restatement_vs_reference(case):
         assert np.array_equal(refd, g["nms_refined_" + case])
 
 
-def test_reference_nms_kernel_builds_unmodified_into_oracle_ref():
-    """oracle/_ref: /root/reference/lib/nms/src/cuda/nms_kernel.cu compiled in place with hipcc (recipe: oracle/Makefile `ref`).
-    Here (no GPU) only: the recipe runs where the reference tree exists, both variants export `_nms`, and the files stay out of
-    history (.gitignore) but travel to the GPU box (.gpurunignore does not list them).  The comparison itself is
-    tests/test_nms_ref_gpu.py (-m gpu)."""
+# A stand-in for the reference's lib/nms/src/cuda (same file names, written here): what the recipe must do with any such tree.
+_STANDIN_H = """#pragma once
+extern "C" int _nms(const float* x, unsigned long long* m, int n);
+"""
+_STANDIN_CU = """#include "nms_kernel.h"
+__global__ void nms_kernel(const float* x, unsigned long long* m, int n) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) m[i] = x[i] > 0.f;
+}
+extern "C" int _nms(const float* x, unsigned long long* m, int n) {
+  nms_kernel<<<(n + 63) / 64, 64>>>(x, m, n);
+  return 0;
+}
+"""
+
+
+def test_reference_nms_kernel_builds_unmodified_into_oracle_ref(tmp_path):
+    """oracle/_ref: the reference's lib/nms/src/cuda/nms_kernel.cu compiled in place with hipcc (recipe: oracle/Makefile `ref`,
+    REF = the reference tree).  Self-contained: the recipe runs on a stand-in tree written here into a copy of oracle/, both variants
+    export `_nms` and the kernel, and nothing is written into the source tree.  Where build() found the reference, the files it made
+    under oracle/_ref are checked the same way.  Those files stay out of history (.gitignore) but travel with the working tree.  The
+    comparison itself is tests/test_nms_ref_gpu.py (-m gpu)."""
     import os
+    import shutil
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.exists("/root/reference/lib/nms/src/cuda/nms_kernel.cu"):
-        pytest.skip("reference tree not present (GPU box): the prebuilt oracle/_ref files are used as they are")
-    subprocess.check_call(["make", "-s", "-C", os.path.join(root, "oracle"), "ref"])
-    for so in ("libref_nms_kernel.so", "libref_nms_kernel_nocontract.so"):
-        p = os.path.join(root, "oracle", "_ref", so)
+    src = tmp_path / "ref" / "lib" / "nms" / "src" / "cuda"
+    src.mkdir(parents=True)
+    (src / "nms_kernel.h").write_text(_STANDIN_H)
+    (src / "nms_kernel.cu").write_text(_STANDIN_CU)
+    (tmp_path / "oracle").mkdir()
+    shutil.copy(os.path.join(root, "oracle", "Makefile"), str(tmp_path / "oracle" / "Makefile"))
+    subprocess.check_call(["make", "-s", "-C", str(tmp_path / "oracle"), "ref", "REF=%s" % (tmp_path / "ref")])
+    assert sorted(os.listdir(str(src))) == ["nms_kernel.cu", "nms_kernel.h"]
+    sos = ("libref_nms_kernel.so", "libref_nms_kernel_nocontract.so")
+    paths = [str(tmp_path / "oracle" / "_ref" / so) for so in sos]
+    made = [os.path.join(root, "oracle", "_ref", so) for so in sos]
+    if any(os.path.exists(p) for p in made):
+        paths += made
+    for p in paths:
         assert os.path.exists(p), p
         syms = subprocess.check_output(["nm", "-D", "--defined-only", p]).decode()
         assert " T _nms" in syms and "nms_kernel" in syms

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 L=multiposenet/pytorch_amd/libmpn_hip.so
 for V in old new old new old new; do
   cp tools/libmpn_$V.so $L
-  timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-kernel-events 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$V', d['ms_per_step_median_hipevent'], d['ms_per_step'])"
+  timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-kernel-events 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$V', d['ms_per_step_median_hipevent'], d['ms_per_step'])"
 done
 for V in old new; do
   cp tools/libmpn_$V.so $L

@@ -7,7 +7,7 @@ TAG=${1:-pmc}; O=gpurun_out/$TAG; mkdir -p $O
 R=$GRAFT_REPO_ROOT
 cd /tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  MPN_SIDE_STREAM=0 timeout 900 rocprofv3 --kernel-trace --pmc $C -d $R/$O/$C -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-events > $R/$O/$C.out 2>&1
+  MPN_SIDE_STREAM=0 timeout 900 rocprofv3 --kernel-trace --pmc $C -d $R/$O/$C -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-events > $R/$O/$C.out 2>&1
   grep '"metric"' $R/$O/$C.out | cut -c1-200
 done
 cd $R

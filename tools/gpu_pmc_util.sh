@@ -10,7 +10,7 @@ i=0
 for G in "SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES" \
          "SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  MPN_SIDE_STREAM=0 timeout 900 rocprofv3 --kernel-trace --pmc $G -d $R/$O/g$i -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-events > $R/$O/g$i.out 2>&1
+  MPN_SIDE_STREAM=0 timeout 900 rocprofv3 --kernel-trace --pmc $G -d $R/$O/g$i -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-events > $R/$O/g$i.out 2>&1
   DB=$(find $R/$O/g$i -name "*_results.db" | head -1)
   echo "== group $i: $G" >> $R/$O/pmc_raw.txt
   [ -n "$DB" ] && python $R/tools/pmc_generic.py "$DB" >> $R/$O/pmc_raw.txt 2>&1

@@ -5,8 +5,8 @@ export TMPDIR=/tmp
 TAG=${1:-prof}; O=gpurun_out/$TAG; mkdir -p $O
 R=$GRAFT_REPO_ROOT
 cd /tmp
-MPN_SIDE_STREAM=0 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/serial -- python $R/bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-kernel-events > $R/$O/serial.out 2>&1
-timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/overlap -- python $R/bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-kernel-events > $R/$O/overlap.out 2>&1
+MPN_SIDE_STREAM=0 timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/serial -- python $R/bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-kernel-events > $R/$O/serial.out 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats -d $R/$O/overlap -- python $R/bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-kernel-events > $R/$O/overlap.out 2>&1
 cd $R
 for m in serial overlap; do
   DB=$(find $O/$m -name "*_results.db" | head -1)

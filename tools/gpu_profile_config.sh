@@ -6,9 +6,9 @@ export TMPDIR=/tmp
 TAG=$1; FLAGS=$2; O=gpurun_out/$TAG; mkdir -p $O
 R=$GRAFT_REPO_ROOT
 cd /tmp
-MPN_SIDE_STREAM=0 timeout 900 rocprofv3 --kernel-trace --stats -d $R/$O/serial -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-kernel-events $FLAGS > $R/$O/serial.out 2>&1
+MPN_SIDE_STREAM=0 timeout 900 rocprofv3 --kernel-trace --stats -d $R/$O/serial -- python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-kernel-events $FLAGS > $R/$O/serial.out 2>&1
 for C in FETCH_SIZE WRITE_SIZE; do
-  MPN_SIDE_STREAM=0 timeout 900 rocprofv3 --kernel-trace --pmc $C -d $R/$O/$C -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-events $FLAGS > $R/$O/$C.out 2>&1
+  MPN_SIDE_STREAM=0 timeout 900 rocprofv3 --kernel-trace --pmc $C -d $R/$O/$C -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-events $FLAGS > $R/$O/$C.out 2>&1
 done
 cd $R
 DB=$(find $O/serial -name "*_results.db" | head -1)
@@ -28,6 +28,6 @@ python tools/hbm_bw_table.py $O/pmc_hbm_traffic.json $O/kernel_trace_serial.txt 
 # the configuration's bench line LAST, with the instrumented passes: bench.py looks the counter file up under profiles/ by the configuration's
 # tag (config_tag: cfg2 / cfg4), so that roofline.traffic of this line names the file and the build it was just measured on
 [ -n "$3" ] && cp $O/pmc_hbm_traffic.json profiles/$3
-timeout 900 python bench.py --steps 20 --warmup 5 --no-cpu-baseline $FLAGS 2>$O/bench.err | tail -1 > $O/bench.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline $FLAGS 2>$O/bench.err | tail -1 > $O/bench.json
 rm -rf $O/serial $O/FETCH_SIZE $O/WRITE_SIZE
 cut -c1-300 $O/bench.json; head -22 $O/kernel_trace_serial.txt | cut -c1-170; head -20 $O/hbm_bandwidth_per_kernel.txt
