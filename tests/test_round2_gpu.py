@@ -489,14 +489,16 @@ def test_folded_batchnorm_inference_equals_the_separate_passes(dtype):
 
 # ------------------------------------------------------------------------------------------------ shared pixel tile of the 3x3 kernel
 @pytest.mark.parametrize("geom", [(3, 4, 4, 64, 64), (2, 8, 8, 256, 128), (2, 15, 15, 64, 256), (1, 30, 30, 128, 128), (2, 17, 33, 64, 64),
-                                  (1, 60, 60, 64, 64), (32, 30, 30, 256, 256)])
+                                  (1, 60, 60, 64, 64), (32, 30, 30, 256, 256), (4, 115, 113, 256, 256)])
 @pytest.mark.parametrize("mode", [0, 1])
 def test_3x3_kernel_with_shared_pixel_tile_is_exact_at_the_borders(geom, mode):
     """conv_igemm_s3_kernel lands the pixel tile of a kernel row once and reads it at three column shifts; the image's left / right
     border is a per-lane select, the top / bottom border a DMA-time zero fill.  bf16 operands, fp32 output (no output rounding):
     against torch's fp32 convolution of the same bf16-rounded operands the result may differ by accumulation order only — any
     border slip would be an O(1) error.  Forward and stride-1 dgrad, tiles that span several image lines (W = 4, 8, 15), lines
-    that span tiles (W = 33, 60), images that end inside a tile, the 256-row tile (last case)."""
+    that span tiles (W = 33, 60), images that end inside a tile.  Channel tile (pick_tc, asserted): 64 rows for the six small
+    geometries, 128 rows for (32, 30, 30, 256, 256) (225 pixel tiles: below the 400 workgroups of the 256-row rule), 256 rows for
+    (4, 115, 113, 256, 256) (407 pixel tiles, the last one 12 pixels) in both modes."""
     import torch.nn.functional as F
     from multiposenet.pytorch_amd import ops
     from helpers import from_act, rnd, rng_normal, to_act, w_krsc
@@ -506,7 +508,7 @@ def test_3x3_kernel_with_shared_pixel_tile_is_exact_at_the_borders(geom, mode):
     w = rnd(dt, rng_normal(32, Cout, Cin, 3, 3) / (Cin * 9) ** 0.5)
     if mode == 0:
         ref = F.conv2d(x, w, None, stride=1, padding=1)
-        out, _ = ops.conv_forward(to_act(x, dt), w_krsc(w, dt), Cout, 3, 3, 1, 1, out_f32=True)
+        run = lambda: ops.conv_forward(to_act(x, dt), w_krsc(w, dt), Cout, 3, 3, 1, 1, out_f32=True)
     else:
         dy = rnd(dt, rng_normal(33, B, Cout, H, W))
         ref = F.conv_transpose2d(dy, w, None, stride=1, padding=1)          # = dgrad of the forward convolution
@@ -515,8 +517,16 @@ def test_3x3_kernel_with_shared_pixel_tile_is_exact_at_the_borders(geom, mode):
         wm = w.permute(0, 2, 3, 1).contiguous().cuda()
         wt = torch.empty((Cin, 3, 3, cout_pad), dtype=dt, device="cuda")
         ops.weight_transpose(wm, wt, Cout, 9, Cin, cout_pad)
-        out, _ = ops.conv_forward(to_act(dy, dt), wt, Cin, 3, 3, 1, 1, mode=1, out_hw=(H, W), cin=cout_pad, out_f32=True)
+        run = lambda: ops.conv_forward(to_act(dy, dt), wt, Cin, 3, 3, 1, 1, mode=1, out_hw=(H, W), cin=cout_pad, out_f32=True)
+    ops.KERNEL_EVENTS.enable()
+    try:
+        out, _ = run()
+        names = [r[0] for r in ops.KERNEL_EVENTS.rec]
+    finally:
+        ops.KERNEL_EVENTS.disable()
     torch.cuda.synchronize()
+    tc = {(32, 30, 30, 256, 256): 128, (4, 115, 113, 256, 256): 256}.get(geom, 64)
+    assert names == ["conv_igemm_s3_kernel<bf16, %d, 128, true, false>" % tc], names
     got = from_act(out).float()
     err = float((got - ref).abs().max() / ref.abs().max())
     report("3x3 shared-pixel-tile kernel %s mode %d: max err / max |ref| = %.2e" % (str(geom), mode, err))
