@@ -400,6 +400,19 @@ int mpn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
 int mpn_adam_advance(float* hyper, void* stream);
 int mpn_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
                       void* stream);
+/* Gradient clipping by the infinity norm (the reference Trainer's max_grad_norm: torch.nn.utils.clip_grad_norm_(params, max_norm,
+ * inf)), every scalar on the device.  mpn_grad_absmax_partial reduces max |g| over one 16-byte aligned run of n floats to
+ * mpn_grad_absmax_workspace_bytes(n) / 4 partials (one launch per run, each into its own consecutive slots; a NaN anywhere gives a
+ * NaN).  mpn_grad_clip_finalize reduces nparts partials and writes *total = max (the norm torch returns) and
+ * *coef = min(reciprocal(total + 1e-6f) * *max_norm, 1) (NaN stays NaN), max_norm read from device memory.
+ * mpn_scale_by_dev does x *= *s over a 16-byte aligned run (torch scales p.grad in place); mpn_adam_step_clip_dev is
+ * mpn_scale_by_dev(grad, n, coef) followed by mpn_adam_step_dev: the update of torch's clip followed by step(), bit for bit. */
+int64_t mpn_grad_absmax_workspace_bytes(int64_t n);
+int mpn_grad_absmax_partial(const float* grad, int64_t n, float* partials, void* stream);
+int mpn_grad_clip_finalize(const float* partials, int64_t nparts, const float* max_norm, float* total, float* coef, void* stream);
+int mpn_adam_step_clip_dev(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
+                           const float* coef, void* stream);
+int mpn_scale_by_dev(float* x, int64_t n, const float* s, void* stream);
 int mpn_fill_f32(float* dst, float v, int64_t n, void* stream);
 /* device-to-device copy on the stream (gradient hand-over between two activations of equal geometry) */
 int mpn_copy_bytes(void* dst, const void* src, int64_t nbytes, void* stream);

@@ -152,6 +152,11 @@ SIGNATURES = {
     "mpn_adam_step": (_i, [_vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "mpn_adam_advance": (_i, [_vp, _vp]),
     "mpn_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mpn_grad_absmax_workspace_bytes": (_i64, [_i64]),
+    "mpn_grad_absmax_partial": (_i, [_vp, _i64, _vp, _vp]),
+    "mpn_grad_clip_finalize": (_i, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "mpn_adam_step_clip_dev": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "mpn_scale_by_dev": (_i, [_vp, _i64, _vp, _vp]),
     "mpn_fill_f32": (_i, [_vp, _f, _i64, _vp]),
     "mpn_copy_bytes": (_i, [_vp, _vp, _i64, _vp]),
     "mpn_step_log": (_i, [_vp, _vp, _vp, _vp]),
@@ -167,7 +172,7 @@ SIGNATURES = {
 
 # entry points that return a count, not a status
 _COUNT_FUNCS = {"mpn_conv_stats_tiles", "mpn_conv_tile_rows", "mpn_conv_shared_tile", "mpn_conv_wgrad_chunks", "mpn_conv_wgrad_seg_plan", "mpn_conv_wgrad_kernel_id", "mpn_bn_bwd_chunks", "mpn_channel_sum_chunks",
-                "mpn_mse_chunks", "mpn_mse_train_blocks", "mpn_focal_blocks", "mpn_bce_chunks", "mpn_nms_workspace_bytes", "mpn_nms_batched_workspace_bytes", "mpn_heatmap_peaks_workspace_bytes", "mpn_conv2cls_comb_elems", "mpn_version"}
+                "mpn_mse_chunks", "mpn_mse_train_blocks", "mpn_focal_blocks", "mpn_bce_chunks", "mpn_nms_workspace_bytes", "mpn_nms_batched_workspace_bytes", "mpn_heatmap_peaks_workspace_bytes", "mpn_conv2cls_comb_elems", "mpn_grad_absmax_workspace_bytes", "mpn_version"}
 
 _lib = None
 

@@ -297,6 +297,19 @@ extern "C" int mpn_adam_step_dev(float* param, const float* grad, float* exp_avg
     return mpn_launch_status();
 }
 
+// Adam after clipping by the infinity norm (grad_clip.hip): grad *= *coef in place, then the unchanged adam_dev_kernel.  Two launches
+// on purpose: a fused variant of the same source (measured) lets the compiler contract m = b1 m + (1 - b1) g the other way round
+// (fma(b1, m, (1 - b1) g) instead of fma(1 - b1, g, b1 m)), and its parameters then differ from torch's clip followed by step() in
+// the last bit.  The extra pass reads and writes the gradient run once more.
+extern "C" int mpn_adam_step_clip_dev(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,
+                                      const float* coef, void* stream) {
+    MPN_CHECK_ARG(param && grad && exp_avg && exp_avg_sq && hyper && coef && n > 0);
+    MPN_CHECK_ARG(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0 && (uintptr_t)coef % 4 == 0);
+    const int st = mpn_scale_by_dev(grad, n, coef, stream);
+    if (st != 0) return st;
+    return mpn_adam_step_dev(param, grad, exp_avg, exp_avg_sq, n, hyper, stream);
+}
+
 extern "C" int mpn_copy_bytes(void* dst, const void* src, int64_t nbytes, void* stream) {
     MPN_CHECK_ARG(dst && src && nbytes > 0);
     return (int)hipMemcpyAsync(dst, src, (size_t)nbytes, hipMemcpyDeviceToDevice, (hipStream_t)stream);

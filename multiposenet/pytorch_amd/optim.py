@@ -9,6 +9,10 @@ small DEVICE vector (include/mpn.h: mpn_adam_advance / mpn_adam_step_dev), so a 
 in a hipGraph (tools/archive/r2/hipgraph_step.py) replays correct Adam steps; the host only rewrites the vector when a
 scheduler changes a hyper-parameter.
 
+Gradient clipping by the infinity norm (the reference Trainer's ``max_grad_norm``, ``clip_grad_norm_(params, max_norm, inf)``)
+stays on the device too: ``clip_grad_norm_inf_`` reduces max |g| and forms the clip coefficient in two launches, and the next
+``step()`` scales the gradients right before the Adam update (mpn_adam_step_clip_dev) — no host sync between backward and Adam.
+
 ``state_dict()`` / ``load_state_dict()`` use torch.optim.Adam's own layout (per-parameter ``step``,
 ``exp_avg``, ``exp_avg_sq``), which is what the reference pickles next to a checkpoint
 (network/net_utils.py:37-46) and restores at trainer.py:228 — a checkpoint written by
@@ -20,11 +24,27 @@ import warnings
 import torch
 
 from . import ops
+from .arena import _align
 import ctypes
 
 from ._lib import call, call_raw
 
-_NH = 16       # floats in the device hyper vector (9 used)
+_NH = 16       # floats in the device hyper vector (12 used)
+_H_MAXNORM, _H_TOTAL, _H_COEF = 9, 10, 11      # clipping: max_norm (uploaded by sync_hyper), total norm, clip coefficient
+
+
+def _merge_runs(spans):
+    runs = []
+    for s, e in sorted(spans):
+        if runs and runs[-1][1] == s:
+            runs[-1] = (runs[-1][0], e)
+        else:
+            runs.append((s, e))
+    return runs
+
+
+def _lib_bytes(n):
+    return call("mpn_grad_absmax_workspace_bytes", n)
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -40,6 +60,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._hyper_sent = None      # the host values last uploaded
         self._pending_step = 0       # step count to install when the device vector is (re)created
         self.grad_scale = 1.0
+        self.max_grad_norm = math.inf  # last max_norm given to clip_grad_norm_inf_ (device copy: hyper[_H_MAXNORM])
+        self._clip_pending = False     # the next step() applies the clip coefficient
+        self._clip_key = None          # (grad arena, runs) the cached plan below was made for
+        self._clip_plan = None         # (reduction runs, stale runs, partials workspace)
 
     # ------------------------------------------------------------------ binding to the arena
     def _bind(self):
@@ -68,7 +92,8 @@ class FusedAdam(torch.optim.Optimizer):
     def _host_hyper(self):
         g = self.param_groups[0]
         b1, b2 = g["betas"]
-        return (float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), float(self.grad_scale))
+        return (float(g["lr"]), float(b1), float(b2), float(g["eps"]), float(g["weight_decay"]), float(self.grad_scale),
+                float(self.max_grad_norm))
 
     def sync_hyper(self):
         """Upload lr / betas / eps / weight decay / grad scale when they changed on the host (a scheduler step).  Outside
@@ -78,7 +103,8 @@ class FusedAdam(torch.optim.Optimizer):
         if h != self._hyper_sent:
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError("FusedAdam: hyper-parameters changed during graph capture; call sync_hyper() before capturing")
-            self._hyper[:6].copy_(torch.tensor(h, dtype=torch.float32))      # rare (scheduler step): a plain staged H2D copy
+            self._hyper[:6].copy_(torch.tensor(h[:6], dtype=torch.float32))      # rare (scheduler step): a plain staged H2D copy
+            self._hyper[_H_MAXNORM:_H_MAXNORM + 1].copy_(torch.tensor(h[6:], dtype=torch.float32))
             self._hyper_sent = h
 
     def _set_step(self, t):
@@ -121,10 +147,74 @@ class FusedAdam(torch.optim.Optimizer):
         elif self._hyper_sent is None:
             raise RuntimeError("FusedAdam: call sync_hyper() (or take one eager step) before capturing a graph")
         call("mpn_adam_advance", ops.ptr(self._hyper), ops.stream_ptr())
+        if self._clip_pending:
+            self._clip_pending = False
+            coef = ops.ptr(self._hyper[_H_COEF:])
+            for s, e in self._runs:
+                call("mpn_adam_step_clip_dev", ops.ptr(ar.flat[s:e]), ops.ptr(ar.grad_flat[s:e]), ops.ptr(self._m[s:e]),
+                     ops.ptr(self._v[s:e]), e - s, ops.ptr(self._hyper), coef, ops.stream_ptr())
+            return loss
         for s, e in self._runs:
             call("mpn_adam_step_dev", ops.ptr(ar.flat[s:e]), ops.ptr(ar.grad_flat[s:e]), ops.ptr(self._m[s:e]), ops.ptr(self._v[s:e]),
                  e - s, ops.ptr(self._hyper), ops.stream_ptr())
         return loss
+
+    # ------------------------------------------------------------------ gradient clipping by the infinity norm
+    @torch.no_grad()
+    def clip_grad_norm_inf_(self, max_norm):
+        """``torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm, inf)`` on the current stream, without a host sync.
+
+        Returns the total norm (max |g| over every parameter whose ``.grad`` is set, before clipping) as a 0-d device tensor; it is
+        a view of the optimizer's device vector, overwritten by the next call.  Gradients of parameters that are not trained (frozen
+        after an earlier step, their ``.grad`` still attached) are scaled here; the trainable ones are scaled in place by the next
+        ``step()``, just before its update.  Same bits as torch's clip followed by ``step()``."""
+        ar = self._bind()
+        ops.check_device(ar.flat)
+        if ar.grad_flat is None:
+            raise RuntimeError("FusedAdam.clip_grad_norm_inf_: no gradients yet (run backward first)")
+        self.max_grad_norm = float(max_norm)
+        if not torch.cuda.is_current_stream_capturing():
+            self.sync_hyper()
+        elif self._hyper_sent is None or self._hyper_sent[6] != self.max_grad_norm:
+            raise RuntimeError("FusedAdam: max_norm changed during graph capture; call clip_grad_norm_inf_ once before capturing")
+        runs, stale, ws = self.prepare_clip()
+        total = self._hyper[_H_TOTAL:_H_TOTAL + 1]
+        if not runs:                              # torch: no gradients -> total 0, nothing scaled
+            call("mpn_fill_f32", ops.ptr(total), 0.0, 1, ops.stream_ptr())
+            return total.view(())
+        st = ops.stream_ptr()
+        k = 0
+        for s, e in runs:
+            call("mpn_grad_absmax_partial", ops.ptr(ar.grad_flat[s:e]), e - s, ops.ptr(ws[k:]), st)
+            k += _lib_bytes(e - s) // 4
+        call("mpn_grad_clip_finalize", ops.ptr(ws), k, ops.ptr(self._hyper[_H_MAXNORM:]), ops.ptr(total),
+             ops.ptr(self._hyper[_H_COEF:]), st)
+        for s, e in stale:
+            call("mpn_scale_by_dev", ops.ptr(ar.grad_flat[s:e]), e - s, ops.ptr(self._hyper[_H_COEF:]), st)
+        self._clip_pending = True
+        return total.view(())
+
+    def prepare_clip(self):
+        """The runs a clip covers and its workspace, cached until the set of parameters with a gradient changes.  A recorded step
+        (replay.py) calls it before recording, so the workspace is not allocated inside the recording's memory pool."""
+        ar = self._bind()
+        with_grad = []
+        for i, p in enumerate(ar.params):
+            if p.grad is None:
+                continue
+            if ar.grad_flat is None or p.grad.data_ptr() != ar.grad_flat.data_ptr() + 4 * ar.offsets[i]:
+                raise RuntimeError("FusedAdam.clip_grad_norm_inf_: the gradient of %s is not in the gradient arena" % ar.names[i])
+            with_grad.append(i)
+        key = (id(ar.grad_flat), tuple(with_grad), tuple(self._runs))
+        if key != self._clip_key:
+            runs = _merge_runs([(ar.offsets[i], ar.offsets[i] + _align(ar.sizes[i])) for i in with_grad])
+            # runs with a gradient that Adam does not update (requires_grad switched off after a step): scaled on their own
+            stale = _merge_runs([(ar.offsets[i], ar.offsets[i] + _align(ar.sizes[i])) for i in with_grad
+                                 if not ar.params[i].requires_grad])
+            nparts = sum(_lib_bytes(e - s) // 4 for s, e in runs)
+            ws = torch.empty(max(nparts, 1), dtype=torch.float32, device=ar.device)
+            self._clip_plan, self._clip_key = (runs, stale, ws), key
+        return self._clip_plan
 
     # ------------------------------------------------------------------ the update, bucket by bucket (ddp.GradReducer.on_bucket)
     @torch.no_grad()

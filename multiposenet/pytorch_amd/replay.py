@@ -20,15 +20,25 @@ Same interface as ``training.batch_processor.train_step``:
     step = ReplayedTrainStep(model, optimizer)
     loss, saved_for_log = step(inputs, gts)
 
+``ReplayedTrainStep(model, optimizer, max_grad_norm=c)`` also clips the gradients by their infinity norm between backward and
+Adam, like the reference Trainer's ``clip_grad_norm(model.parameters(), c, inf)`` (its ``max_grad_norm`` option), with every
+scalar on the device (FusedAdam.clip_grad_norm_inf_: a max-abs reduction, the clip coefficient, the clipped Adam update).  The
+total norm before clipping is logged as ``max_grad``.  The coefficient needs every gradient complete, so a clipping step updates
+after backward (and, data-parallel, after the reducer's last all-reduce) instead of bucket by bucket.  ``max_norm`` is read from
+the optimizer's device vector: changing ``step.max_grad_norm`` does not re-record.
+
 The parameters after a step are bit-identical to the eager step's (same kernels, same order, same scratch sizes; the heat-map
 loss runs as one launch over the internal tensors whose gradients round exactly as the API path's export -> loss -> import chain,
 and whose logged loss values agree to f32 summation order: tests/test_replay_gpu.py).
 Re-recorded when the model moves, the set of trainable parameters / BN modes / compute dtype changes, or a new input
-signature arrives.  'prn_subnet' (host-made dropout seeds) and gradient clipping stay on the eager path.
+signature arrives.  'prn_subnet' (host-made dropout seeds) stays on the eager path.
 """
 import itertools
+import math
 import os
 from collections import OrderedDict
+
+import ctypes
 
 import torch
 
@@ -44,9 +54,14 @@ class _Entry(object):
 
 
 class ReplayedTrainStep(object):
-    def __init__(self, model, optimizer, eager_steps=1, fused_mse=None, max_entries=None, anno_bucket=8):
+    def __init__(self, model, optimizer, eager_steps=1, fused_mse=None, max_entries=None, anno_bucket=8, max_grad_norm=None):
         self.model = model
         self.opt = optimizer
+        # gradient clipping by the infinity norm (None / inf: off); needs FusedAdam's device clip
+        self.max_grad_norm = None if max_grad_norm is None or math.isinf(max_grad_norm) else float(max_grad_norm)
+        if self.max_grad_norm is not None and not hasattr(optimizer, "clip_grad_norm_inf_"):
+            raise TypeError("ReplayedTrainStep(max_grad_norm=...) needs an optimizer with a device clip (FusedAdam), got %s"
+                            % type(optimizer).__name__)
         # heat-map loss + gradients in one launch over the internal tensors (MPN_FUSED_MSE=0: the API path's kernel chain)
         self.fused_mse = (os.environ.get("MPN_FUSED_MSE", "1") != "0") if fused_mse is None else bool(fused_mse)
         # Adam bucket by bucket behind each bucket's all-reduce (ddp.GradReducer's finishing stream) instead of one launch after
@@ -112,7 +127,8 @@ class ReplayedTrainStep(object):
         if want_det:
             anno = tensors[2] if want_kp else tensors[0]
             det2, fsaved = losses.focal_forward_raw(cls, reg, m.anchors(img), anno)
-        logv = torch.zeros(12, dtype=torch.float32, device=dev)
+        clip = self.max_grad_norm is not None
+        logv = torch.zeros(13 if clip else 12, dtype=torch.float32, device=dev)
         _lib.call("mpn_step_log", ops.ptr(kp8), ops.ptr(det2), ops.ptr(logv), ops.stream_ptr())
         self.opt.zero_grad()
         if want_kp and not fused_mse:      # d(total)/d(heat-map total) = 1 (posenet.py:387 sums the level losses; the combined step adds the two totals)
@@ -126,13 +142,16 @@ class ReplayedTrainStep(object):
             sched = m._reducer if m._reducer is not None else self._local_schedule()
             eng.run_backward(ctx, grads, schedule=sched, on_bucket=self.opt.begin_bucketed())
         else:
-            eng.run_backward(ctx, grads)
+            eng.run_backward(ctx, grads)         # data-parallel: returns after the reducer's join
+            if clip:
+                total = self.opt.clip_grad_norm_inf_(self.max_grad_norm)
+                _lib.call("mpn_copy_bytes", ctypes.c_void_p(logv.data_ptr() + 4 * 12), ops.ptr(total), 4, ops.stream_ptr())
             self.opt.step()
         return logv, want_kp, want_det
 
     @property
     def bucketed_update(self):
-        if not self._can_bucket or self.bucket_mode == "0":
+        if not self._can_bucket or self.bucket_mode == "0" or self.max_grad_norm is not None:
             return False
         return self.bucket_mode == "1" or self.model._reducer is not None
 
@@ -151,13 +170,15 @@ class ReplayedTrainStep(object):
         return t
 
     @staticmethod
-    def _log_names(want_kp, want_det):
+    def _log_names(want_kp, want_det, clip=False):
         names = []
         if want_kp:
             kn = losses.build_names()
             names += [(kn[j * 2], j) for j in range(5)] + [("max_ht", 6), ("min_ht", 7)]
         if want_det:
             names += [("total_loss", 8), ("classification_loss", 9), ("regression_loss", 10)]
+        if clip:
+            names.append(("max_grad", 12))
         return names
 
     def _state_sig(self):
@@ -165,7 +186,14 @@ class ReplayedTrainStep(object):
         ar = m._arena
         return (id(ar), id(ar.grad_flat), tuple(p.requires_grad for p in ar.params), tuple(b.training for b in m._bns),
                 m.compute_dtype, id(m._reducer), m._engine.overlap_wgrad, m._engine.fork_every, id(self.opt._m), self.bucketed_update,
-                m._engine.conv2_classes, m._engine.virtual_concat)
+                m._engine.conv2_classes, m._engine.virtual_concat, self._clip_sig())
+
+    def _clip_sig(self):
+        """Clipping on/off and which parameters hold a gradient (a parameter frozen after a step keeps its .grad, and the clip
+        scales it): either changes the recorded launches.  The max_norm value does not (it is read from device memory)."""
+        if self.max_grad_norm is None:
+            return None
+        return tuple(p.grad is not None for p in self.model._arena.params)
 
     # ------------------------------------------------------------------ call
     def __call__(self, inputs, gts):
@@ -175,6 +203,9 @@ class ReplayedTrainStep(object):
             raise ValueError("inputs and gts name different subnets (%r vs %r)" % (subnet, gts[0]))
         tensors = gts[1:]
         if subnet not in ("keypoint_subnet", "detection_subnet", "train_both"):
+            if self.max_grad_norm is not None:
+                raise ValueError("recorded train step: %r is not recorded and train_step does not clip; clip it on the eager path "
+                                 "(training.trainer._Stepper does)" % (subnet,))
             from .training.batch_processor import train_step
             return train_step(self.model, self.opt, inputs, gts)
         ops.check_device(img)
@@ -200,7 +231,7 @@ class ReplayedTrainStep(object):
             self._seen[key] = n + 1
             if n < self.eager_steps:
                 logv, kp, det = self._body(img, subnet, tensors)          # plain eager execution of the same body
-                return logv[11], self._log(logv, self._log_names(kp, det))
+                return logv[11], self._log(logv, self._log_names(kp, det, self.max_grad_norm is not None))
             ent = self._record(key, img, subnet, tensors)                  # the recording IS this call's step
             return ent.loss, self._log(ent.logv, ent.names)
         if ent.img.data_ptr() != img.data_ptr():
@@ -208,6 +239,8 @@ class ReplayedTrainStep(object):
         for dst, src in zip(ent.gts, tensors):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src, non_blocking=True)
+        if self.max_grad_norm is not None:
+            self.opt.max_grad_norm = self.max_grad_norm          # uploaded by sync_hyper: the recorded clip reads it on the device
         self.opt.sync_hyper()
         for fn, args, is_c in ent.tape:
             st = fn(*args)
@@ -256,6 +289,8 @@ class ReplayedTrainStep(object):
         m = self.model
         m._arena.ensure_grads()
         self.opt.sync_hyper()
+        if self.max_grad_norm is not None:
+            self.opt.prepare_clip()          # the clip's workspace belongs to the optimizer, not to this recording's pool
         self._ones(img.device)
         ent = _Entry()
         ent.img = img if img.is_contiguous() else img.contiguous()      # the tensors of THIS call become the step's inputs
@@ -276,7 +311,7 @@ class ReplayedTrainStep(object):
             ops.KERNEL_EVENTS.on = was_on
         ent.tape, ent.pool, ent.logv = tape, pool, logv
         ent.loss = logv[11]
-        ent.names = self._log_names(kp, det)
+        ent.names = self._log_names(kp, det, self.max_grad_norm is not None)
         ent.keep = ops.take_epoch_workspaces(epoch)
         ent.sig = self._state_sig()
         self._entries[key] = ent

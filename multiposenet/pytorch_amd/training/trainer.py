@@ -9,8 +9,9 @@ under ``re_init`` / ``zero_epoch`` / ``ignore_opt_state``, the BatchNorm mode ru
 What is built differently, for one process per GPU and a device that runs a step in 40 ms:
 
   * **the step** is the recorded launch list (``replay.ReplayedTrainStep``): forward, losses, both backward streams, gradient
-    buckets and FusedAdam are re-issued from one list (host cost 5 ms instead of 19); the eager tape is used when the optimizer
-    is not ``FusedAdam``, the subnet is the PRN, or gradient clipping needs the norms on the host;
+    buckets and FusedAdam are re-issued from one list (host cost 5 ms instead of 19), gradient clipping (``max_grad_norm``)
+    included: its norm, coefficient and scaling stay on the device; the eager tape is used when the optimizer is not
+    ``FusedAdam`` or the subnet is the PRN;
   * **no per-step host sync**: the loss and the log values are fetched with asynchronous copies (``losses.LazyFloat``) and
     only become floats when a log line is formatted (every ``print_freq`` steps) — the reference reads ``loss.item()``
     and seven more ``.item()`` values per step;
@@ -246,12 +247,13 @@ class _Stepper(object):
         fused = type(optimizer).__name__ == 'FusedAdam' and hasattr(model, '_engine')
         if params.launch not in ('replay', 'eager'):
             raise ValueError("TrainParams.launch must be 'replay' or 'eager', got %r" % (params.launch,))
-        if fused and self.clip is None and params.launch == 'replay':
+        if fused and params.launch == 'replay':
             from ..replay import ReplayedTrainStep
-            self.fast = ReplayedTrainStep(model, optimizer)
+            self.fast = ReplayedTrainStep(model, optimizer, max_grad_norm=self.clip)
 
     def __call__(self, inputs, gts):
-        if self.fast is not None:
+        # the recorded step clips on the device; the PRN subnet is not recorded, and clipping it stays on the path below
+        if self.fast is not None and (self.clip is None or gts[0] != 'prn_subnet'):
             return self.fast(inputs, gts)
         model = self.model
         _, saved_for_loss = model(*inputs)
