@@ -88,6 +88,7 @@ SIGNATURES = {
     "mpn_conv_wgrad_seg_plan": (_i, [_PW]),
     "mpn_conv_wgrad": (_i, [_PW, _vp]),
     "mpn_conv_wgrad_partials": (_i, [_PW, _vp]),
+    "mpn_conv_wgrad_reduce": (_i, [_PW, _vp]),
     "mpn_conv_wgrad_kernel_id": (_i, [_PW]),
     "mpn_reduce_partials": (_i, [_vp, _i, _i64, _vp, _i, _vp]),
     "mpn_cast_f32_to_bf16": (_i, [_vp, _vp, _i64, _vp]),

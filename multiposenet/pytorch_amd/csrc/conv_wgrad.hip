@@ -728,6 +728,19 @@ __global__ void reduce_partials_small_kernel(const float* __restrict__ ws, int c
     }
 }
 
+// second stage of a split weight gradient (chunks > 1): the slices' bias partials (if fused) into db, then their weight partials into dw.
+// mpn_conv_wgrad runs it after the slices; mpn_conv_wgrad_reduce lets a caller that launched the slices alone (mpn_conv_wgrad_partials,
+// the profiler-bracketed path) finish with the same kernels in the same order, so both paths give the same bits
+inline int launch_wgrad_reduce(const MpnWgradParams& p, hipStream_t st) {
+    if (p.db) {
+        hipLaunchKernelGGL(reduce_partials_small_kernel, dim3((unsigned)((p.Cout + 15) / 16)), dim3(256), 0, st,
+                           (const float*)p.db_ws, p.chunks, (long)p.Cout, p.db, 1);
+        const int rc = mpn_launch_status();
+        if (rc != 0) return rc;
+    }
+    return launch_reduce_partials((const float*)p.ws, p.chunks, (long)p.Cout * p.R * p.S * p.Cin, p.dw, 1, st);
+}
+
 #if MPN_EXP
 unsigned long long* g_wgrad_prof = nullptr;        // tools/kloop_profile.py: [workgroups][4 waves][8] cycle sums of the next 128x128 launches
 #endif
@@ -859,15 +872,7 @@ int launch_wgrad(const MpnWgradParams& p, hipStream_t st, bool reduce = true) {
     else if (tm == 64) rc = launch_wgrad_n<T, 64>(p, tn, grid, chunk_pixels, st);
     else rc = launch_wgrad_n<T, 32>(p, tn, grid, chunk_pixels, st);
     if (rc != 0) return rc;
-    if (p.chunks > 1 && reduce) {
-        if (p.db) {
-            hipLaunchKernelGGL(reduce_partials_small_kernel, dim3((unsigned)((p.Cout + 15) / 16)), dim3(256), 0, st,
-                               (const float*)p.db_ws, p.chunks, (long)p.Cout, p.db, 1);
-            rc = mpn_launch_status();
-            if (rc != 0) return rc;
-        }
-        rc = launch_reduce_partials((const float*)p.ws, p.chunks, (long)p.Cout * p.R * p.S * p.Cin, p.dw, 1, st);
-    }
+    if (p.chunks > 1 && reduce) rc = launch_wgrad_reduce(p, st);
     return rc;
 }
 
@@ -977,6 +982,13 @@ extern "C" int mpn_conv_wgrad_partials(const MpnWgradParams* pp, void* stream) {
     if (p.dtype == MPN_F32) return launch_wgrad<float>(p, st, false);
     if (p.dtype == MPN_F16) return launch_wgrad<f16_t>(p, st, false);
     return launch_wgrad<bf16_t>(p, st, false);
+}
+
+extern "C" int mpn_conv_wgrad_reduce(const MpnWgradParams* pp, void* stream) {
+    if (!pp) return MPN_E_BADARG;
+    const MpnWgradParams& p = *pp;
+    MPN_CHECK_ARG(p.dw && p.ws && p.chunks > 1 && p.Cout > 0 && p.Cin > 0 && p.R > 0 && p.S > 0 && (!p.db || p.db_ws));
+    return launch_wgrad_reduce(p, (hipStream_t)stream);
 }
 
 extern "C" int mpn_conv_wgrad_kernel_id(const MpnWgradParams* p) {

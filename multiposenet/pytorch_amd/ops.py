@@ -288,10 +288,8 @@ def conv_wgrad_seg(xs, dys, dw, Cout, R, S, pad, db=None):
         if KERNEL_EVENTS.detail:
             name = "wgrad %dx%d %d->%d pyramid(%s) chunks=%d|0" % (R, S, x0.C, Cout, ",".join(str(x.H) for x in xs), chunks)
         KERNEL_EVENTS.end(name, sum(2.0 * x.B * x.H * x.W * Cout * R * S * x.C for x in xs), e0)
-        if chunks > 1:
-            call("mpn_reduce_partials", p.ws, chunks, Cout * R * S * x0.C, p.dw, 1, stream_ptr())
-            if fused_db:
-                call("mpn_reduce_partials", p.db_ws, chunks, Cout, p.db, 1, stream_ptr())
+        if chunks > 1:          # the reduction mpn_conv_wgrad runs (same kernels and order: the same bits as without events)
+            call("mpn_conv_wgrad_reduce", ctypes.byref(p), stream_ptr())
     else:
         call("mpn_conv_wgrad", ctypes.byref(p), stream_ptr())
     return True, fused_db
@@ -388,10 +386,8 @@ def conv_wgrad_cat(srcs, H, W, dy, dw, Cout, db=None):
         if KERNEL_EVENTS.detail:
             name = "wgrad 3x3 %d->%d @%dx%d s1 virtual-cat chunks=%d|%d" % (Cin, Cout, H, W, chunks, sum(a.t.numel() for a in srcs) * 2 + dy.t.numel() * 2)
         KERNEL_EVENTS.end(name, 2.0 * x0.B * H * W * Cout * 9 * Cin, e0)
-        if chunks > 1:
-            call("mpn_reduce_partials", p.ws, chunks, Cout * 9 * Cin, p.dw, 1, stream_ptr())
-            if fused_db:
-                call("mpn_reduce_partials", p.db_ws, chunks, Cout, p.db, 1, stream_ptr())
+        if chunks > 1:          # the reduction mpn_conv_wgrad runs (same kernels and order: the same bits as without events)
+            call("mpn_conv_wgrad_reduce", ctypes.byref(p), stream_ptr())
     else:
         call("mpn_conv_wgrad", ctypes.byref(p), stream_ptr())
     return fused_db
@@ -709,10 +705,8 @@ def conv_wgrad(x, dy, dw, Cout, R, S, stride, pad, cin=None, x_geom=None, db=Non
             name = "wgrad %dx%d %d->%d @%dx%d s%d chunks=%d|%d" % (R, S, Cin, Cout, dy.H, dy.W, stride, chunks,
                                                                  (x.B * H * W * Cin + x.B * dy.H * dy.W * dy.Cs) * es)
         KERNEL_EVENTS.end(name, 2.0 * x.B * dy.H * dy.W * Cout * R * S * Cin, e0)
-        if chunks > 1:
-            call("mpn_reduce_partials", p.ws, chunks, Cout * R * S * Cin, p.dw, 1, stream_ptr())
-            if fused_db:
-                call("mpn_reduce_partials", p.db_ws, chunks, Cout, p.db, 1, stream_ptr())
+        if chunks > 1:          # the reduction mpn_conv_wgrad runs (same kernels and order: the same bits as without events)
+            call("mpn_conv_wgrad_reduce", ctypes.byref(p), stream_ptr())
     else:
         call("mpn_conv_wgrad", ctypes.byref(p), stream_ptr())
     return fused_db

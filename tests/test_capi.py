@@ -108,6 +108,7 @@ def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
     assert L.mpn_conv_forward(None, nul) == BAD
     assert L.mpn_conv_wgrad(None, nul) == BAD
     assert L.mpn_conv_wgrad_partials(None, nul) == BAD
+    assert L.mpn_conv_wgrad_reduce(None, nul) == BAD
     p = ConvParams()                          # all-zero struct: null tensors
     assert L.mpn_conv_forward(ctypes.byref(p), nul) == BAD
     p.x, p.w, p.y = 0x1000, 0x1000, 0x1000
@@ -116,6 +117,7 @@ def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
     assert L.mpn_conv_forward(ctypes.byref(p), nul) == BAD            # Cin not a multiple of the 64-byte K chunk
     w = WgradParams()
     assert L.mpn_conv_wgrad(ctypes.byref(w), nul) == BAD
+    assert L.mpn_conv_wgrad_reduce(ctypes.byref(w), nul) == BAD          # no dw / ws, chunks 0
     assert L.mpn_reduce_partials(nul, 4, 16, one, 1, nul) == BAD
     assert L.mpn_reduce_partials(one, 0, 16, one, 1, nul) == BAD
     assert L.mpn_weight_transpose(nul, one, 8, 1, 8, 8, 1, nul) == BAD

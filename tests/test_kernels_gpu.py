@@ -194,7 +194,9 @@ def test_wgrad_partials_entry_point_matches_fused_call():
             ops.KERNEL_EVENTS.disable()
         assert torch.equal(dw, dw2)
         assert names and names[0].startswith("conv_wgrad_"), names
-        # bias gradient fused into the same kernel (ones-vector MFMA): sliced and bracketed paths, vs the column sums
+        # bias gradient fused into the same kernel (ones-vector MFMA): sliced and bracketed paths, vs the column sums; both paths
+        # run the same reduction, so db agrees bit for bit
+        dbs = []
         for events in (False, True):
             dw3 = torch.zeros_like(dw)
             db = torch.full((Cout,), 0.5, dtype=torch.float32, device="cuda")
@@ -206,6 +208,8 @@ def test_wgrad_partials_entry_point_matches_fused_call():
                 ops.KERNEL_EVENTS.disable()
             assert torch.equal(dw3, dw)
             check_close("fused bias grad %dx%d" % (Cin, Cout), db.cpu() - 0.5, dy.float().cpu().sum((0, 2, 3)), torch.float32, factor=5)
+            dbs.append(db.cpu())
+        assert torch.equal(dbs[0], dbs[1]), "fused bias grad %dx%d: bracketed path differs from the plain path" % (Cin, Cout)
         ref = torch.einsum("bohw,bihw->oi", dy.float().cpu(), x.float().cpu())
         check_close("wgrad dma tile %dx%d" % (Cin, Cout), dw.cpu().view(Cout, Cin), ref, dtype)
 
