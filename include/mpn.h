@@ -319,6 +319,17 @@ int mpn_focal_forward(const float* cls, const float* reg, const float* anchors, 
 int mpn_focal_backward(const float* cls, const float* reg, const float* anchors, const float* anno,
                        int B, int A, int maxN, const float* per_img, const float* gscale,
                        float* dcls, float* dreg, void* stream);
+/* the same for K > 1 classes (losses.py:65-77 one-hot targets): cls [B,A,K] f32 (post-sigmoid), dcls [B,A,K] with the same
+ * alignment modulo 16 bytes.  A positive anchor is 1 at class int(anno[...,4]) and 0 at the other K - 1; a class id outside [0, K)
+ * is never used as an index (such an anchor counts as negative everywhere) and bad[b] (device float[B]) receives the number of
+ * valid annotations of image b that carry one.  per_img / out / gscale as above. */
+int mpn_focal_mc_blocks(int A);   /* partial needs B * mpn_focal_mc_blocks(A) * 4 floats */
+int mpn_focal_forward_mc(const float* cls, const float* reg, const float* anchors, const float* anno, int B, int A, int K,
+                         int maxN, float* partial, float* per_img, float* bad, float* out, void* stream);
+int mpn_focal_backward_mc(const float* cls, const float* reg, const float* anchors, const float* anno, int B, int A, int K,
+                          int maxN, const float* per_img, const float* gscale, float* dcls, float* dreg, void* stream);
+/* score[b,a] = max_k cls[b,a,k], cls_id[b,a] = index of the first maximum (torch.max(dim) ties, posenet.py:267,283); K < 4096 */
+int mpn_class_max(const float* cls, int B, int A, int K, float* score, int64_t* cls_id, void* stream);
 int mpn_sigmoid_forward(const float* x, float* y, int64_t n, void* stream);   /* in place allowed */
 /* dlogit = dp * p * (1-p) */
 int mpn_sigmoid_backward(const float* dp, const float* p, float* dlogit, int64_t n, void* stream);
@@ -361,6 +372,10 @@ int mpn_gather_dets(const float* dets, const int64_t* keep, int k, float* boxes,
  * image's candidate block dets + b*dets_stride (floats); kmax >= max num[b] sizes the launch */
 int mpn_gather_dets_batched(const float* dets, int64_t dets_stride, const int64_t* keep, int64_t keep_stride, const int64_t* num,
                             int B, int kmax, float* boxes, float* scores, int64_t out_stride, void* stream);
+/* class ids of the kept detections (posenet.py:283): out[b*out_stride + i] = cls_id[b*A + src[b*A + keep[b*keep_stride + i]]] for
+ * i < num[b], 0 for num[b] <= i < kmax; src = the anchor indices mpn_score_filter(_batched) recorded.  num == NULL (B == 1): kmax rows */
+int mpn_gather_class(const int64_t* cls_id, const int32_t* src, int A, const int64_t* keep, int64_t keep_stride,
+                     const int64_t* num, int B, int kmax, int64_t* out, int64_t out_stride, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * NMS — replaces lib/nms: gpu_nms (src/nms_cuda.c:17-67), _nms/nms_kernel

@@ -130,6 +130,10 @@ SIGNATURES = {
     "mpn_focal_blocks": (_i, [_i]),
     "mpn_focal_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mpn_focal_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mpn_focal_mc_blocks": (_i, [_i]),
+    "mpn_focal_forward_mc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mpn_focal_backward_mc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mpn_class_max": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "mpn_sigmoid_forward": (_i, [_vp, _vp, _i64, _vp]),
     "mpn_gather_dets": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "mpn_sigmoid_backward": (_i, [_vp, _vp, _vp, _i64, _vp]),
@@ -145,6 +149,7 @@ SIGNATURES = {
     "mpn_score_filter": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
     "mpn_score_filter_batched": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "mpn_gather_dets_batched": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _vp, _i64, _vp]),
+    "mpn_gather_class": (_i, [_vp, _vp, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp]),
     "mpn_nms_batched_workspace_bytes": (_i64, [_i, _i64]),
     "mpn_nms_batched": (_i, [_vp, _i64, _vp, _i, _i64, _f, _i, _vp, _i64, _vp, _vp, _vp]),
     "mpn_nms_batched_topk": (_i, [_vp, _i64, _vp, _i, _i64, _i64, _f, _i, _vp, _i64, _vp, _vp, _vp]),
@@ -173,7 +178,7 @@ SIGNATURES = {
 
 # entry points that return a count, not a status
 _COUNT_FUNCS = {"mpn_conv_stats_tiles", "mpn_conv_tile_rows", "mpn_conv_shared_tile", "mpn_conv_wgrad_chunks", "mpn_conv_wgrad_seg_plan", "mpn_conv_wgrad_kernel_id", "mpn_bn_bwd_chunks", "mpn_channel_sum_chunks",
-                "mpn_mse_chunks", "mpn_mse_train_blocks", "mpn_focal_blocks", "mpn_bce_chunks", "mpn_nms_workspace_bytes", "mpn_nms_batched_workspace_bytes", "mpn_heatmap_peaks_workspace_bytes", "mpn_conv2cls_comb_elems", "mpn_grad_absmax_workspace_bytes", "mpn_version"}
+                "mpn_mse_chunks", "mpn_mse_train_blocks", "mpn_focal_blocks", "mpn_focal_mc_blocks", "mpn_bce_chunks", "mpn_nms_workspace_bytes", "mpn_nms_batched_workspace_bytes", "mpn_heatmap_peaks_workspace_bytes", "mpn_conv2cls_comb_elems", "mpn_grad_absmax_workspace_bytes", "mpn_version"}
 
 _lib = None
 

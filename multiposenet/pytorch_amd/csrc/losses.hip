@@ -387,6 +387,231 @@ __global__ void focal_bwd_kernel(const float* __restrict__ cls, const float* __r
     *reinterpret_cast<float4*>(dreg + ((long)b * A + a) * 4) = make_float4(dr[0], dr[1], dr[2], dr[3]);
 }
 
+// ------------------------------------------------------------------------- multi-class focal loss
+// losses.py:27-137 with K > 1 classes: one-hot targets (IoU >= .5: 1 at the annotation's class, 0 at the other K - 1; IoU < .4: 0
+// everywhere; between: ignored).  A block owns FMC_TILE anchors of one image.  Its lanes first assign one anchor each (the state goes
+// to LDS, the smooth-L1 term stays in the lane), then the block streams the anchors' contiguous [FMC_TILE x K] slice of cls with
+// 16-byte accesses: no lane walks a K-float row of its own.
+constexpr int FMC_TILE = 256;
+constexpr int FMC_IGNORE = -1;      // anchor state in LDS: ignored, negative at every class, or (>= 0) positive at that class;
+constexpr int FMC_NEG = -2;         // a positive whose class id lies outside [0, K) is stored as K and matches no column
+
+// int(anno[..., 4]) (losses.py:77 .long(), truncation) when it lies in [0, K), else K (NaN included)
+__device__ __forceinline__ int focal_class(float c, int K) {
+    const float t = truncf(c);
+    return (t >= 0.f && t < (float)K) ? (int)t : K;
+}
+
+// Lane t of the block visits the elements [0, n) of a slice of rows of K floats: the scalar head up to a 16-byte boundary of src,
+// a float4 body, a scalar tail.  f(r, c, x) gets the element's row and column within the slice and its value: one division per
+// float4, then the column steps.  STORE: f's result goes to the same element of dst (same address as src modulo 16 bytes).
+template <bool STORE, typename F>
+__device__ __forceinline__ void stream_rows(const float* __restrict__ src, float* __restrict__ dst, int n, int K, F f) {
+    const int t = threadIdx.x;
+    const unsigned uK = (unsigned)K;
+    int head = (int)(((16u - ((unsigned)(uintptr_t)src & 15u)) & 15u) >> 2);
+    head = head < n ? head : n;
+    auto one = [&](int e) {
+        const unsigned r = (unsigned)e / uK;
+        const float y = f((int)r, (int)((unsigned)e - r * uK), src[e]);
+        if (STORE) dst[e] = y;
+    };
+    if (t < head) one(t);
+    const int nv = (n - head) >> 2;
+    const float4* __restrict__ v = reinterpret_cast<const float4*>(src + head);
+    auto quad = [&](int i, const float4 x) {
+        const unsigned e = (unsigned)(head + 4 * i);
+        int r = (int)(e / uK), c = (int)(e - (unsigned)r * uK);
+        const float xs[4] = {x.x, x.y, x.z, x.w};
+        float y[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            y[j] = f(r, c, xs[j]);
+            if (++c == K) { c = 0; ++r; }
+        }
+        if (STORE) reinterpret_cast<float4*>(dst + head)[i] = make_float4(y[0], y[1], y[2], y[3]);
+    };
+    // two 16-byte loads in flight per lane
+    const int stride = blockDim.x;
+    int i = t;
+    for (; i + stride < nv; i += 2 * stride) {
+        const float4 x0 = v[i], x1 = v[i + stride];
+        quad(i, x0);
+        quad(i + stride, x1);
+    }
+    if (i < nv) quad(i, v[i]);
+    const int e = head + 4 * nv + t;
+    if (e < n) one(e);
+}
+
+// per image: valid annotations and those among them whose class id lies outside [0, K)
+__device__ __forceinline__ void focal_count_anno(const float* __restrict__ an, int maxN, int K, int& nvalid, int& nbad) {
+    nvalid = 0; nbad = 0;
+    for (int n = 0; n < maxN; ++n) {
+        const float c = an[n * 5 + 4];
+        if (c == -1.f) continue;
+        ++nvalid;
+        nbad += focal_class(c, K) == K;
+    }
+}
+
+// grid (mpn_focal_mc_blocks(A), B); partial as focal_fwd_kernel's; bad[b] = annotations of image b with a class outside [0, K)
+__global__ void __launch_bounds__(FMC_TILE) focal_fwd_mc_kernel(const float* __restrict__ cls, const float* __restrict__ reg,
+        const float* __restrict__ anchors, const float* __restrict__ anno, int A, int K, int maxN, float* __restrict__ partial,
+        float* __restrict__ bad) {
+    __shared__ int st[FMC_TILE];
+    __shared__ float sh[4][3];
+    const int b = blockIdx.y, a0 = blockIdx.x * FMC_TILE, t = threadIdx.x;
+    const float* an = anno + (long)b * maxN * 5;
+    int nvalid, nbad;
+    focal_count_anno(an, maxN, K, nvalid, nbad);
+    float cl = 0.f, rl = 0.f, np = 0.f;
+    int s = FMC_IGNORE;
+    const int a = a0 + t;
+    if (a < A && nvalid > 0) {
+        const float4 box = *reinterpret_cast<const float4*>(anchors + (long)a * 4);
+        const Assign as = assign_anchor(box, an, maxN);
+        if (as.iou_max >= 0.5f) {
+            s = focal_class(an[as.arg * 5 + 4], K);
+            np = 1.f;
+            float tg[4]; reg_targets(box, an + as.arg * 5, tg);
+            const float4 r = *reinterpret_cast<const float4*>(reg + ((long)b * A + a) * 4);
+            const float rr[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float d = fabsf(tg[k] - rr[k]);
+                rl += (d <= 1.0f / 9.0f) ? 0.5f * 9.0f * d * d : d - 0.5f / 9.0f;
+            }
+        } else if (as.iou_max < 0.4f) {
+            s = FMC_NEG;
+        }
+    }
+    st[t] = s;
+    __syncthreads();
+    if (nvalid > 0) {
+        const int na = min(FMC_TILE, A - a0);
+        stream_rows<false>(cls + ((long)b * A + a0) * K, nullptr, na * K, K, [&](int r, int c, float x) -> float {
+            const int sa = st[r];
+            if (sa == FMC_IGNORE) return 0.f;
+            const float p = fminf(fmaxf(x, 1e-4f), 1.0f - 1e-4f);
+            if (sa == c) {
+                const float om = 1.f - p;
+                cl += 0.25f * (om * om) * (-logf(p));
+            } else {
+                cl += 0.75f * (p * p) * (-logf(1.f - p));
+            }
+            return 0.f;
+        });
+    }
+    cl = wave_sum(cl); rl = wave_sum(rl); np = wave_sum(np);
+    const int lane = t & 63, wave = t >> 6;
+    if (lane == 0) { sh[wave][0] = cl; sh[wave][1] = rl; sh[wave][2] = np; }
+    __syncthreads();
+    if (t == 0) {
+        float* o = partial + ((long)b * gridDim.x + blockIdx.x) * 4;
+        o[0] = sh[0][0] + sh[1][0] + sh[2][0] + sh[3][0];
+        o[1] = sh[0][1] + sh[1][1] + sh[2][1] + sh[3][1];
+        o[2] = sh[0][2] + sh[1][2] + sh[2][2] + sh[3][2];
+        o[3] = (float)nvalid;
+        if (blockIdx.x == 0) bad[b] = (float)nbad;
+    }
+}
+
+// grid (mpn_focal_mc_blocks(A), B): dcls [B,A,K] (every element written), dreg [B,A,4]; ((cls ^ dcls) & 15) == 0
+__global__ void __launch_bounds__(FMC_TILE) focal_bwd_mc_kernel(const float* __restrict__ cls, const float* __restrict__ reg,
+        const float* __restrict__ anchors, const float* __restrict__ anno, int B, int A, int K, int maxN,
+        const float* __restrict__ per_img, const float* __restrict__ gscale, float* __restrict__ dcls, float* __restrict__ dreg) {
+    __shared__ int st[FMC_TILE];
+    const int b = blockIdx.y, a0 = blockIdx.x * FMC_TILE, t = threadIdx.x;
+    const float gs = gscale ? gscale[0] : 1.f;
+    const float gsr = gscale ? gscale[1] : 1.f;
+    const float* an = anno + (long)b * maxN * 5;
+    const float npos = per_img[b * 4 + 2], nvalid = per_img[b * 4 + 3];
+    int s = FMC_IGNORE;
+    const int a = a0 + t;
+    if (a < A) {
+        float dr[4] = {0.f, 0.f, 0.f, 0.f};
+        if (nvalid > 0.f) {
+            const float4 box = *reinterpret_cast<const float4*>(anchors + (long)a * 4);
+            const Assign as = assign_anchor(box, an, maxN);
+            if (as.iou_max >= 0.5f) {
+                s = focal_class(an[as.arg * 5 + 4], K);
+                float tg[4]; reg_targets(box, an + as.arg * 5, tg);
+                const float4 r = *reinterpret_cast<const float4*>(reg + ((long)b * A + a) * 4);
+                const float rr[4] = {r.x, r.y, r.z, r.w};
+                const float kr = gsr / ((float)B * 4.f * npos);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float e = rr[k] - tg[k];
+                    const float d = fabsf(e);
+                    dr[k] = kr * ((d <= 1.0f / 9.0f) ? 9.0f * e : (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)));
+                }
+            } else if (as.iou_max < 0.4f) {
+                s = FMC_NEG;
+            }
+        }
+        *reinterpret_cast<float4*>(dreg + ((long)b * A + a) * 4) = make_float4(dr[0], dr[1], dr[2], dr[3]);
+    }
+    st[t] = s;
+    __syncthreads();
+    const int na = min(FMC_TILE, A - a0);
+    const long base = ((long)b * A + a0) * K;
+    const float kc = gs / ((float)B * fmaxf(npos, 1.f));
+    stream_rows<true>(cls + base, dcls + base, na * K, K, [&](int r, int c, float x) -> float {
+        const int sa = st[r];
+        if (sa == FMC_IGNORE || !((x >= 1e-4f) && (x <= 1.0f - 1e-4f))) return 0.f;     // clamp passes gradient inside [min, max]
+        const float p = x;
+        if (sa == c) {
+            const float om = 1.f - p;
+            return kc * 0.25f * (2.f * om * logf(p) - om * om / p);
+        }
+        return kc * 0.75f * (-2.f * p * logf(1.f - p) + p * p / (1.f - p));
+    });
+}
+
+// ------------------------------------------------------------------------- class maximum
+// posenet.py:267 / :283: max over the K classes of every anchor and the index of the first maximum (torch.max(dim) ties; a NaN
+// wins, the first NaN).  A block stages R whole rows through LDS (coalesced 16-byte loads; row stride K + 1 words spreads the
+// banks), then 256 / R lanes reduce each row and combine with shuffles.
+__device__ __forceinline__ bool cmax_better(float v2, int i2, float v1, int i1) {
+    const bool n2 = v2 != v2, n1 = v1 != v1;
+    if (n2 != n1) return n2;
+    if (n2) return i2 < i1;
+    return v2 > v1 || (v2 == v1 && i2 < i1);
+}
+
+__global__ void __launch_bounds__(256) class_max_kernel(const float* __restrict__ cls, long rows, int K, int R,
+                                                        float* __restrict__ score, int64_t* __restrict__ cls_id) {
+    extern __shared__ float rows_lds[];
+    const long r0 = (long)blockIdx.x * R;
+    const int nr = (int)min((long)R, rows - r0);
+    const int ld = K + 1;
+    stream_rows<false>(cls + r0 * K, nullptr, nr * K, K, [&](int r, int c, float x) -> float {
+        rows_lds[r * ld + c] = x;
+        return 0.f;
+    });
+    __syncthreads();
+    const int L = 256 / R;                 // lanes per row: a power of two <= 64, so a row's lanes sit in one wave
+    const int row = threadIdx.x / L, j = threadIdx.x % L;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    if (row < nr) {
+        for (int c = j; c < K; c += L) {
+            const float v = rows_lds[row * ld + c];
+            if (cmax_better(v, c, best, bi)) { best = v; bi = c; }
+        }
+    }
+    for (int m = L >> 1; m >= 1; m >>= 1) {
+        const float v2 = __shfl_xor(best, m, 64);
+        const int i2 = __shfl_xor(bi, m, 64);
+        if (cmax_better(v2, i2, best, bi)) { best = v2; bi = i2; }
+    }
+    if (row < nr && j == 0) {
+        score[r0 + row] = best;
+        cls_id[r0 + row] = (int64_t)bi;
+    }
+}
+
 __global__ void sigmoid_bwd_kernel(const float* __restrict__ dp, const float* __restrict__ p, float* __restrict__ dl, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { const float pv = p[i]; dl[i] = dp[i] * pv * (1.f - pv); }
@@ -563,6 +788,41 @@ extern "C" int mpn_focal_backward(const float* cls, const float* reg, const floa
     MPN_CHECK_ARG(cls && reg && anchors && anno && per_img && dcls && dreg && B > 0 && A > 0 && maxN > 0);
     hipLaunchKernelGGL(focal_bwd_kernel, dim3((A + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, cls, reg, anchors, anno, B, A, maxN,
                        per_img, gscale, dcls, dreg);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_focal_mc_blocks(int A) { return (A + FMC_TILE - 1) / FMC_TILE; }
+
+extern "C" int mpn_focal_forward_mc(const float* cls, const float* reg, const float* anchors, const float* anno, int B, int A, int K,
+                                    int maxN, float* partial, float* per_img, float* bad, float* out, void* stream) {
+    MPN_CHECK_ARG(cls && reg && anchors && anno && partial && per_img && bad && out && B > 0 && A > 0 && K > 0 && maxN > 0);
+    MPN_CHECK_ARG((int64_t)FMC_TILE * K < (int64_t)1 << 31);
+    const int blocksA = mpn_focal_mc_blocks(A);
+    hipLaunchKernelGGL(focal_fwd_mc_kernel, dim3(blocksA, B), dim3(FMC_TILE), 0, (hipStream_t)stream, cls, reg, anchors, anno, A, K, maxN,
+                       partial, bad);
+    hipLaunchKernelGGL(focal_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, B, blocksA, per_img, out);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_focal_backward_mc(const float* cls, const float* reg, const float* anchors, const float* anno, int B, int A, int K,
+                                     int maxN, const float* per_img, const float* gscale, float* dcls, float* dreg, void* stream) {
+    MPN_CHECK_ARG(cls && reg && anchors && anno && per_img && dcls && dreg && B > 0 && A > 0 && K > 0 && maxN > 0);
+    MPN_CHECK_ARG((int64_t)FMC_TILE * K < (int64_t)1 << 31);
+    MPN_CHECK_ARG((((uintptr_t)cls ^ (uintptr_t)dcls) & 15) == 0 && ((uintptr_t)cls & 3) == 0);
+    hipLaunchKernelGGL(focal_bwd_mc_kernel, dim3(mpn_focal_mc_blocks(A), B), dim3(FMC_TILE), 0, (hipStream_t)stream, cls, reg, anchors,
+                       anno, B, A, K, maxN, per_img, gscale, dcls, dreg);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_class_max(const float* cls, int B, int A, int K, float* score, int64_t* cls_id, void* stream) {
+    MPN_CHECK_ARG(cls && score && cls_id && B > 0 && A > 0 && K > 0 && K < 4096 && ((uintptr_t)cls & 3) == 0);
+    int R = 256;                                              // rows per block: the staged rows fill at most 32 KB (64 KB for K > 2047)
+    while (R > 4 && (long)R * (K + 1) * 4 > 32768) R >>= 1;
+    const long rows = (long)B * A;
+    const long blocks = (rows + R - 1) / R;
+    MPN_CHECK_ARG(blocks < (1L << 31));
+    hipLaunchKernelGGL(class_max_kernel, dim3((unsigned)blocks), dim3(256), (size_t)R * (K + 1) * 4, (hipStream_t)stream, cls, rows, K, R,
+                       score, cls_id);
     return mpn_launch_status();
 }
 

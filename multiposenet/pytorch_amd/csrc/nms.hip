@@ -257,6 +257,20 @@ __global__ void gather_dets_kernel(const float* __restrict__ dets_all, long dets
     scores_all[(long)b * out_stride + i] = s[4];
 }
 
+// class id of every kept detection (posenet.py:283): out[b, i] = cls_id[b, src[b, keep[b, i]]] for i < k, 0 for k <= i < kmax;
+// src[b*A ...] are the anchor indices the score filter recorded, image = blockIdx.y, k = num[image] when num != NULL
+__global__ void gather_class_kernel(const int64_t* __restrict__ cls_id, const int* __restrict__ src, int A, const int64_t* __restrict__ keep,
+                                    long keep_stride, const int64_t* __restrict__ num, int k_host, int kmax, int64_t* __restrict__ out,
+                                    long out_stride) {
+    const int b = blockIdx.y;
+    const int k = num ? (int)num[b] : k_host;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= kmax) return;
+    int64_t c = 0;
+    if (i < k) c = cls_id[(long)b * A + src[(long)b * A + keep[(long)b * keep_stride + i]]];
+    out[(long)b * out_stride + i] = c;
+}
+
 inline long align_up(long v, long a) { return (v + a - 1) / a * a; }
 
 }  // namespace
@@ -313,6 +327,14 @@ extern "C" int mpn_gather_dets_batched(const float* dets, int64_t dets_stride, c
     MPN_CHECK_ARG(dets && keep && num && boxes && scores && B > 0 && kmax > 0 && out_stride >= kmax);
     hipLaunchKernelGGL(gather_dets_kernel, dim3((kmax + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, dets, (long)dets_stride, keep,
                        (long)keep_stride, num, 0, boxes, scores, (long)out_stride);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_gather_class(const int64_t* cls_id, const int32_t* src, int A, const int64_t* keep, int64_t keep_stride,
+                                const int64_t* num, int B, int kmax, int64_t* out, int64_t out_stride, void* stream) {
+    MPN_CHECK_ARG(cls_id && src && keep && out && A > 0 && B > 0 && kmax > 0 && out_stride >= kmax && (num || B == 1));
+    hipLaunchKernelGGL(gather_class_kernel, dim3((kmax + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, cls_id, src, A, keep,
+                       (long)keep_stride, num, kmax, kmax, out, (long)out_stride);
     return mpn_launch_status();
 }
 

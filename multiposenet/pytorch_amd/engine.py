@@ -16,7 +16,7 @@ import os
 import torch
 
 from . import ops
-from ._lib import call, gpu_op
+from ._lib import MpnError, call, gpu_op
 from .ops import Act, round_up
 
 
@@ -63,6 +63,14 @@ class Ctx(object):
 
     def pop_grad(self, act):
         return self.grads.pop(id(act), None)
+
+
+def num_classes(cm):
+    """Classes of a ClassificationModel: its output convolution has 9 * K channels (9 anchors per cell, anchors.py)."""
+    cout = cm.output.weight.shape[0]
+    if cout % 9 != 0 or cout == 0 or getattr(cm, "num_anchors", 9) != 9:
+        raise MpnError("classificationModel: the output convolution has %d channels; the detector needs 9 anchors x K classes" % cout)
+    return cout // 9
 
 
 def _geom(layer):
@@ -994,18 +1002,20 @@ class Engine(object):
             ctx.fwd_side_join = False
 
     def detection_head(self, ctx, feats):
-        """posenet.py:327-328: shared towers over p3..p7, outputs written straight into [B,A,4] / [B,A,1]."""
+        """posenet.py:327-328: shared towers over p3..p7, outputs written straight into [B,A,4] / [B,A,K]; K = the classification
+        head's output channels / 9 (ClassificationModel(num_classes=K), posenet.py:72-117)."""
         self.join_forward_side(ctx, feats[0].t.device)
         m = self.m
         B = feats[0].B
         dev = feats[0].t.device
         cells = [f.H * f.W for f in feats]
         A = 9 * sum(cells)
+        rm, cm = m.regressionModel, m.classificationModel
+        K = num_classes(cm)
         reg_all = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
-        cls_all = torch.empty((B, A, 1), dtype=torch.float32, device=dev)
+        cls_all = torch.empty((B, A, K), dtype=torch.float32, device=dev)
         outs = []
         off = 0
-        rm, cm = m.regressionModel, m.classificationModel
         if self.pyramid_towers and len(feats) > 1:
             r = c = feats
             for layer in (rm.conv1, rm.conv2, rm.conv3, rm.conv4):
@@ -1029,10 +1039,10 @@ class Engine(object):
                 co, _ = self.conv(ctx, c, cm.output, out_f32=True)
                 outs.append((ro, co, off, n))
                 off += n * 9
-        # pack the per-level outputs, then one sigmoid over [B,A,1] (its backward needs only p)
+        # pack the per-level outputs, then one sigmoid over [B,A,K] (its backward needs only p)
         for ro, co, o, n in outs:
             call("mpn_det_pack", ops.ptr(ro.t), 0, ctypes.c_void_p(reg_all.data_ptr() + o * 4 * 4), B, n, ro.Cs, 36, A * 4, ops.stream_ptr())
-            call("mpn_det_pack", ops.ptr(co.t), 0, ctypes.c_void_p(cls_all.data_ptr() + o * 4), B, n, co.Cs, 9, A, ops.stream_ptr())
+            call("mpn_det_pack", ops.ptr(co.t), 0, ctypes.c_void_p(cls_all.data_ptr() + o * K * 4), B, n, co.Cs, 9 * K, A * K, ops.stream_ptr())
         call("mpn_sigmoid_forward", ops.ptr(cls_all), ops.ptr(cls_all), cls_all.numel(), ops.stream_ptr())
         if ctx.train:
             if any(x[0].needs_grad or x[1].needs_grad for x in outs):
@@ -1046,15 +1056,15 @@ class Engine(object):
                         gr = gr.contiguous()
                     # output gradients of all levels in one buffer per tower (the pyramid backward consumes them in one launch)
                     dros = ops.alloc_seg([x[0] for x in outs], 36, self.cdt)
-                    dcos = ops.alloc_seg([x[1] for x in outs], 9, self.cdt)
+                    dcos = ops.alloc_seg([x[1] for x in outs], 9 * K, self.cdt)
                     for (ro, co, o, n), dr, dc in zip(outs, dros, dcos):
                         if gr is not None and ro.needs_grad:
                             call("mpn_det_unpack", ctypes.c_void_p(gr.data_ptr() + o * 4 * 4), ops.ptr(dr.t), ops.dtype_code(self.cdt),
                                  B, n, dr.Cs, 36, A * 4, ops.stream_ptr())
                             ctx.set_grad(ro, dr)
                         if gc is not None and co.needs_grad:
-                            call("mpn_det_unpack", ctypes.c_void_p(dlogit.data_ptr() + o * 4), ops.ptr(dc.t), ops.dtype_code(self.cdt),
-                                 B, n, dc.Cs, 9, A, ops.stream_ptr())
+                            call("mpn_det_unpack", ctypes.c_void_p(dlogit.data_ptr() + o * K * 4), ops.ptr(dc.t), ops.dtype_code(self.cdt),
+                                 B, n, dc.Cs, 9 * K, A * K, ops.stream_ptr())
                             ctx.set_grad(co, dc)
                 ctx.tape.append(bwd)
         return cls_all, reg_all

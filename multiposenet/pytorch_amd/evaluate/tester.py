@@ -280,7 +280,9 @@ class Tester(object):
         from ..network.joint_utils import NMS_batch_arrays, body_peaks_flat
         from .prn_process import prn_assign_arrays
         S = self.params.inp_size
-        boxes, scores, kept = self.model.detect_padded(anchors, cls)
+        multi = cls.shape[-1] > 1
+        det = self.model.detect_padded(anchors, cls, return_class=multi)
+        boxes, scores, kept = det[:3]
         pk, cnt = NMS_batch_arrays({'thre1': 0.1}, heat, float(S) / heat.shape[2])
         peaks_xy, joint_off = body_peaks_flat(pk, cnt)
         sc = np.asarray(scales)
@@ -288,11 +290,12 @@ class Tester(object):
         peaks_xy = peaks_xy * np.repeat(sc, per_img)[:, None]                             # get_joint_list: peaks * scale
         nmax = boxes.shape[1]
         if nmax:
-            # score > 0.5 among the kept rows (the single class is class 0 = person: forward_all_images_padded refuses anything else,
-            # so the reference's `classification == 0` filter, tester.py:232, holds by construction); masks built on the host from the
-            # two arrays that travel anyway
+            # score > 0.5 among the kept rows of class 0 = person (the reference's `classification == 0` filter, tester.py:232; a
+            # single-class head has no other class); masks built on the host from the arrays that travel anyway
             scores_h, boxes_h = scores.cpu().numpy(), boxes.cpu().numpy()
             ok_h = (scores_h > 0.5) & (np.arange(nmax)[None, :] < np.asarray(kept)[:, None])
+            if multi:
+                ok_h &= det[3].cpu().numpy() == 0
         else:
             ok_h, boxes_h = np.zeros((len(idx), 0), dtype=bool), np.zeros((len(idx), 0, 4), dtype=np.float32)
         # boxes * scale in float32 like the reference's numpy expression (tester.py:228-234), image-major

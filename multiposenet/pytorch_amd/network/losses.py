@@ -276,34 +276,51 @@ def build_keypoint_loss(saved_for_loss, heat_temp, heat_weight):
 
 
 def focal_forward_raw(cls, reg, anchors, anno):
-    """Returns (out[2] = {classification loss, regression loss}, saved operands for focal_backward_raw)."""
-    B, A = cls.shape[0], cls.shape[1]
-    if cls.shape[2] != 1:
-        raise NotImplementedError("the hot path is single-class (posenet.py:189 num_classes=1)")
+    """Returns (out[2] = {classification loss, regression loss}, saved operands for focal_backward_raw).  cls [B,A,K]: K = 1 runs the
+    single-class kernels, K > 1 the multi-class ones (one-hot targets, losses.py:65-77); for those the saved operands end with bad [B],
+    the number of valid annotations of each image whose class id lies outside [0, K) (FocalLoss raises on it)."""
+    B, A, K = cls.shape[0], cls.shape[1], cls.shape[2]
     dev = cls.device
     c = cls.detach().float().contiguous()
     r = reg.detach().float().contiguous()
     an = anchors.detach().float().reshape(-1, 4).contiguous()
     ann = anno.detach().float().contiguous()
     maxn = ann.shape[1]
-    blocks = call("mpn_focal_blocks", A)
+    if K == 1:
+        blocks = call("mpn_focal_blocks", A)
+        part = ops.workspace(B * blocks * 4 * 4, dev, slot=6)
+        per_img = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+        call("mpn_focal_forward", ops.ptr(c), ops.ptr(r), ops.ptr(an), ops.ptr(ann), B, A, maxn, ops.ptr(part), ops.ptr(per_img),
+             ops.ptr(out), ops.stream_ptr())
+        return out, (c, r, an, ann, per_img)
+    if c.data_ptr() % 16 != 0:
+        # the backward streams cls and its fresh dcls with the same 16-byte split (mpn_focal_backward_mc); a view that starts inside
+        # a 16-byte group (cls[1:] of an odd A * K) gets its own copy
+        c = c.clone()
+    blocks = call("mpn_focal_mc_blocks", A)
     part = ops.workspace(B * blocks * 4 * 4, dev, slot=6)
     per_img = torch.empty((B, 4), dtype=torch.float32, device=dev)
     out = torch.empty(2, dtype=torch.float32, device=dev)
-    call("mpn_focal_forward", ops.ptr(c), ops.ptr(r), ops.ptr(an), ops.ptr(ann), B, A, maxn, ops.ptr(part), ops.ptr(per_img),
-         ops.ptr(out), ops.stream_ptr())
-    return out, (c, r, an, ann, per_img)
+    bad = torch.empty(B, dtype=torch.float32, device=dev)
+    call("mpn_focal_forward_mc", ops.ptr(c), ops.ptr(r), ops.ptr(an), ops.ptr(ann), B, A, K, maxn, ops.ptr(part), ops.ptr(per_img),
+         ops.ptr(bad), ops.ptr(out), ops.stream_ptr())
+    return out, (c, r, an, ann, per_img, bad)
 
 
 def focal_backward_raw(saved, gs):
-    """gs: device float[2] = upstream gradients of {cls loss, reg loss}.  Returns (dcls [B,A,1], dreg [B,A,4])."""
-    c, r, an, ann, per_img = saved
-    B, A = c.shape[0], c.shape[1]
+    """gs: device float[2] = upstream gradients of {cls loss, reg loss}.  Returns (dcls [B,A,K], dreg [B,A,4])."""
+    c, r, an, ann, per_img = saved[:5]
+    B, A, K = c.shape[0], c.shape[1], c.shape[2]
     dev = c.device
-    dcls = torch.empty((B, A, 1), dtype=torch.float32, device=dev)
+    dcls = torch.empty((B, A, K), dtype=torch.float32, device=dev)
     dreg = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
-    call("mpn_focal_backward", ops.ptr(c), ops.ptr(r), ops.ptr(an), ops.ptr(ann), B, A, ann.shape[1], ops.ptr(per_img),
-         ops.ptr(gs), ops.ptr(dcls), ops.ptr(dreg), ops.stream_ptr())
+    if K == 1:
+        call("mpn_focal_backward", ops.ptr(c), ops.ptr(r), ops.ptr(an), ops.ptr(ann), B, A, ann.shape[1], ops.ptr(per_img),
+             ops.ptr(gs), ops.ptr(dcls), ops.ptr(dreg), ops.stream_ptr())
+    else:
+        call("mpn_focal_backward_mc", ops.ptr(c), ops.ptr(r), ops.ptr(an), ops.ptr(ann), B, A, K, ann.shape[1], ops.ptr(per_img),
+             ops.ptr(gs), ops.ptr(dcls), ops.ptr(dreg), ops.stream_ptr())
     return dcls, dreg
 
 
@@ -311,6 +328,13 @@ class _Focal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cls, reg, anchors, anno):
         out, ctx.saved = focal_forward_raw(cls, reg, anchors, anno)
+        if len(ctx.saved) > 5:
+            # the reference fails on such an annotation (losses.py:77 indexes the one-hot targets with it); the kernels never use it
+            # as an index.  One host read per eager multi-class step; the recorded step (replay.py) does not check.
+            nbad = int(sum(ctx.saved[5].tolist()))
+            if nbad:
+                from .._lib import MpnError
+                raise MpnError("focal loss: %d annotation(s) carry a class id outside [0, %d)" % (nbad, cls.shape[2]))
         return out[0:1].clone(), out[1:2].clone()
 
     @staticmethod

@@ -41,8 +41,8 @@ def nms(dets, thresh):
     return pth_nms(dets, thresh)
 
 
-def _conv(cin, cout, k, padding=0):
-    return nn.Conv2d(cin, cout, kernel_size=k, stride=1, padding=padding, device="meta")
+def _conv(cin, cout, k, padding=0, device="meta"):
+    return nn.Conv2d(cin, cout, kernel_size=k, stride=1, padding=padding, device=device)
 
 
 class Concat(nn.Module):
@@ -69,21 +69,25 @@ class RegressionModel(nn.Module):
 
 
 class ClassificationModel(nn.Module):
-    """posenet.py:72-117: 4 x (3x3 conv + ReLU) + 3x3 conv -> 9*num_classes + sigmoid."""
+    """posenet.py:72-117: 4 x (3x3 conv + ReLU) + 3x3 conv -> 9*num_classes + sigmoid.
 
-    def __init__(self, num_features_in, num_anchors=9, num_classes=80, prior=0.01, feature_size=256):
+    Built on its own, e.g. to swap the head of a model (``model.classificationModel = ClassificationModel(256, num_classes=K)``), it
+    holds CPU parameters with torch's default Conv2d initialisation, as the reference's does; the next forward moves them into the
+    model's arena.  poseNet builds its own head on the meta device (``device="meta"``) and initialises it with the rest of the network."""
+
+    def __init__(self, num_features_in, num_anchors=9, num_classes=80, prior=0.01, feature_size=256, device=None):
         super(ClassificationModel, self).__init__()
         self.num_classes = num_classes
         self.num_anchors = num_anchors
-        self.conv1 = _conv(num_features_in, feature_size, 3, 1)
+        self.conv1 = _conv(num_features_in, feature_size, 3, 1, device=device)
         self.act1 = nn.ReLU()
-        self.conv2 = _conv(feature_size, feature_size, 3, 1)
+        self.conv2 = _conv(feature_size, feature_size, 3, 1, device=device)
         self.act2 = nn.ReLU()
-        self.conv3 = _conv(feature_size, feature_size, 3, 1)
+        self.conv3 = _conv(feature_size, feature_size, 3, 1, device=device)
         self.act3 = nn.ReLU()
-        self.conv4 = _conv(feature_size, feature_size, 3, 1)
+        self.conv4 = _conv(feature_size, feature_size, 3, 1, device=device)
         self.act4 = nn.ReLU()
-        self.output = _conv(feature_size, num_anchors * num_classes, 3, 1)
+        self.output = _conv(feature_size, num_anchors * num_classes, 3, 1, device=device)
         self.output_act = nn.Sigmoid()
 
 
@@ -135,7 +139,7 @@ class _NetFn(torch.autograd.Function):
 
 
 class poseNet(nn.Module):
-    def __init__(self, layers, prn_node_count=1024, prn_coeff=2, compute_dtype=torch.bfloat16, device=None):
+    def __init__(self, layers, prn_node_count=1024, prn_coeff=2, compute_dtype=torch.bfloat16, device=None, num_classes=1):
         super(poseNet, self).__init__()
         if layers == 101:
             self.fpn = FPN101()
@@ -164,7 +168,7 @@ class poseNet(nn.Module):
         self.convfin = _conv(256, 18, 1)
         # detection subnet (posenet.py:188-194)
         self.regressionModel = RegressionModel(256)
-        self.classificationModel = ClassificationModel(256, num_classes=1)
+        self.classificationModel = ClassificationModel(256, num_classes=num_classes, device="meta")     # the reference pins 1
         self.anchors = Anchors()
         self.regressBoxes = BBoxTransform()
         self.clipBoxes = ClipBoxes()
@@ -219,6 +223,7 @@ class poseNet(nn.Module):
     def _build_arena(self, device):
         named = [(n, p) for n, p in self.named_parameters()]
         self._arena = ParamArena(named, device)
+        self._arena.cls_head = self.classificationModel          # a head swapped in later (another K) rebuilds the arena
         # all num_batches_tracked counters share one int64 tensor: one add per training forward
         bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
         nbt = torch.zeros(len(bns), dtype=torch.int64, device=device)
@@ -233,9 +238,13 @@ class poseNet(nn.Module):
         p0 = next(self.parameters())
         if p0.dtype != torch.float32:
             raise MpnError("master parameters stay f32; choose the arithmetic type with compute_dtype")
-        if self._arena is None or not self._arena.consistent():
+        if not self._arena_current():
             self._build_arena(p0.device)
         return out
+
+    def _arena_current(self):
+        ar = self._arena
+        return ar is not None and ar.cls_head is self.classificationModel and ar.consistent()
 
     def freeze_bn(self):
         '''Freeze BatchNorm layers (posenet.py:220-224).'''
@@ -262,7 +271,7 @@ class poseNet(nn.Module):
         if not img.is_cuda:
             raise MpnError("poseNet runs on the MI355X only (input is on %s); there is no CPU path" % img.device)
         ops.check_device(img)
-        if self._arena is None or not self._arena.consistent() or self._arena.device != img.device:
+        if not self._arena_current() or self._arena.device != img.device:
             if next(self.parameters()).device != img.device:
                 raise MpnError("model parameters are on %s but the input is on %s" % (next(self.parameters()).device, img.device))
             self._build_arena(img.device)
@@ -325,19 +334,20 @@ class poseNet(nn.Module):
         [nms_scores, nms_class, boxes]]); entry b equals what the reference returns for image b run alone."""
         return self._entire_net(img_batch, all_images=True)
 
-    def forward_all_images_padded(self, img_batch, pre_nms_top_n=None):
+    def forward_all_images_padded(self, img_batch, pre_nms_top_n=None, return_class=False):
         """forward_all_images for batched post-processing: (heat-maps [B,18,H/4,W/4], boxes [B,nmax,4], scores [B,nmax], kept) with
-        image b's detections in rows [:kept[b]] (descending score; single class) — no per-image tensors or Python lists.
+        image b's detections in rows [:kept[b]] (descending score) — no per-image tensors or Python lists.  return_class: also the
+        arg-max class of every row, classes [B,nmax] int64 (posenet.py:283; zeros for a single-class head and past kept[b]).
         pre_nms_top_n: optional cap on the candidates that enter the suppression (ops.detect_batched; not in the reference)."""
         predict_keypoint, transformed_anchors, classification, _keep = self.forward_padded_begin(img_batch)
-        boxes, scores, kept = self.detect_padded(transformed_anchors, classification, pre_nms_top_n)
-        return predict_keypoint, boxes, scores, kept
+        out = self.detect_padded(transformed_anchors, classification, pre_nms_top_n, return_class)
+        return (predict_keypoint,) + tuple(out)
 
     def forward_padded_begin(self, img_batch):
         """First half of forward_all_images_padded: the network and the box decode are ENQUEUED, nothing is read back — the host returns
         while the GPU still runs, so a serving loop can post-process the previous batch meanwhile (evaluate/tester.py:
-        infer_images_batched).  Returns (heat-maps, decoded boxes [B,A,4], scores [B,A,1], keep-alive): hold on to the last item until
-        this batch's results have been read (it owns tensors that side-stream launches of this forward still use)."""
+        infer_images_batched).  Returns (heat-maps, decoded boxes [B,A,4], class scores [B,A,K], keep-alive): hold on to the last item
+        until this batch's results have been read (it owns tensors that side-stream launches of this forward still use)."""
         self._prepare(img_batch)
         eng = self._engine
         ctx = Ctx(False)
@@ -347,19 +357,23 @@ class poseNet(nn.Module):
         predict_keypoint, _ = eng.keypoint_head(ctx, kp, False)
         classification, regression = eng.detection_head(ctx, det)
         self._finish_forward(ctx)
-        if classification.shape[-1] != 1:
-            # the padded batch path has no class column: with several classes the arg-max class (posenet.py:283) would have to travel
-            # with every detection — use forward_all_images, which carries it
-            raise MpnError("forward_all_images_padded serves the single-class detector (classificationModel num_classes = 1), "
-                                "got %d classes" % classification.shape[-1])
         transformed_anchors = decode_and_clip(self.anchors(img_batch), regression, img_batch)
         return predict_keypoint, transformed_anchors, classification, (ctx, regression)
 
     @staticmethod
-    def detect_padded(transformed_anchors, classification, pre_nms_top_n=None):
-        """Second half: score filter + per-image NMS + gather on the CURRENT stream (two host reads)."""
-        return ops.detect_batched(transformed_anchors, classification.reshape(classification.shape[0], -1), 0.05, 0.5, padded=True,
-                                  pre_nms_top_n=pre_nms_top_n)
+    def detect_padded(transformed_anchors, classification, pre_nms_top_n=None, return_class=False):
+        """Second half: score filter + per-image NMS + gather on the CURRENT stream (two host reads) -> (boxes, scores, kept[, classes]).
+        Several classes: the score is the maximum over the classes and the class its arg-max (posenet.py:267,283); the suppression
+        runs across classes, as the reference's."""
+        B, K = classification.shape[0], classification.shape[-1]
+        if K == 1:
+            out = ops.detect_batched(transformed_anchors, classification.reshape(B, -1), 0.05, 0.5, padded=True, pre_nms_top_n=pre_nms_top_n)
+            if return_class:
+                out = out + (torch.zeros(out[1].shape, dtype=torch.int64, device=out[1].device),)
+            return out
+        score, cls_id = ops.class_max(classification.contiguous())
+        out = ops.detect_batched(transformed_anchors, score, 0.05, 0.5, padded=True, pre_nms_top_n=pre_nms_top_n, cls_id=cls_id)
+        return out if return_class else out[:3]
 
     def _entire_net(self, img_batch, all_images):
         self._prepare(img_batch)
@@ -374,6 +388,19 @@ class poseNet(nn.Module):
         anchors = self.anchors(img_batch)
         transformed_anchors = decode_and_clip(anchors, regression, img_batch)
         results = []
+        K = classification.shape[2]
+        if K > 1:
+            # posenet.py:267: scores = max over the classes (image 0 alone feeds 'both'); the arg-max (:283) is gathered for the kept
+            # anchors only
+            score, cls_id = ops.class_max(classification if all_images else classification[:1])
+        if all_images and K > 1:
+            dets = ops.detect_batched(transformed_anchors, score, 0.05, 0.5, cls_id=cls_id)
+            for boxes, nms_scores, nms_class in dets:
+                if boxes is None:
+                    results.append([torch.zeros(0), torch.zeros(0), torch.zeros(0, 4)])      # posenet.py:273-275 (CPU empties)
+                else:
+                    results.append([nms_scores, nms_class, boxes])
+            return predict_keypoint, results
         if all_images:
             # every image thresholded (posenet.py:269-271), NMS'd (:281) and gathered (:283-285) by batch-wide launches;
             # sizes stay on the device between the stages (ops.detect_batched: two host reads per BATCH)
@@ -390,13 +417,16 @@ class poseNet(nn.Module):
             return predict_keypoint, results
         for b in range(1):
             # posenet.py:269-275: score > 0.05, early-out with the CPU empty triple
-            dets, _src = ops.score_filter(transformed_anchors[b], classification[b, :, 0], 0.05)
+            dets, src = ops.score_filter(transformed_anchors[b], classification[b, :, 0] if K == 1 else score[b], 0.05)
             if dets.shape[0] == 0:
                 results.append([torch.zeros(0), torch.zeros(0), torch.zeros(0, 4)])
                 continue
             anchors_nms_idx = nms(dets, 0.5)
             boxes, nms_scores = ops.gather_dets(dets, anchors_nms_idx)
-            nms_class = torch.zeros(nms_scores.shape[0], dtype=torch.int64, device=nms_scores.device)   # single class
+            if K == 1:
+                nms_class = torch.zeros(nms_scores.shape[0], dtype=torch.int64, device=nms_scores.device)   # single class
+            else:
+                nms_class = ops.gather_class(cls_id[b], src, anchors_nms_idx)
             results.append([nms_scores, nms_class, boxes])
         return predict_keypoint, results
 
@@ -413,7 +443,7 @@ class poseNet(nn.Module):
         return outs[4], outs
 
     def detection_forward(self, img_batch):
-        """posenet.py:320-335 -> ([], [classification [B,A,1], regression [B,A,4], anchors [1,A,4]])."""
+        """posenet.py:320-335 -> ([], [classification [B,A,K], regression [B,A,4], anchors [1,A,4]])."""
         self._prepare(img_batch)
         eng = self._engine
         ctx = Ctx(self._want_tape())

@@ -988,24 +988,48 @@ def nms_pre_topn_env():
         return 0
 
 
-def detect_batched(boxes, scores, score_thresh, iou_thresh, mode=0, ws_limit=4 << 30, padded=False, pre_nms_top_n=None):
+def class_max(cls):
+    """cls [B,A,K] f32 contiguous -> (score [B,A] f32, cls_id [B,A] int64): the maximum over the classes and the index of its first
+    occurrence (torch.max(dim=2); posenet.py:267,283)."""
+    B, A, K = cls.shape
+    score = torch.empty((B, A), dtype=torch.float32, device=cls.device)
+    cls_id = torch.empty((B, A), dtype=torch.int64, device=cls.device)
+    call("mpn_class_max", ptr(cls), B, A, K, ptr(score), ptr(cls_id), stream_ptr())
+    return score, cls_id
+
+
+def gather_class(cls_id0, src, keep):
+    """Class ids [k] int64 of the detections keep[k] selected from the candidates of score_filter(..., src) of one image."""
+    k = keep.numel()
+    out = torch.empty((k,), dtype=torch.int64, device=cls_id0.device)
+    if k > 0:
+        call("mpn_gather_class", ptr(cls_id0), ptr(src), cls_id0.numel(), ptr(keep), 0, None, 1, k, ptr(out), k, stream_ptr())
+    return out
+
+
+def detect_batched(boxes, scores, score_thresh, iou_thresh, mode=0, ws_limit=4 << 30, padded=False, pre_nms_top_n=None, cls_id=None):
     """Score filter + per-image NMS + gather for EVERY image of a batch with two host round trips per batch (the candidate
     counts size the NMS launches, the kept counts size the returned tensors) instead of two per image.
     boxes [B,A,4], scores [B,A] (f32, contiguous).  Returns per image (boxes[k,4], scores[k]) device tensors (views); with
     padded=True the batch-wide tensors themselves: (boxes [B,nmax,4], scores [B,nmax] in descending order, kept counts list).
     pre_nms_top_n (not in the reference; None = every candidate, as posenet.py:269-285): only that many best-scored candidates of
-    an image enter the suppression, which bounds its N x N/64 mask."""
+    an image enter the suppression, which bounds its N x N/64 mask.
+    cls_id (optional, [B,A] int64, from class_max): the class id of every kept detection travels along (its anchor index passes the
+    score filter): each result gains it as a last item, (boxes, scores, classes [k] int64) / (..., kept, classes [B,nmax] int64)."""
     B, A = scores.shape[0], scores.shape[1]
     dev = scores.device
     dets = torch.empty((B, A, 5), dtype=torch.float32, device=dev)
     counts = torch.empty((B,), dtype=torch.int32, device=dev)
-    call("mpn_score_filter_batched", ptr(boxes), ptr(scores), B, A, float(score_thresh), ptr(dets), None, ptr(counts), stream_ptr())
+    src = torch.empty((B, A), dtype=torch.int32, device=dev) if cls_id is not None else None
+    call("mpn_score_filter_batched", ptr(boxes), ptr(scores), B, A, float(score_thresh), ptr(dets), ptr(src) if src is not None else None,
+         ptr(counts), stream_ptr())
     cnt = counts.tolist()                              # host round trip 1
     nmax = max(cnt)
     if nmax == 0:
         if padded:
-            return torch.zeros((B, 0, 4), dtype=torch.float32, device=dev), torch.zeros((B, 0), dtype=torch.float32, device=dev), [0] * B
-        return [(None, None)] * B
+            out = (torch.zeros((B, 0, 4), dtype=torch.float32, device=dev), torch.zeros((B, 0), dtype=torch.float32, device=dev), [0] * B)
+            return out + (torch.zeros((B, 0), dtype=torch.int64, device=dev),) if cls_id is not None else out
+        return [(None, None, None) if cls_id is not None else (None, None)] * B
     ncand = nmax
     if pre_nms_top_n is None and nms_pre_topn_env() > 0:
         pre_nms_top_n = nms_pre_topn_env()
@@ -1036,9 +1060,16 @@ def detect_batched(boxes, scores, score_thresh, iou_thresh, mode=0, ws_limit=4 <
     out_boxes = torch.empty((B, nmax, 4), dtype=torch.float32, device=dev)
     out_scores = torch.empty((B, nmax), dtype=torch.float32, device=dev)
     call("mpn_gather_dets_batched", ptr(dets), A * 5, ptr(keep), nmax, ptr(num), B, nmax, ptr(out_boxes), ptr(out_scores), nmax, stream_ptr())
+    out_cls = None
+    if cls_id is not None:
+        out_cls = torch.empty((B, nmax), dtype=torch.int64, device=dev)
+        call("mpn_gather_class", ptr(cls_id), ptr(src), A, ptr(keep), nmax, ptr(num), B, nmax, ptr(out_cls), nmax, stream_ptr())
     kept = num.tolist()                                # host round trip 2
     if padded:
-        return out_boxes, out_scores, [k if cnt[b] > 0 else 0 for b, k in enumerate(kept)]
+        out = (out_boxes, out_scores, [k if cnt[b] > 0 else 0 for b, k in enumerate(kept)])
+        return out + (out_cls,) if out_cls is not None else out
+    if out_cls is not None:
+        return [(out_boxes[b, :k], out_scores[b, :k], out_cls[b, :k]) if cnt[b] > 0 else (None, None, None) for b, k in enumerate(kept)]
     return [(out_boxes[b, :k], out_scores[b, :k]) if cnt[b] > 0 else (None, None) for b, k in enumerate(kept)]
 
 
