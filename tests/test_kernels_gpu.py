@@ -325,7 +325,9 @@ def test_maxpool_and_resample(dtype):
     ya, idx = ops.maxpool_forward(xa, needs_grad=True)
     assert torch.equal(from_act(ya), y.detach()), "max-pool forward must be exact"
     dx = ops.maxpool_backward(to_act(dy, dtype), idx, xa)
-    # positive maxima are unique with probability 1; all-zero windows route to the first tap in both
+    # all-zero windows route to the first tap in both; tied positive maxima are rare here but not impossible (16-bit significands collide):
+    # the tie rule (first maximum in scan order), clipped windows and H, W of 1 or 2 are tested where ties dominate, in
+    # tests/test_stream_parity_gpu.py::test_maxpool_ties_and_clipped_windows
     check_close("maxpool bwd %s" % dtype, from_act(dx), x.grad, dtype)
     # nearest upsample backward (2x and a non-integer ratio)
     for (hc, wc, hf, wf) in ((5, 6, 10, 12), (4, 3, 7, 5)):
