@@ -465,6 +465,45 @@ int mpn_conv2cls_fold(const float* dcomb, float* dw, int O, int C, void* stream)
 const char* mpn_version(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training augmentation from raw uint8 sources (datasets/coco_data/ImageAugmentation.py:25-231 aug_scale, aug_rotate,
+ * aug_croppad, aug_flip; COCO_data_pipeline.py:211-215; preprocessing.py:15-26), one launch per batch, one cubic
+ * (A = -0.75) sample per output element through the composed inverse transform, taps clamped to the source, no
+ * intermediate image and no uint8 rounding.  Coordinates are float64, weights and the 16-term sum float32.
+ *
+ * src: the packed sources of the whole batch (device, src_bytes long).  table: double [B][MPN_AUG_COLS] (device), per
+ * sample: byte offset and row pitch of its BGR image ([H][W][3]) and of its mask ([H][W]) in their packed buffers,
+ * H, W, the resize factor, the scaled size (nw, nh), the rotated canvas size (cw, ch), the row-major 2x3 INVERSE of
+ * the matrix handed to warpAffine, the canvas pixel (ox, oy) of crop pixel (0, 0), and the flip flag.  A row whose
+ * source does not lie inside [0, src_bytes) is not dereferenced: its outputs are NaN.
+ *
+ * mpn_augment_image: out f32 [B][3][crop_y][crop_x], plane c = (BGR[2 - c] / 255 - mean[c]) / std[c] with
+ *   mean_std = {mean[3], std[3]} (HOST pointer, RGB order); outside the canvas or the scaled image the BGR value is 128.
+ * mpn_augment_mask: out f32 [B][18][gh][gw]; cell (i, j) samples the (crop_x + 1)-wide mask crop at
+ *   ((j + 0.5) stride - 0.5, (i + 0.5) stride - 0.5), flipped over that width; border value 255; result / 255 written
+ *   to all 18 channels.
+ * -------------------------------------------------------------------------------------------*/
+#define MPN_AUG_IMG_OFF 0
+#define MPN_AUG_IMG_PITCH 1
+#define MPN_AUG_MASK_OFF 2
+#define MPN_AUG_MASK_PITCH 3
+#define MPN_AUG_H 4
+#define MPN_AUG_W 5
+#define MPN_AUG_SCALE 6
+#define MPN_AUG_NW 7
+#define MPN_AUG_NH 8
+#define MPN_AUG_CW 9
+#define MPN_AUG_CH 10
+#define MPN_AUG_MINV 11
+#define MPN_AUG_OX 17
+#define MPN_AUG_OY 18
+#define MPN_AUG_FLIP 19
+#define MPN_AUG_COLS 20
+int mpn_augment_image(const uint8_t* src, int64_t src_bytes, const double* table, int B, float* out, int crop_y, int crop_x,
+                      const float* mean_std, void* stream);
+int mpn_augment_mask(const uint8_t* src, int64_t src_bytes, const double* table, int B, float* out, int gh, int gw, int stride,
+                     int crop_x, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Ground-truth heat-maps (datasets/coco_data/heatmap.py:20-41 + COCO_data_pipeline.py:218-236,283):
  * out[b][k][y][x] (f32, 18 keypoint channels) = min(1, sum over people j < num_people[b] with
  * visibility <= 1 of exp(-e) where e = d2/2/sigma/sigma <= 4.6052), float64 arithmetic in annotation

@@ -1,0 +1,384 @@
+"""Training augmentation of keypoint batches on the GPU, from raw uint8 images.
+
+Device replacement for what the reference's ``Cocokeypoints.__getitem__`` (``datasets/coco_data/COCO_data_pipeline.py:238-291``)
+does per image on the host between the decoded image and the tensors of a batch: ``aug_scale``, ``aug_rotate``,
+``aug_croppad``, ``aug_flip`` (``datasets/coco_data/ImageAugmentation.py:25-231``), the mask's second resize
+(``COCO_data_pipeline.py:211-215``) and ``resnet_preprocess`` (``preprocessing.py:15-26``).
+
+Two halves:
+
+* the META-DATA side (where every joint lands, every stage's size, the matrix handed to ``warpAffine``, the crop, the flip) is
+  restated here op for op in numpy float64 — :func:`add_neck`, :func:`augment_meta`, :func:`remove_illegal_joint` — with the
+  random draws as an explicit input (:func:`draw_dice` draws them from a ``random.Random`` in the reference's order);
+* the PIXEL side runs in csrc/augment.hip: every output element is mapped through the composed inverse transform to a source
+  coordinate and sampled ONCE with the 4x4 cubic kernel, without the intermediate uint8 images of the reference and without
+  rounding (DESIGN.md section 7 states the deviation).  :class:`DeviceAugmenter` packs a batch, launches the two kernels and
+  renders the heat-maps with :func:`..heatmap.put_gaussian_maps`.
+
+Decoding the image files and reading the COCO json stay with the loader.
+"""
+import ctypes
+import math
+import random
+
+import numpy as np
+import torch
+
+from .._lib import MpnError, call
+from .. import ops
+from .heatmap import put_gaussian_maps
+
+# COCO_data_pipeline.py:25-42
+DEFAULT_PARAMS = {
+    "mode": 5,
+    "scale_min": 0.8, "scale_max": 1.2, "scale_prob": 1, "target_dist": 0.6,
+    "max_rotate_degree": 40,
+    "center_perterb_max": 40,
+    "flip_prob": 0.3,
+    "np": 56, "sigma": 7.0,
+}
+
+# preprocessing.py:17-18 (RGB order)
+MEANS = (0.485, 0.456, 0.406)
+STDS = (0.229, 0.224, 0.225)
+
+# COCO_data_pipeline.py:138-139 and ImageAugmentation.py:148-149
+OUR_ORDER = [0, 17, 6, 8, 10, 5, 7, 9, 12, 14, 16, 11, 13, 15, 2, 1, 4, 3]
+FLIP_ORDER = [0, 1, 5, 6, 7, 2, 3, 4, 11, 12, 13, 8, 9, 10, 15, 14, 17, 16]
+
+# dice layout: aug_scale dice, aug_scale dice2 (NaN when not drawn), aug_rotate dice, aug_croppad dice_x, dice_y, aug_flip dice
+N_DICE = 6
+
+# columns of the per-sample table the kernels read (include/mpn.h: MPN_AUG_*)
+T_IMG_OFF, T_IMG_PITCH, T_MASK_OFF, T_MASK_PITCH, T_H, T_W, T_SCALE, T_NW, T_NH, T_CW, T_CH = range(11)
+T_MINV, T_OX, T_OY, T_FLIP, T_COLS = 11, 17, 18, 19, 20
+
+
+def draw_dice(rng, params=None):
+    """The six draws of one sample from ``rng`` (a ``random.Random`` or the ``random`` module) in the reference's order: aug_scale's
+    ``dice`` and — only when ``dice <= scale_prob`` — ``dice2`` (ImageAugmentation.py:26-31), aug_rotate's ``dice`` (:206), aug_croppad's
+    ``dice_x``, ``dice_y`` (:56-57), aug_flip's ``dice`` (:124).  The same seed gives the reference's stream."""
+    p = DEFAULT_PARAMS if params is None else params
+    d = np.full(N_DICE, np.nan, dtype=np.float64)
+    d[0] = rng.random()
+    if not d[0] > p["scale_prob"]:
+        d[1] = rng.random()
+    d[2] = rng.random()
+    d[3] = rng.random()
+    d[4] = rng.random()
+    d[5] = rng.random()
+    return d
+
+
+def _neck(right_shoulder, left_shoulder):
+    neck = (right_shoulder + left_shoulder) / 2
+    if right_shoulder[2] == 2 or left_shoulder[2] == 2:
+        neck[2] = 2
+    elif right_shoulder[2] == 1 or left_shoulder[2] == 1:
+        neck[2] = 1
+    else:
+        neck[2] = right_shoulder[2] * left_shoulder[2]
+    return np.round(neck.reshape(1, len(neck)))
+
+
+def add_neck(joint_self, joint_others):
+    """COCO_data_pipeline.py:123-174: 17 COCO keypoints -> the 18 of this work (neck = rounded mean of the shoulders, visibility by
+    the reference's rule), re-ordered.  joint_self [17, 3], joint_others [n, 17, 3] -> ([18, 3], [n, 18, 3]) float64."""
+    js = np.array(joint_self, dtype=np.float64)
+    jo = np.array(joint_others, dtype=np.float64).reshape(-1, 17, 3)
+    js = np.vstack((js, _neck(js[6, :], js[5, :])))[OUR_ORDER, :]
+    out = np.zeros((jo.shape[0], 18, 3), dtype=np.float64)
+    for i in range(jo.shape[0]):
+        out[i] = np.vstack((jo[i], _neck(jo[i, 6, :], jo[i, 5, :])))[OUR_ORDER, :]
+    return js, out
+
+
+def remove_illegal_joint(joint_self, joint_others, crop_x, crop_y):
+    """COCO_data_pipeline.py:176-194: joints outside the crop become (1, 1, 2).  Returns new arrays."""
+    js, jo = joint_self.copy(), joint_others.copy()
+    for j in (js, jo):
+        if j.size == 0:
+            continue
+        mask = np.logical_or.reduce((j[..., 0] >= crop_x, j[..., 0] < 0, j[..., 1] >= crop_y, j[..., 1] < 0))
+        j[mask, :] = (1, 1, 2)
+    return js, jo
+
+
+def rotation_matrix(center, angle, scale):
+    """The documented cv2.getRotationMatrix2D: angle in degrees, positive = counter-clockwise."""
+    a = float(angle) * math.pi / 180.0
+    alpha, beta = math.cos(a) * scale, math.sin(a) * scale
+    cx, cy = float(center[0]), float(center[1])
+    return np.array([[alpha, beta, (1 - alpha) * cx - beta * cy], [-beta, alpha, beta * cx + (1 - alpha) * cy]], dtype=np.float64)
+
+
+def invert_affine(M):
+    """Inverse of a 2x3 affine map in the operation order of warpAffine's own inversion (imgproc/imgwarp.cpp)."""
+    M = np.array(M, dtype=np.float64)
+    D = M[0, 0] * M[1, 1] - M[0, 1] * M[1, 0]
+    D = 1.0 / D if D != 0 else 0.0
+    A11, A22 = M[1, 1] * D, M[0, 0] * D
+    iM = np.zeros((2, 3), dtype=np.float64)
+    iM[0, 0], iM[0, 1], iM[1, 0], iM[1, 1] = A11, M[0, 1] * (-D), M[1, 0] * (-D), A22
+    iM[0, 2] = -iM[0, 0] * M[0, 2] - iM[0, 1] * M[1, 2]
+    iM[1, 2] = -iM[1, 0] * M[0, 2] - iM[1, 1] * M[1, 2]
+    return iM
+
+
+def _rotatepoint(p, R):
+    # ImageAugmentation.py:161-172 (the same [2, 3] x [3, 1] product, so the same rounding)
+    point = np.zeros((3, 1))
+    point[0] = p[0]
+    point[1] = p[1]
+    point[2] = 1
+    new_point = R.dot(point)
+    p[0] = new_point[0, 0]
+    p[1] = new_point[1, 0]
+    return p
+
+
+def augment_meta(H, W, scale_provided, objpos, joint_self, joint_others, dice, crop_x, crop_y, params=None, objpos_other=None,
+                 with_mask=True):
+    """The meta-data side of aug_scale -> aug_rotate -> aug_croppad -> aug_flip for one sample, op for op.
+
+    joint_self [18, 3] / joint_others [n, 18, 3] (after :func:`add_neck`), objpos [2] in source pixels; ``dice`` as laid out by
+    :func:`draw_dice`.  Returns a dict: the transformed ``joint_self`` / ``joint_others`` / ``objpos`` / ``objpos_other`` (before
+    :func:`remove_illegal_joint`) and the numbers the kernels need — ``scale``, the scaled size ``(nh, nw)``, the canvas size
+    ``(nH, nW)``, ``M`` (the matrix handed to warpAffine) and ``Minv``, the crop origin ``(ox, oy)`` on the canvas, ``flip`` — plus
+    ``degree`` and ``center``."""
+    p = DEFAULT_PARAMS if params is None else params
+    dice = np.asarray(dice, dtype=np.float64)
+    if dice.shape != (N_DICE,):
+        raise MpnError("dice must hold %d draws per sample" % N_DICE)
+    crop_x, crop_y = int(crop_x), int(crop_y)
+    objpos = np.array(objpos, dtype=np.float64)
+    js = np.array(joint_self, dtype=np.float64)
+    jo = np.array(joint_others, dtype=np.float64).reshape(-1, 18, 3)
+    n_other = jo.shape[0]
+    oo = np.zeros((n_other, 2)) if objpos_other is None else np.array(objpos_other, dtype=np.float64).reshape(n_other, 2)
+    if js.shape != (18, 3) or objpos.shape != (2,):
+        raise MpnError("joint_self must be [18, 3] and objpos [2]")
+
+    # --- aug_scale (ImageAugmentation.py:25-52)
+    if dice[0] > p["scale_prob"]:
+        scale_multiplier = 1
+    else:
+        if np.isnan(dice[1]):
+            raise MpnError("dice[1] (aug_scale's dice2) is needed when dice[0] <= scale_prob")
+        scale_multiplier = (p["scale_max"] - p["scale_min"]) * float(dice[1]) + p["scale_min"]
+    scale_abs = p["target_dist"] / scale_provided
+    scale = scale_abs * scale_multiplier
+    if not (scale > 0 and math.isfinite(scale)):
+        raise MpnError("scale_provided gives a non-positive or non-finite scale")
+    nh, nw = int(round(H * scale)), int(round(W * scale))            # cv2.resize with fx, fy: dsize = round(size * f)
+    if nh < 1 or nw < 1:
+        raise MpnError("the scaled image is empty")
+    objpos *= scale
+    js[:, :2] *= scale
+    if n_other != 0:
+        oo *= scale
+        jo[:, :, :2] *= scale
+
+    # --- aug_rotate (:205-231) with rotate_bound (:179-202)
+    degree = (float(dice[2]) - 0.5) * 2 * p["max_rotate_degree"]
+    cX, cY = nw // 2, nh // 2
+    M = rotation_matrix((cX, cY), -degree, 1.0)
+    cos, sin = np.abs(M[0, 0]), np.abs(M[0, 1])
+    nW = int((nh * sin) + (nw * cos))
+    nH = int((nh * cos) + (nw * sin))
+    M[0, 2] += (nW / 2) - cX
+    M[1, 2] += (nH / 2) - cY
+    objpos = _rotatepoint(objpos, M)
+    for i in range(18):
+        js[i, :] = _rotatepoint(js[i, :], M)
+    for j in range(n_other):
+        oo[j, :] = _rotatepoint(oo[j, :], M)
+        for i in range(18):
+            jo[j, i, :] = _rotatepoint(jo[j, i, :], M)
+
+    # --- aug_croppad (:55-118)
+    x_offset = int((float(dice[3]) - 0.5) * 2 * p["center_perterb_max"])
+    y_offset = int((float(dice[4]) - 0.5) * 2 * p["center_perterb_max"])
+    center = objpos + np.array([x_offset, y_offset])
+    if not np.all(np.isfinite(center)):
+        raise MpnError("objpos is not finite")
+    center = center.astype(int)
+    # the slices [center + int(crop / 2), ... + crop (+ 1 for the mask)) of the canvas padded by crop on every side must lie inside it:
+    # a negative start would wrap, an end past the padded size would truncate the crop
+    x0, y0 = int(center[0]) + int(crop_x / 2), int(center[1]) + int(crop_y / 2)
+    extra = 1 if with_mask else 0
+    if x0 < 0 or y0 < 0 or x0 + crop_x + extra > nW + 2 * crop_x or y0 + crop_y + extra > nH + 2 * crop_y:
+        raise MpnError("crop centre (%d, %d) is too far outside the %d x %d canvas: the reference's slices would wrap or truncate"
+                       % (center[0], center[1], nW, nH))
+    ox, oy = x0 - crop_x, y0 - crop_y                                 # canvas pixel of crop pixel (0, 0)
+    offset = np.array([crop_x / 2 - center[0], crop_y / 2 - center[1]])
+    objpos += offset
+    js[:, :2] += offset
+    mask = np.logical_or.reduce((js[:, 0] >= crop_x, js[:, 0] < 0, js[:, 1] >= crop_y, js[:, 1] < 0))
+    js[mask, 2] = 2
+    if n_other != 0:
+        oo += offset
+        jo[:, :, :2] += offset
+        mask = np.logical_or.reduce((jo[:, :, 0] >= crop_x, jo[:, :, 0] < 0, jo[:, :, 1] >= crop_y, jo[:, :, 1] < 0))
+        jo[mask, 2] = 2
+
+    # --- aug_flip (:121-158); w is the IMAGE's width (the mask, one pixel wider, is flipped over its own)
+    flip = bool(dice[5] <= p["flip_prob"])
+    if flip:
+        w = crop_x
+        objpos[0] = w - 1 - objpos[0]
+        js[:, 0] = w - 1 - js[:, 0]
+        js = js[FLIP_ORDER]
+        if n_other != 0:
+            oo[:, 0] = w - 1 - oo[:, 0]
+            jo[:, :, 0] = w - 1 - jo[:, :, 0]
+            for i in range(n_other):
+                jo[i] = jo[i][FLIP_ORDER]
+    return {"joint_self": js, "joint_others": jo, "objpos": objpos, "objpos_other": oo, "scale": float(scale), "nh": nh, "nw": nw,
+            "nH": nH, "nW": nW, "M": M, "Minv": invert_affine(M), "ox": ox, "oy": oy, "flip": flip, "degree": degree,
+            "center": (int(center[0]), int(center[1]))}
+
+
+def table_row(geo, H, W, img_off, img_pitch, mask_off=0, mask_pitch=0):
+    """One row of the per-sample table of mpn_augment_image / mpn_augment_mask (float64; every integer in it is exact)."""
+    row = np.zeros(T_COLS, dtype=np.float64)
+    row[[T_IMG_OFF, T_IMG_PITCH, T_MASK_OFF, T_MASK_PITCH, T_H, T_W]] = (img_off, img_pitch, mask_off, mask_pitch, H, W)
+    row[[T_SCALE, T_NW, T_NH, T_CW, T_CH]] = (geo["scale"], geo["nw"], geo["nh"], geo["nW"], geo["nH"])
+    row[T_MINV:T_MINV + 6] = geo["Minv"].reshape(6)
+    row[[T_OX, T_OY, T_FLIP]] = (geo["ox"], geo["oy"], 1.0 if geo["flip"] else 0.0)
+    return row
+
+
+def _pinned(n, dtype):
+    return torch.empty(n, dtype=dtype, pin_memory=True)
+
+
+def augment_image(src, table, crop_y, crop_x):
+    """mpn_augment_image: packed uint8 BGR sources (device) + table [B, 20] float64 (device) -> float32 [B, 3, crop_y, crop_x]."""
+    B = table.shape[0]
+    out = torch.empty((B, 3, crop_y, crop_x), dtype=torch.float32, device=src.device)
+    ms = (ctypes.c_float * 6)(*(MEANS + STDS))
+    call("mpn_augment_image", ops.ptr(src), src.numel(), ops.ptr(table), B, ops.ptr(out), crop_y, crop_x, ms, ops.stream_ptr())
+    return out
+
+
+def augment_mask(src, table, gh, gw, stride, crop_x):
+    """mpn_augment_mask: packed uint8 masks (device) + table -> float32 [B, 18, gh, gw], the 18 channels materialised."""
+    B = table.shape[0]
+    out = torch.empty((B, 18, gh, gw), dtype=torch.float32, device=src.device)
+    call("mpn_augment_mask", ops.ptr(src), src.numel(), ops.ptr(table), B, ops.ptr(out), gh, gw, stride, crop_x, ops.stream_ptr())
+    return out
+
+
+class DeviceAugmenter(object):
+    """``DeviceAugmenter(inp_size, feat_stride)(samples)`` -> ``(img, heatmaps, heat_mask, meta)``: the reference's training triple
+    for ``keypoint_subnet`` (float32, contiguous, on the current device) plus the host-side geometry of every sample.
+
+    A sample is a dict with the decoded image and the reference's meta fields::
+
+        {"img": uint8 tensor [H, W, 3] (BGR, CPU, contiguous), "mask_miss": uint8 tensor [H, W] or None,
+         "objpos": (x, y), "scale_provided": s, "joint_self": [17, 3], "joint_others": [n, 17, 3] (optional),
+         "objpos_other": [n, 2] (optional)}
+
+    ``joint_self`` / ``joint_others`` with 18 rows are taken as already in this work's order (no neck is added).  With
+    ``mask_miss`` None in every sample the image-only form is returned: ``heat_mask`` is None (the ``aug_*_bbox`` chain of the
+    detection loader is the identical image chain).  ``dice`` [B, 6] makes the draws explicit; otherwise they come from ``rng``
+    (a ``random.Random``; default the ``random`` module, as in the reference) through :func:`draw_dice`."""
+
+    def __init__(self, inp_size, feat_stride, params=None):
+        self.inp_size, self.stride = int(inp_size), int(feat_stride)
+        if self.inp_size <= 0 or self.stride <= 0 or int(self.inp_size / self.stride) <= 0:
+            raise MpnError("inp_size and feat_stride must be positive, inp_size >= feat_stride")
+        self.params = dict(DEFAULT_PARAMS)
+        if params:
+            self.params.update(params)
+        self.grid = int(self.inp_size / self.stride)                  # COCO_data_pipeline.py:206-207
+
+    @staticmethod
+    def _check_u8(t, what, dims):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.is_cuda or t.dim() != dims or not t.is_contiguous():
+            raise MpnError("%s must be a contiguous uint8 CPU tensor with %d dimensions" % (what, dims))
+
+    def geometry(self, samples, dice=None, rng=None):
+        """Part 1 for a batch: list of per-sample dicts of :func:`augment_meta` with the final (``remove_illegal_joint``) joints
+        under ``joint_self_out`` / ``joint_others_out``.  Needs no GPU."""
+        B = len(samples)
+        if B == 0:
+            raise MpnError("empty batch")
+        with_mask = [s.get("mask_miss") is not None for s in samples]
+        if any(with_mask) != all(with_mask):
+            raise MpnError("either every sample of a batch has a mask_miss or none has")
+        if dice is None:
+            rng = random if rng is None else rng
+            dice = np.stack([draw_dice(rng, self.params) for _ in range(B)])
+        dice = np.asarray(dice, dtype=np.float64)
+        if dice.shape != (B, N_DICE):
+            raise MpnError("dice must be [B, %d]" % N_DICE)
+        metas = []
+        for s, d in zip(samples, dice):
+            img = s["img"]
+            self._check_u8(img, "img", 3)
+            if img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+                raise MpnError("img must be [H, W, 3]")
+            H, W = int(img.shape[0]), int(img.shape[1])
+            if s.get("mask_miss") is not None:
+                self._check_u8(s["mask_miss"], "mask_miss", 2)
+                if tuple(s["mask_miss"].shape) != (H, W):
+                    raise MpnError("mask_miss must have the image's [H, W]")
+            js = np.asarray(s["joint_self"], dtype=np.float64)
+            jo = np.asarray(s.get("joint_others", np.zeros((0,) + js.shape)), dtype=np.float64)
+            if js.shape == (17, 3):
+                js, jo = add_neck(js, jo)
+            elif js.shape != (18, 3):
+                raise MpnError("joint_self must be [17, 3] (COCO order) or [18, 3]")
+            jo = jo.reshape(-1, 18, 3)
+            geo = augment_meta(H, W, s["scale_provided"], s["objpos"], js, jo, d, self.inp_size, self.inp_size, self.params,
+                               s.get("objpos_other"), with_mask=with_mask[0])
+            geo["joint_self_out"], geo["joint_others_out"] = remove_illegal_joint(geo["joint_self"], geo["joint_others"],
+                                                                                  self.inp_size, self.inp_size)
+            geo["dice"], geo["H"], geo["W"] = d.copy(), H, W
+            metas.append(geo)
+        return metas
+
+    def __call__(self, samples, dice=None, rng=None):
+        if not torch.cuda.is_available():
+            raise MpnError("DeviceAugmenter runs on the MI355X only; there is no CPU path")
+        metas = self.geometry(samples, dice, rng)
+        B, S = len(samples), self.inp_size
+        has_mask = samples[0].get("mask_miss") is not None
+        dev = torch.device("cuda", torch.cuda.current_device())
+        # one pinned staging buffer per kind (every source starts on a 16-byte boundary), one H2D copy each
+        img_off, mask_off, ni, nm = [], [], 0, 0
+        for g in metas:
+            img_off.append(ni)
+            mask_off.append(nm)
+            ni += (g["H"] * g["W"] * 3 + 15) // 16 * 16
+            nm += (g["H"] * g["W"] + 15) // 16 * 16
+        stage_i = _pinned(ni, torch.uint8)
+        stage_m = _pinned(nm, torch.uint8) if has_mask else None
+        table = _pinned(B * T_COLS, torch.float64).view(B, T_COLS)
+        maxP = max(1 + g["joint_others_out"].shape[0] for g in metas)
+        joints = _pinned(B * maxP * 18 * 3, torch.float64).view(B, maxP, 18, 3).zero_()
+        num = _pinned(B, torch.int32)
+        for b, (s, g) in enumerate(zip(samples, metas)):
+            H, W = g["H"], g["W"]
+            stage_i[img_off[b]: img_off[b] + H * W * 3] = s["img"].view(-1)
+            if has_mask:
+                stage_m[mask_off[b]: mask_off[b] + H * W] = s["mask_miss"].view(-1)
+            table[b] = torch.from_numpy(table_row(g, H, W, img_off[b], W * 3, mask_off[b], W))
+            n = g["joint_others_out"].shape[0]
+            joints[b, 0] = torch.from_numpy(g["joint_self_out"])
+            if n:
+                joints[b, 1:1 + n] = torch.from_numpy(g["joint_others_out"])
+            num[b] = 1 + n
+        d_img = stage_i.to(dev, non_blocking=True)
+        d_table = table.to(dev, non_blocking=True)
+        img = augment_image(d_img, d_table, S, S)
+        heat_mask = None
+        if has_mask:
+            heat_mask = augment_mask(stage_m.to(dev, non_blocking=True), d_table, self.grid, self.grid, self.stride, S)
+        heatmaps = put_gaussian_maps(joints.to(dev, non_blocking=True), num.to(dev, non_blocking=True), S, S, self.stride,
+                                     self.params["sigma"])
+        # the pinned staging buffers may go out of scope here: torch's caching host allocator records the stream of a non_blocking
+        # copy and hands a block out again only after that copy has finished
+        return img, heatmaps, heat_mask, metas

@@ -2,9 +2,10 @@
 
 Device replacement for the CPU target generation in the reference's data loader:
 ``datasets/coco_data/heatmap.py:20-41`` (``putGaussianMaps``) and the per-keypoint loop of
-``datasets/coco_data/COCO_data_pipeline.py:218-236`` (``get_ground_truth``), batched.  The loader keeps doing the
-image decoding / augmentation; it hands over the augmented keypoints and the 46 x 18 Gaussians per image are
-rendered where the loss will read them.
+``datasets/coco_data/COCO_data_pipeline.py:218-236`` (``get_ground_truth``), batched.  It takes the augmented keypoints and
+renders the 46 x 18 Gaussians per image where the loss will read them.  The keypoints come either from a loader that
+still augments on the host, or from ``datasets/augment.py`` (``DeviceAugmenter``), which augments raw decoded samples
+on the device and calls this function; only the image decoding stays with the loader.
 """
 import torch
 
