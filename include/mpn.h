@@ -504,6 +504,29 @@ int mpn_augment_mask(const uint8_t* src, int64_t src_bytes, const double* table,
                      int crop_x, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PRN training pairs from raw COCO annotations (datasets/coco_data/prn_data_pipeline.py:33-111), one launch per batch.
+ * Per sample b: box[b] = the annotation's raw (x, y, w, h); own_kp[b] = its 17 (x, y, v) keypoints; the annotations of its image
+ * (the own one, crowds and people with few keypoints among them), in the image's annotation order, are rows
+ * person_off[b] .. person_off[b + 1] of img_kp [P][17][3] (offsets outside 0..P are clamped on the device: img_kp is never read
+ * out of range).  H = 28 coeff, W = 18 coeff, coeff 1..3.  Both results are f32 [B][H][W][17], channel c = COCO joint
+ * (0, 6, 8, 10, 5, 7, 9, 12, 14, 16, 11, 13, 15, 2, 1, 4, 3)[c]:
+ *   input = the reference's `weights`: every v > 0 keypoint of the image's annotations that passes the margin test on the raw box
+ *           floats (:85-86) sets its cell through the one-branch clamp chain (:90-103), blurred with taps9 ('nearest');
+ *   label = the reference's `output`: the own v > 0 keypoints, no margin test, the chain of :56-72 with its try/except, blurred
+ *           with taps17 ('constant', 0).
+ * Cell arithmetic in float64 with int() truncation and Python's negative-index wrap; blur along axis 0 then axis 1 in
+ * scipy.ndimage.correlate1d's summation order with the caller's float64 taps (scipy's _gaussian_kernel1d for sigma 1 radius 4 and
+ * sigma 2 radius 8); one rounding to f32.  err[b] (written for every b, with vector stores) is 0 or an OR of MPN_PRN_ERR_* where
+ * the reference raises; both maps of such a sample are zero.  All pointers are device pointers; doubles 8-byte aligned.
+ * -------------------------------------------------------------------------------------------*/
+#define MPN_PRN_ERR_INDEX 1      /* IndexError: x0 >= W with y0 < -H, or (input only) y0 >= H with x0 < -W */
+#define MPN_PRN_ERR_ZERODIV 2    /* ZeroDivisionError: ceil(w) == 0 or ceil(h) == 0 */
+#define MPN_PRN_ERR_NONFINITE 4  /* ValueError / OverflowError of int() or math.ceil on a NaN or an infinity */
+int mpn_prn_train_maps(const double* box, const double* own_kp, const double* img_kp, const int32_t* person_off, int B, int P,
+                       int coeff, double threshold, const double* taps9, const double* taps17, float* input, float* label,
+                       int32_t* err, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Ground-truth heat-maps (datasets/coco_data/heatmap.py:20-41 + COCO_data_pipeline.py:218-236,283):
  * out[b][k][y][x] (f32, 18 keypoint channels) = min(1, sum over people j < num_people[b] with
  * visibility <= 1 of exp(-e) where e = d2/2/sigma/sigma <= 4.6052), float64 arithmetic in annotation

@@ -73,6 +73,7 @@ SIGNATURES = {
     "mpn_gt_heatmaps": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),
     "mpn_augment_image": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i, ctypes.POINTER(ctypes.c_float), _vp]),
     "mpn_augment_mask": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "mpn_prn_train_maps": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpn_heatmap_peaks_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "mpn_heatmap_peaks": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _f, ctypes.c_double, _i, _vp, _vp, _i, _vp, _vp]),
     "mpn_resize": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),

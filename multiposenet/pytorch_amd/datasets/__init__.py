@@ -1,0 +1,1 @@
+from .prn_data import DevicePRNBatcher, PRNDeviceLoader, PRNSampleSet  # noqa: F401
