@@ -131,11 +131,14 @@ typedef struct MpnConvParams {
 
 /* number of pixel tiles (rows of `stats`) mpn_conv_forward will use for this problem */
 int mpn_conv_stats_tiles(const MpnConvParams* p);
-/* output-channel rows of the tile (256 / 128 / 64 / 32) the launcher will pick: names the kernel instantiation */
-int mpn_conv_tile_rows(const MpnConvParams* p);
-/* 1 when the launcher will take conv_igemm_s3_kernel (3x3, stride 1, pad 1, 16-bit operands, dense input: the pixel tile of a kernel
- * row lands once and serves its three taps), 0 for conv_igemm_kernel: names the kernel instantiation */
-int mpn_conv_shared_tile(const MpnConvParams* p);
+/* Host only (no HIP call): writes the NUL-terminated name of the instantiation mpn_conv_forward will launch for p, as rocprofv3 prints it
+ * without the trailing experiments-only profiling flag: conv_igemm[_s3]_kernel<bf16|_Float16|float, TC, 128, OUTF32, GENERAL, EXT> — TC the
+ * output-channel rows of the tile (256 / 128 / 64 / 32); _s3 the shared-pixel-tile kernel (3x3, stride 1, pad 1, 16-bit operands, dense
+ * input: the pixel tile of a kernel row lands once and serves its three taps); GENERAL / EXT the epilogue (an extended one is general).
+ * It is the launcher's own routing decision, so it cannot disagree with the launch.  Returns the length of the name; MPN_E_BADARG for a
+ * null argument, an unknown dtype or a cap that does not hold the name and its NUL; MPN_E_UNSUPPORTED where mpn_conv_forward has no
+ * instantiation (an extended epilogue with out_f32). */
+int mpn_conv_kernel_name(const MpnConvParams* p, char* buf, int cap);
 int mpn_conv_forward(const MpnConvParams* p, void* stream);
 
 typedef struct MpnWgradParams {
@@ -191,6 +194,10 @@ int mpn_conv_wgrad_reduce(const MpnWgradParams* p, void* stream);
 /* which kernel mpn_conv_wgrad launches for p: (tile_cin << 16) | (tile_cout << 4) | linear_x_addressing << 1 | uses_lds_dma
  * (bit 1: the instantiation for stride-1 same-extent convolutions over a dense x — halo predicate only, no per-lane address arithmetic) */
 int mpn_conv_wgrad_kernel_id(const MpnWgradParams* p);
+/* Host only: the name of the instantiation mpn_conv_wgrad / mpn_conv_wgrad_partials will launch for p, from the same routing decision as
+ * the launch and the id above: conv_wgrad_dma[_lin|_seg][_f16|_f32]_kernel<TM, TN>, or conv_wgrad_kernel<T, TM, TN> where the LDS-DMA
+ * kernel does not serve the launch.  Returns and errors as mpn_conv_kernel_name. */
+int mpn_conv_wgrad_kernel_name(const MpnWgradParams* p, char* buf, int cap);
 
 /* dst[i] (+)= sum_{c<chunks} ws[c*n + i]  — deterministic second stage of split reductions */
 int mpn_reduce_partials(const float* ws, int chunks, int64_t n, float* dst, int accumulate, void* stream);

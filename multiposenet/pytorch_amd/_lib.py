@@ -82,8 +82,7 @@ SIGNATURES = {
     "mpn_prn_scores_compact": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpn_prn_match_host": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "mpn_conv_stats_tiles": (_i, [_PC]),
-    "mpn_conv_tile_rows": (_i, [_PC]),
-    "mpn_conv_shared_tile": (_i, [_PC]),
+    "mpn_conv_kernel_name": (_i, [_PC, ctypes.c_char_p, _i]),
     "mpn_conv_forward": (_i, [_PC, _vp]),
     "mpn_debug_wgrad_prof": (_i, [_vp]),
     "mpn_debug_igemm_prof": (_i, [_vp]),
@@ -93,6 +92,7 @@ SIGNATURES = {
     "mpn_conv_wgrad_partials": (_i, [_PW, _vp]),
     "mpn_conv_wgrad_reduce": (_i, [_PW, _vp]),
     "mpn_conv_wgrad_kernel_id": (_i, [_PW]),
+    "mpn_conv_wgrad_kernel_name": (_i, [_PW, ctypes.c_char_p, _i]),
     "mpn_reduce_partials": (_i, [_vp, _i, _i64, _vp, _i, _vp]),
     "mpn_cast_f32_to_bf16": (_i, [_vp, _vp, _i64, _vp]),
     "mpn_cast_f32": (_i, [_vp, _vp, _i64, _i, _vp]),
@@ -180,7 +180,7 @@ SIGNATURES = {
 }
 
 # entry points that return a count, not a status
-_COUNT_FUNCS = {"mpn_conv_stats_tiles", "mpn_conv_tile_rows", "mpn_conv_shared_tile", "mpn_conv_wgrad_chunks", "mpn_conv_wgrad_seg_plan", "mpn_conv_wgrad_kernel_id", "mpn_bn_bwd_chunks", "mpn_channel_sum_chunks",
+_COUNT_FUNCS = {"mpn_conv_stats_tiles", "mpn_conv_kernel_name", "mpn_conv_wgrad_chunks", "mpn_conv_wgrad_seg_plan", "mpn_conv_wgrad_kernel_id", "mpn_conv_wgrad_kernel_name", "mpn_bn_bwd_chunks", "mpn_channel_sum_chunks",
                 "mpn_mse_chunks", "mpn_mse_train_blocks", "mpn_focal_blocks", "mpn_focal_mc_blocks", "mpn_bce_chunks", "mpn_nms_workspace_bytes", "mpn_nms_batched_workspace_bytes", "mpn_heatmap_peaks_workspace_bytes", "mpn_conv2cls_comb_elems", "mpn_grad_absmax_workspace_bytes", "mpn_version"}
 
 _lib = None

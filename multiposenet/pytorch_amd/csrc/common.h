@@ -125,6 +125,8 @@ static inline int mpn_launch_status() {
 #define MPN_CHECK_ARG(cond) do { if (!(cond)) return MPN_E_BADARG; } while (0)
 
 static inline bool mpn_dtype_ok(int dtype) { return dtype == MPN_F32 || dtype == MPN_BF16 || dtype == MPN_F16; }
+// element type of a kernel instantiation as rocprofv3 prints it (mpn_conv_kernel_name, mpn_conv_wgrad_kernel_name)
+static inline const char* mpn_type_name(int dtype) { return dtype == MPN_BF16 ? "bf16" : (dtype == MPN_F16 ? "_Float16" : "float"); }
 
 // run `...` with T bound to the element type of dtype code `dtype` (callers validate the code first)
 #define MPN_DISPATCH_T(dtype, ...)                                              \

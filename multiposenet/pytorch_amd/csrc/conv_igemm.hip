@@ -23,6 +23,7 @@
 // 3x3 / stride 1 / pad 1 launches with 16-bit operands take conv_igemm_s3_kernel (below): same tile, ring and epilogue, but the pixel
 // tile of a kernel row lands once for its three taps (the k-loop is bound by operand delivery, not by MFMA issue).
 #include "common.h"
+#include <stdio.h>
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1015,19 +1016,44 @@ inline bool conv_uses_s3(const MpnConvParams& p, int tc) {
     return p.H == p.Ho && p.W == p.Wo && p.x_sH == (int64_t)p.W * p.x_sW && p.x_sB == (int64_t)p.H * p.x_sH;
 }
 
+// the extended epilogue (see conv_epilogue): only when a launch asks for one of its features
+inline bool conv_needs_ext(const MpnConvParams& p) {
+    return (p.bnb_partial && p.bnb_relu && p.bnb_z && !p.bnb_mask) ||
+           (p.res_mode && p.accumulate) || p.kseg_n > 0 || p.y_step > 1;
+}
+
+// The instantiation a launch takes, decided once: launch_conv() launches from it and mpn_conv_kernel_name() spells it.
+struct ConvRoute {
+    int tc;                 // output-channel rows of the block tile
+    long tilesP;            // pixel tiles
+    bool s3, general, ext;  // shared-pixel-tile 3x3 kernel; GENERAL and EXT as instantiated (an extended epilogue is a general one)
+};
+
+inline ConvRoute conv_route(const MpnConvParams& p) {
+    ConvRoute r;
+    r.tilesP = p.nseg > 0 ? (long)p.seg_tile0[p.nseg] : ((long)p.B * p.Ho * p.Wo + kTP - 1) / kTP;
+    r.tc = pick_tc(p, r.tilesP);
+    r.s3 = conv_uses_s3(p, r.tc);
+    r.ext = conv_needs_ext(p);
+    // "plain" = conv (+ BN tile statistics): no per-element epilogue math at all, lighter register footprint
+    r.general = r.ext || p.scale || p.bias || p.res_mode || p.accumulate || p.act || (p.Cout % r.tc) != 0 || p.bnb_partial;
+    return r;
+}
+
 template <typename T, bool OUTF32, bool GENERAL, bool EXT = false>
-int launch_conv_k(const MpnConvParams& p, int tc, long grid, int dbg, hipStream_t st) {
+int launch_conv_k(const MpnConvParams& p, const ConvRoute& r, long grid, int dbg, hipStream_t st) {
+    const int tc = r.tc;
 #if MPN_EXP
     if constexpr (std::is_same<T, bf16_t>::value && !OUTF32 && !EXT) {
         if (g_igemm_prof && tc == 128 && !p.fin_counters) {
-            if (conv_uses_s3(p, tc)) hipLaunchKernelGGL((conv_igemm_s3_kernel<T, 128, kTP, false, GENERAL, false, true>), dim3((unsigned)grid), dim3(256), 0, st, p, dbg);
+            if (r.s3) hipLaunchKernelGGL((conv_igemm_s3_kernel<T, 128, kTP, false, GENERAL, false, true>), dim3((unsigned)grid), dim3(256), 0, st, p, dbg);
             else hipLaunchKernelGGL((conv_igemm_kernel<T, 128, kTP, false, GENERAL, false, true>), dim3((unsigned)grid), dim3(256), 0, st, p, dbg);
             return mpn_launch_status();
         }
     }
 #endif
     if constexpr (sizeof(T) == 2) {
-        if (conv_uses_s3(p, tc)) {
+        if (r.s3) {
             if (tc == 256) hipLaunchKernelGGL((conv_igemm_s3_kernel<T, 256, kTP, OUTF32, GENERAL, EXT>), dim3((unsigned)grid), dim3(256), 0, st, p, dbg);
             else if (tc == 128) hipLaunchKernelGGL((conv_igemm_s3_kernel<T, 128, kTP, OUTF32, GENERAL, EXT>), dim3((unsigned)grid), dim3(256), 0, st, p, dbg);
             else hipLaunchKernelGGL((conv_igemm_s3_kernel<T, 64, kTP, OUTF32, GENERAL, EXT>), dim3((unsigned)grid), dim3(256), 0, st, p, dbg);
@@ -1045,28 +1071,19 @@ int launch_conv_k(const MpnConvParams& p, int tc, long grid, int dbg, hipStream_
     return mpn_launch_status();
 }
 
-// the extended epilogue (see conv_epilogue): only when a launch asks for one of its features
-inline bool conv_needs_ext(const MpnConvParams& p) {
-    return (p.bnb_partial && p.bnb_relu && p.bnb_z && !p.bnb_mask) ||
-           (p.res_mode && p.accumulate) || p.kseg_n > 0 || p.y_step > 1;
-}
-
 template <typename T, bool OUTF32>
 int launch_conv(const MpnConvParams& p, hipStream_t st) {
-    const long P = p.nseg > 0 ? (long)p.seg_tile0[p.nseg] * kTP : (long)p.B * p.Ho * p.Wo;
-    const long tilesP = p.nseg > 0 ? (long)p.seg_tile0[p.nseg] : (P + kTP - 1) / kTP;
-    const int tc = pick_tc(p, tilesP);
-    const long tilesC = (p.Cout_store + tc - 1) / tc;
-    const long grid = tilesP * tilesC;
+    const ConvRoute r = conv_route(p);
+    const long P = p.nseg > 0 ? r.tilesP * kTP : (long)p.B * p.Ho * p.Wo;
+    const long tilesC = (p.Cout_store + r.tc - 1) / r.tc;
+    const long grid = r.tilesP * tilesC;
     if (grid <= 0 || grid > 0x7fffffffL || P >= 0x7fffffffL) return MPN_E_BADARG;
     static const int dbg = (int)mpn_tune("MPN_DEBUG_FLAGS", 0);   // microbenchmark ablations (experiments build only)
-    // "plain" = conv (+ BN tile statistics): no per-element epilogue math at all, lighter register footprint
-    const bool general = p.scale || p.bias || p.res_mode || p.accumulate || p.act || (p.Cout % tc) != 0 || p.bnb_partial;
-    if (conv_needs_ext(p)) {
+    if (r.ext) {
         if constexpr (OUTF32) return MPN_E_UNSUPPORTED;          // none of the extended features writes f32 from 16-bit operands
-        else return launch_conv_k<T, false, true, true>(p, tc, grid, dbg, st);
+        else return launch_conv_k<T, false, true, true>(p, r, grid, dbg, st);
     }
-    return general ? launch_conv_k<T, OUTF32, true>(p, tc, grid, dbg, st) : launch_conv_k<T, OUTF32, false>(p, tc, grid, dbg, st);
+    return r.general ? launch_conv_k<T, OUTF32, true>(p, r, grid, dbg, st) : launch_conv_k<T, OUTF32, false>(p, r, grid, dbg, st);
 }
 
 }  // namespace
@@ -1088,16 +1105,14 @@ extern "C" int mpn_conv_stats_tiles(const MpnConvParams* p) {
     return (int)((P + kTP - 1) / kTP);
 }
 
-extern "C" int mpn_conv_tile_rows(const MpnConvParams* p) {
-    if (!p) return MPN_E_BADARG;
-    const long P = (long)p->B * p->Ho * p->Wo;
-    return pick_tc(*p, p->nseg > 0 ? (long)p->seg_tile0[p->nseg] : (P + kTP - 1) / kTP);
-}
-
-extern "C" int mpn_conv_shared_tile(const MpnConvParams* p) {
-    if (!p) return MPN_E_BADARG;
-    const long P = (long)p->B * p->Ho * p->Wo;
-    return conv_uses_s3(*p, pick_tc(*p, p->nseg > 0 ? (long)p->seg_tile0[p->nseg] : (P + kTP - 1) / kTP)) ? 1 : 0;
+extern "C" int mpn_conv_kernel_name(const MpnConvParams* p, char* buf, int cap) {
+    if (!p || !buf || cap <= 0 || !mpn_dtype_ok(p->dtype)) return MPN_E_BADARG;
+    const ConvRoute r = conv_route(*p);
+    const bool outf32 = p->out_f32 && p->dtype != MPN_F32;       // mpn_conv_forward: f32 operands are OT == T == float
+    if (r.ext && outf32) return MPN_E_UNSUPPORTED;               // as launch_conv(): no such instantiation
+    const int n = snprintf(buf, (size_t)cap, "conv_igemm%s_kernel<%s, %d, %d, %s, %s, %s>", r.s3 ? "_s3" : "", mpn_type_name(p->dtype), r.tc, kTP,
+                           outf32 ? "true" : "false", r.general ? "true" : "false", r.ext ? "true" : "false");
+    return n < cap ? n : MPN_E_BADARG;
 }
 
 extern "C" int mpn_conv_forward(const MpnConvParams* pp, void* stream) {

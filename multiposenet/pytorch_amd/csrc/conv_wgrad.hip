@@ -17,6 +17,7 @@
 //     partials to a workspace and mpn_reduce_partials adds them into dW in a fixed order
 //     (deterministic; no atomics).  chunks == 1 accumulates straight into dW.
 #include "common.h"
+#include <stdio.h>
 #include <stdlib.h>
 
 namespace {
@@ -798,28 +799,40 @@ inline bool wgrad_lin_ok(const MpnWgradParams& p) {
 
 constexpr long kWgradTarget = 512;       // workgroups per launch (~2 per CU): long slices, little partial-sum traffic
 
-inline void wgrad_tiles(const MpnWgradParams& p, int& tm, int& tn) {
-    tm = pick_tile(p.Cin); tn = pick_tile(p.Cout);
-    if (!wgrad_uses_dma(p)) return;
-    if (tm < 64) tm = 64;
-    if (tn < 64) tn = 64;
+// The instantiation a launch takes, decided once: launch_wgrad() launches from it, mpn_conv_wgrad_kernel_id() packs it and
+// mpn_conv_wgrad_kernel_name() spells it.
+struct WgradRoute {
+    int tm, tn;             // cin / cout rows of the block tile
+    bool dma, lin, seg;     // LDS-DMA kernel; its linear-addressing and its pyramid instantiation (at most one of the two)
+};
+
+inline WgradRoute wgrad_route(const MpnWgradParams& p) {
+    WgradRoute r;
+    r.tm = pick_tile(p.Cin); r.tn = pick_tile(p.Cout);
+    r.dma = wgrad_uses_dma(p);
+    r.seg = r.dma && p.nseg > 0;
+    r.lin = r.dma && !r.seg && wgrad_lin_ok(p);
+    if (!r.dma) return r;
+    if (r.tm < 64) r.tm = 64;
+    if (r.tn < 64) r.tn = 64;
     // A 256 x 128 tile moves a third less data per FLOP through the DMA/LDS path (it pays in conv_igemm), but here it
     // measured SLOWER (3x3 256->256 @60x60: 243 vs 208 us, 512->256 @120x120: 1595 vs 1431 us): with two workgroups
     // per CU the transpose reads are no longer hidden and the slice count (partial-sum traffic) doubles.  Kept behind
     // MPN_WGRAD_TM256_MIN_STEPS (minimum k-steps per workgroup) for experiments, off by default.
     static const long min_steps = mpn_tune("MPN_WGRAD_TM256_MIN_STEPS", 1L << 40);
-    if (p.dtype != MPN_F32 && p.Cin >= 256 && tn == 128) {        // (the f32 ring kernel has no 256-row instantiation)
+    if (p.dtype != MPN_F32 && p.Cin >= 256 && r.tn == 128) {        // (the f32 ring kernel has no 256-row instantiation)
         const long tiles = (long)((p.Cin + 255) / 256) * ((p.Cout + 127) / 128) * p.R * p.S;
         const long chunks = (kWgradTarget + tiles - 1) / tiles;
         const long P = (long)p.B * p.Ho * p.Wo;
-        if (P / 32 / chunks >= min_steps) tm = 256;
+        if (P / 32 / chunks >= min_steps) r.tm = 256;
     }
+    return r;
 }
 
 template <typename T>
 int launch_wgrad(const MpnWgradParams& p, hipStream_t st, bool reduce = true) {
-    int tm, tn;
-    wgrad_tiles(p, tm, tn);
+    const WgradRoute r = wgrad_route(p);
+    const int tm = r.tm, tn = r.tn;
     const long tilesM = (p.Cin + tm - 1) / tm, tilesN = (p.Cout + tn - 1) / tn;
     const long P = wgrad_total_pixels(p);
     const int kp = sizeof(T) == 2 ? 32 : 16;
@@ -834,34 +847,33 @@ int launch_wgrad(const MpnWgradParams& p, hipStream_t st, bool reduce = true) {
     if ((ablate & 1) && p.chunks > 1) reduce = false;
     int rc;
     const dim3 g((unsigned)grid), blk(256);
-    if (sizeof(T) == 4 && wgrad_uses_dma(p)) {
+    if (sizeof(T) == 4 && r.dma) {
 #define MPN_WGRAD_DMA_LAUNCH_F32(KERNEL)                                                                                 \
         if (tm == 128 && tn == 128) hipLaunchKernelGGL((KERNEL<128, 128>), g, blk, 0, st, p, chunk_pixels);              \
         else if (tm == 128) hipLaunchKernelGGL((KERNEL<128, 64>), g, blk, 0, st, p, chunk_pixels);                       \
         else if (tn == 128) hipLaunchKernelGGL((KERNEL<64, 128>), g, blk, 0, st, p, chunk_pixels);                       \
         else hipLaunchKernelGGL((KERNEL<64, 64>), g, blk, 0, st, p, chunk_pixels)
-        if (wgrad_lin_ok(p)) { MPN_WGRAD_DMA_LAUNCH_F32(conv_wgrad_dma_lin_f32_kernel); }
+        if (r.lin) { MPN_WGRAD_DMA_LAUNCH_F32(conv_wgrad_dma_lin_f32_kernel); }
         else { MPN_WGRAD_DMA_LAUNCH_F32(conv_wgrad_dma_f32_kernel); }
 #undef MPN_WGRAD_DMA_LAUNCH_F32
         rc = mpn_launch_status();
-    } else if (sizeof(T) == 2 && wgrad_uses_dma(p)) {
+    } else if (sizeof(T) == 2 && r.dma) {
 #define MPN_WGRAD_DMA_LAUNCH(KERNEL)                                                                                     \
         if (tm == 256) hipLaunchKernelGGL((KERNEL<256, 128>), g, blk, 0, st, p, chunk_pixels);                           \
         else if (tm == 128 && tn == 128) hipLaunchKernelGGL((KERNEL<128, 128>), g, blk, 0, st, p, chunk_pixels);         \
         else if (tm == 128) hipLaunchKernelGGL((KERNEL<128, 64>), g, blk, 0, st, p, chunk_pixels);                       \
         else if (tn == 128) hipLaunchKernelGGL((KERNEL<64, 128>), g, blk, 0, st, p, chunk_pixels);                       \
         else hipLaunchKernelGGL((KERNEL<64, 64>), g, blk, 0, st, p, chunk_pixels)
-        const bool lin = wgrad_lin_ok(p);
 #if MPN_EXP
-        if (g_wgrad_prof && p.nseg == 0 && p.dtype == MPN_BF16 && tm == 128 && tn == 128) {
-            if (lin) hipLaunchKernelGGL((conv_wgrad_dma_lin_prof_kernel<128, 128>), g, blk, 0, st, p, chunk_pixels, g_wgrad_prof);
+        if (g_wgrad_prof && !r.seg && p.dtype == MPN_BF16 && tm == 128 && tn == 128) {
+            if (r.lin) hipLaunchKernelGGL((conv_wgrad_dma_lin_prof_kernel<128, 128>), g, blk, 0, st, p, chunk_pixels, g_wgrad_prof);
             else hipLaunchKernelGGL((conv_wgrad_dma_prof_kernel<128, 128>), g, blk, 0, st, p, chunk_pixels, g_wgrad_prof);
         } else
 #endif
-        if (p.nseg == 0 && lin) {
+        if (r.lin) {
             if (p.dtype == MPN_F16) { MPN_WGRAD_DMA_LAUNCH(conv_wgrad_dma_lin_f16_kernel); }
             else { MPN_WGRAD_DMA_LAUNCH(conv_wgrad_dma_lin_kernel); }
-        } else if (p.nseg > 0) {
+        } else if (r.seg) {
             if (p.dtype == MPN_F16) { MPN_WGRAD_DMA_LAUNCH(conv_wgrad_dma_seg_f16_kernel); }
             else { MPN_WGRAD_DMA_LAUNCH(conv_wgrad_dma_seg_kernel); }
         } else if (p.dtype == MPN_F16) { MPN_WGRAD_DMA_LAUNCH(conv_wgrad_dma_f16_kernel); }
@@ -920,14 +932,13 @@ extern "C" int mpn_conv_wgrad_seg_plan(MpnWgradParams* p) {
 
 extern "C" int mpn_conv_wgrad_chunks(const MpnWgradParams* p) {
     if (!p) return MPN_E_BADARG;
-    int tm, tn;
-    wgrad_tiles(*p, tm, tn);
-    const long tiles = (long)((p->Cin + tm - 1) / tm) * ((p->Cout + tn - 1) / tn) * p->R * p->S;
+    const WgradRoute r = wgrad_route(*p);
+    const long tiles = (long)((p->Cin + r.tm - 1) / r.tm) * ((p->Cout + r.tn - 1) / r.tn) * p->R * p->S;
     const long P = wgrad_total_pixels(*p);
     static const long target16 = mpn_tune("MPN_WGRAD_TARGET", kWgradTarget);
     // f32 launches that fall back to the register-staged generic kernel (matrix-pipe bound, no DMA ring): three workgroups per CU's worth
     // of slices (cfg2 55.7 -> 55.1 ms; 256: 62.3); on the ring 512 and 768 measure the same (52.06 / 52.08 ms), 1024 worse
-    const long target = (p->dtype == MPN_F32 && !wgrad_uses_dma(*p) && target16 == kWgradTarget) ? 768 : target16;
+    const long target = (p->dtype == MPN_F32 && !r.dma && target16 == kWgradTarget) ? 768 : target16;
     static const long minpix = mpn_tune("MPN_WGRAD_MINPIX", 512);
     // ~2 workgroups per CU (long slices run near peak, partial-sum traffic dominates beyond) and NEVER one more than that: rounding the
     // slice count up put 540 workgroups on the 512 slots of the 3x3 256-channel layers — the 28 that share a CU three ways finish last,
@@ -956,9 +967,8 @@ extern "C" int mpn_conv_wgrad(const MpnWgradParams* pp, void* stream) {
         MPN_CHECK_ARG((p.x || p.kseg_n > 0) && p.dy && p.Ho > 0 && p.Wo > 0);
     }
     if (p.kseg_n > 0) {
-        int tm, tn;
-        wgrad_tiles(p, tm, tn);
-        MPN_CHECK_ARG(p.kseg_n <= 4 && p.kseg_c == 128 && tm == 128 && p.Cin == p.kseg_n * p.kseg_c && wgrad_uses_dma(p) && p.stride == 1);
+        const WgradRoute r = wgrad_route(p);
+        MPN_CHECK_ARG(p.kseg_n <= 4 && p.kseg_c == 128 && r.tm == 128 && p.Cin == p.kseg_n * p.kseg_c && r.dma && p.stride == 1);
         for (int k = 0; k < p.kseg_n; ++k)
             MPN_CHECK_ARG(p.kseg_x[k] && p.kseg_shift[k] >= 0 && p.kseg_shift[k] < 8 && ((p.H >> p.kseg_shift[k]) << p.kseg_shift[k]) == p.H &&
                           ((p.W >> p.kseg_shift[k]) << p.kseg_shift[k]) == p.W);
@@ -993,10 +1003,17 @@ extern "C" int mpn_conv_wgrad_reduce(const MpnWgradParams* pp, void* stream) {
 
 extern "C" int mpn_conv_wgrad_kernel_id(const MpnWgradParams* p) {
     if (!p) return MPN_E_BADARG;
-    int tm, tn;
-    wgrad_tiles(*p, tm, tn);
-    const bool dma = wgrad_uses_dma(*p);
-    return (tm << 16) | (tn << 4) | (dma && p->nseg == 0 && wgrad_lin_ok(*p) ? 2 : 0) | (dma ? 1 : 0);      // bit 1: the linear-addressing instantiation
+    const WgradRoute r = wgrad_route(*p);
+    return (r.tm << 16) | (r.tn << 4) | (r.lin ? 2 : 0) | (r.dma ? 1 : 0);      // bit 1: the linear-addressing instantiation
+}
+
+extern "C" int mpn_conv_wgrad_kernel_name(const MpnWgradParams* p, char* buf, int cap) {
+    if (!p || !buf || cap <= 0 || !mpn_dtype_ok(p->dtype)) return MPN_E_BADARG;
+    const WgradRoute r = wgrad_route(*p);
+    const int n = r.dma ? snprintf(buf, (size_t)cap, "conv_wgrad_dma%s%s_kernel<%d, %d>", r.lin ? "_lin" : (r.seg ? "_seg" : ""),
+                                   p->dtype == MPN_F16 ? "_f16" : (p->dtype == MPN_F32 ? "_f32" : ""), r.tm, r.tn)
+                        : snprintf(buf, (size_t)cap, "conv_wgrad_kernel<%s, %d, %d>", mpn_type_name(p->dtype), r.tm, r.tn);
+    return n < cap ? n : MPN_E_BADARG;
 }
 
 extern "C" int mpn_reduce_partials(const float* ws, int chunks, int64_t n, float* dst, int accumulate, void* stream) {

@@ -71,11 +71,6 @@ def is16(dt):
     return dt == torch.bfloat16 or dt == torch.float16
 
 
-def dtype_name(dt):
-    """Element-type spelling rocprofv3 prints for a kernel instantiation (tools/rocprof_summary.py)."""
-    return "bf16" if dt == torch.bfloat16 else ("_Float16" if dt == torch.float16 else "float")
-
-
 def ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -185,6 +180,57 @@ def workspace(nbytes, device, slot=0):
     return buf
 
 
+def _kernel_name(query, p):
+    """The instantiation the library launches for the parameter block p, as rocprofv3 spells it (`query`: mpn_conv_kernel_name or
+    mpn_conv_wgrad_kernel_name — the launcher's own routing decision; nothing here re-derives it)."""
+    buf = ctypes.create_string_buffer(128)
+    n = call(query, ctypes.byref(p), buf, len(buf))
+    if n < 0:
+        raise _lib.MpnError("%s failed with status %d" % (query, n))
+    return buf.value.decode()
+
+
+def _launch_conv(p, flops, label):
+    """The one mpn_conv_forward call site.  flops() / label() (algorithmic FLOPs; the shape label of tools/shape_report.py) are only
+    evaluated while KERNEL_EVENTS brackets the launch."""
+    events = KERNEL_EVENTS.on
+    if events:
+        # KERNEL_EVENTS classes keep the five-argument spelling bench.py's pmc_traffic keys on: the library's name without its last (EXT) argument
+        name = label() if KERNEL_EVENTS.detail else _kernel_name("mpn_conv_kernel_name", p).rsplit(", ", 1)[0] + ">"
+        e0 = KERNEL_EVENTS.begin()
+    call("mpn_conv_forward", ctypes.byref(p), stream_ptr())
+    if events:
+        KERNEL_EVENTS.end(name, flops(), e0)
+
+
+def _launch_wgrad(p, dev, db, flops, label, plan="mpn_conv_wgrad_chunks"):
+    """The one weight-gradient call site: splits the contraction (`plan`: mpn_conv_wgrad_chunks, or mpn_conv_wgrad_seg_plan for a pyramid),
+    attaches the partial-sum workspaces and the bias gradient db the launch fuses (None: not fused), and launches.  flops() / label(chunks)
+    as in _launch_conv."""
+    p.chunks = 1
+    chunks = call(plan, ctypes.byref(p))
+    if chunks < 1:
+        raise _lib.MpnError("%s failed with status %d" % (plan, chunks))
+    p.chunks = chunks
+    if chunks > 1:
+        p.ws = workspace(chunks * p.Cout * p.R * p.S * p.Cin * 4, dev, slot=1).data_ptr()
+    if db is not None:
+        p.db = db.data_ptr()
+        if chunks > 1:
+            p.db_ws = workspace(chunks * p.Cout * 4, dev, slot=4).data_ptr()
+    events = KERNEL_EVENTS.on
+    if events:
+        name = label(chunks) if KERNEL_EVENTS.detail else _kernel_name("mpn_conv_wgrad_kernel_name", p)
+        e0 = KERNEL_EVENTS.begin()
+    # under events the MFMA kernel is bracketed alone (the partial-sum reduction is launched separately) so the class time matches the
+    # kernel's own row in a rocprofv3 trace
+    call("mpn_conv_wgrad_partials" if events and chunks > 1 else "mpn_conv_wgrad", ctypes.byref(p), stream_ptr())
+    if events:
+        KERNEL_EVENTS.end(name, flops(), e0)
+        if chunks > 1:          # the reduction mpn_conv_wgrad runs (same kernels and order: the same bits as without events)
+            call("mpn_conv_wgrad_reduce", ctypes.byref(p), stream_ptr())
+
+
 def alloc_seg(like, C, dtype):
     """One buffer holding an activation per pyramid level (geometry of the Acts in `like`, C channels): the levels are views
     of a single flat tensor, so element-wise kernels can treat the whole pyramid as one array."""
@@ -239,17 +285,8 @@ def conv_forward_seg(xs, w, Cout, R, S, pad, bias=None, act=0, out_f32=False, mo
         p.seg_tile0[l] = tile0
         tile0 += (x.B * x.H * x.W + 127) // 128
     p.seg_tile0[len(xs)] = tile0
-    if KERNEL_EVENTS.on:
-        e0 = KERNEL_EVENTS.begin()
-        call("mpn_conv_forward", ctypes.byref(p), stream_ptr())
-        tc = call("mpn_conv_tile_rows", ctypes.byref(p))
-        general = (bias is not None or accumulate or act != 0 or Cout % tc != 0)
-        name = ("conv_igemm_s3_kernel" if call("mpn_conv_shared_tile", ctypes.byref(p)) == 1 else "conv_igemm_kernel") + "<%s, %d, 128, %s, %s>" % (dtype_name(dt), tc, "true" if p.out_f32 else "false", "true" if general else "false")
-        if KERNEL_EVENTS.detail:
-            name = "%s %dx%d %d->%d pyramid(%s)|0" % ("dgrad" if mode == 1 else "fwd", R, S, p.Cin, Cout, ",".join(str(x.H) for x in xs))
-        KERNEL_EVENTS.end(name, sum(2.0 * x.B * x.H * x.W * Cout * R * S * min(p.Cin, x.C) for x in xs), e0)
-    else:
-        call("mpn_conv_forward", ctypes.byref(p), stream_ptr())
+    _launch_conv(p, lambda: sum(2.0 * x.B * x.H * x.W * Cout * R * S * min(p.Cin, x.C) for x in xs),
+                 lambda: "%s %dx%d %d->%d pyramid(%s)|0" % ("dgrad" if mode == 1 else "fwd", R, S, p.Cin, Cout, ",".join(str(x.H) for x in xs)))
     return outs
 
 
@@ -267,32 +304,12 @@ def conv_wgrad_seg(xs, dys, dw, Cout, R, S, pad, db=None):
     for l, (x, d) in enumerate(zip(xs, dys)):
         p.seg_x[l], p.seg_dy[l] = x.t.data_ptr(), d.t.data_ptr()
         p.seg_H[l], p.seg_W[l] = x.H, x.W
-    p.chunks = 1
     if not (call("mpn_conv_wgrad_kernel_id", ctypes.byref(p)) & 1):
         return False, False
-    chunks = call("mpn_conv_wgrad_seg_plan", ctypes.byref(p))
-    if chunks < 1:
-        raise _lib.MpnError("mpn_conv_wgrad_seg_plan failed with status %d" % chunks)
-    if chunks > 1:
-        p.ws = workspace(chunks * Cout * R * S * x0.C * 4, dev, slot=1).data_ptr()
-    fused_db = db is not None
-    if fused_db:
-        p.db = db.data_ptr()
-        if chunks > 1:
-            p.db_ws = workspace(chunks * Cout * 4, dev, slot=4).data_ptr()
-    if KERNEL_EVENTS.on:
-        kid = call("mpn_conv_wgrad_kernel_id", ctypes.byref(p))
-        e0 = KERNEL_EVENTS.begin()
-        call("mpn_conv_wgrad_partials" if chunks > 1 else "mpn_conv_wgrad", ctypes.byref(p), stream_ptr())
-        name = "conv_wgrad_dma_seg%s_kernel<%d, %d>" % ("_f16" if dt == torch.float16 else "", kid >> 16, (kid >> 4) & 0xfff)
-        if KERNEL_EVENTS.detail:
-            name = "wgrad %dx%d %d->%d pyramid(%s) chunks=%d|0" % (R, S, x0.C, Cout, ",".join(str(x.H) for x in xs), chunks)
-        KERNEL_EVENTS.end(name, sum(2.0 * x.B * x.H * x.W * Cout * R * S * x.C for x in xs), e0)
-        if chunks > 1:          # the reduction mpn_conv_wgrad runs (same kernels and order: the same bits as without events)
-            call("mpn_conv_wgrad_reduce", ctypes.byref(p), stream_ptr())
-    else:
-        call("mpn_conv_wgrad", ctypes.byref(p), stream_ptr())
-    return True, fused_db
+    _launch_wgrad(p, dev, db, lambda: sum(2.0 * x.B * x.H * x.W * Cout * R * S * x.C for x in xs),
+                  lambda chunks: "wgrad %dx%d %d->%d pyramid(%s) chunks=%d|0" % (R, S, x0.C, Cout, ",".join(str(x.H) for x in xs), chunks),
+                  plan="mpn_conv_wgrad_seg_plan")
+    return True, db is not None
 
 
 def _kseg_fill(p, srcs, H, W):
@@ -340,17 +357,9 @@ def conv_forward_cat(srcs, H, W, w, Cout, bias=None, act=0, tag="", res=None):
         p.res, p.res_mode = res.t.data_ptr(), 1
         p.res_sB, p.res_sP = H * W * res.Cs, res.Cs
         p.res_H, p.res_W = H, W
-    if KERNEL_EVENTS.on:
-        e0 = KERNEL_EVENTS.begin()
-        call("mpn_conv_forward", ctypes.byref(p), stream_ptr())
-        tc = call("mpn_conv_tile_rows", ctypes.byref(p))
-        name = "conv_igemm_s3_kernel<%s, %d, 128, false, true>" % (dtype_name(dt), tc)
-        if KERNEL_EVENTS.detail:
-            name = "fwd 3x3 %d->%d @%dx%d s1 virtual-cat%s%s|%d" % (p.Cin, Cout, H, W, " bias" if bias is not None else "", " act%d" % act if act else "",
-                                                                    sum(a.t.numel() for a in srcs) * 2 + out.t.numel() * 2)
-        KERNEL_EVENTS.end(name, 2.0 * x0.B * H * W * Cout * 9 * p.Cin, e0)
-    else:
-        call("mpn_conv_forward", ctypes.byref(p), stream_ptr())
+    _launch_conv(p, lambda: 2.0 * x0.B * H * W * Cout * 9 * p.Cin,
+                 lambda: "fwd 3x3 %d->%d @%dx%d s1 virtual-cat%s%s|%d" % (p.Cin, Cout, H, W, " bias" if bias is not None else "", " act%d" % act if act else "",
+                                                                         sum(a.t.numel() for a in srcs) * 2 + out.t.numel() * 2))
     return out
 
 
@@ -368,29 +377,10 @@ def conv_wgrad_cat(srcs, H, W, dy, dw, Cout, db=None):
     p.Ho, p.Wo, p.Cout = H, W, Cout
     p.R, p.S, p.stride, p.pad = 3, 3, 1, 1
     p.dtype = dtype_code(dt)
-    p.chunks = 1
-    chunks = call("mpn_conv_wgrad_chunks", ctypes.byref(p))
-    p.chunks = chunks
-    if chunks > 1:
-        p.ws = workspace(chunks * Cout * 9 * Cin * 4, dev, slot=1).data_ptr()
-    fused_db = db is not None
-    if fused_db:
-        p.db = db.data_ptr()
-        if chunks > 1:
-            p.db_ws = workspace(chunks * Cout * 4, dev, slot=4).data_ptr()
-    if KERNEL_EVENTS.on:
-        kid = call("mpn_conv_wgrad_kernel_id", ctypes.byref(p))
-        e0 = KERNEL_EVENTS.begin()
-        call("mpn_conv_wgrad_partials" if chunks > 1 else "mpn_conv_wgrad", ctypes.byref(p), stream_ptr())
-        name = "conv_wgrad_dma%s%s_kernel<%d, %d>" % ("_lin" if (kid & 2) else "", "_f16" if dt == torch.float16 else "", kid >> 16, (kid >> 4) & 0xfff)
-        if KERNEL_EVENTS.detail:
-            name = "wgrad 3x3 %d->%d @%dx%d s1 virtual-cat chunks=%d|%d" % (Cin, Cout, H, W, chunks, sum(a.t.numel() for a in srcs) * 2 + dy.t.numel() * 2)
-        KERNEL_EVENTS.end(name, 2.0 * x0.B * H * W * Cout * 9 * Cin, e0)
-        if chunks > 1:          # the reduction mpn_conv_wgrad runs (same kernels and order: the same bits as without events)
-            call("mpn_conv_wgrad_reduce", ctypes.byref(p), stream_ptr())
-    else:
-        call("mpn_conv_wgrad", ctypes.byref(p), stream_ptr())
-    return fused_db
+    _launch_wgrad(p, dev, db, lambda: 2.0 * x0.B * H * W * Cout * 9 * Cin,
+                  lambda chunks: "wgrad 3x3 %d->%d @%dx%d s1 virtual-cat chunks=%d|%d" % (Cin, Cout, H, W, chunks,
+                                                                                       sum(a.t.numel() for a in srcs) * 2 + dy.t.numel() * 2))
+    return db is not None
 
 
 # ---- conv2 of the keypoint head by position classes (csrc/conv2cls.hip) -------------------------------------------------------------
@@ -558,7 +548,7 @@ def conv_forward(x, w, Cout, R, S, stride, pad, bias=None, scale=None, act=0, re
             # the BNState comes back in the stats slot
             gamma, beta, rm, rv, momentum, eps = bn_fin
             keep, stats = stats, BNState(Cout, dev)
-            fin_attach(p, tiles, Cout, dev)
+            p.fin_counters = fin_counters(dev).data_ptr()
             p.fin_gamma, p.fin_beta = gamma.data_ptr(), beta.data_ptr()
             p.fin_rm = rm.data_ptr() if rm is not None else None
             p.fin_rv = rv.data_ptr() if rv is not None else None
@@ -588,7 +578,7 @@ def conv_forward(x, w, Cout, R, S, stride, pad, bias=None, scale=None, act=0, re
             # dy = k1*g + k2*y + k3 (mpn_bn_bwd_finalize's work); the coefficient tensor comes back in the stats slot
             gamma, train, dgamma, dbeta = bnb[4]
             keep, stats = stats, (torch.empty((3, Cout), dtype=torch.float32, device=dev) if train else None)
-            fin_attach(p, tiles, Cout, dev)
+            p.fin_counters = fin_counters(dev).data_ptr()
             p.fin_gamma = gamma.data_ptr()
             p.fin_out = stats.data_ptr() if stats is not None else None
             p.fin_dgamma = dgamma.data_ptr() if dgamma is not None else None
@@ -596,30 +586,23 @@ def conv_forward(x, w, Cout, R, S, stride, pad, bias=None, scale=None, act=0, re
             p.fin_count, p.fin_train = float(x.B * Ho * Wo), 1 if train else 0
             if stats is None:
                 stats = "frozen"
-    if KERNEL_EVENTS.on:
-        e0 = KERNEL_EVENTS.begin()
-        call("mpn_conv_forward", ctypes.byref(p), stream_ptr())
-        tc = call("mpn_conv_tile_rows", ctypes.byref(p))
+
+    def flops():
         # algorithmic FLOPs: 2 * output pixels * Cout * taps * Cin; a stride-s dgrad only has 1/s^2 live taps
         live = (R * S) / float(stride * stride) if mode == 1 else R * S
-        flops = 2.0 * x.B * Ho * Wo * Cout * live * min(Cin, x.C if x_geom is None else Cin)
-        # the name rocprofv3 prints for this instantiation (tools/rocprof_summary.py spelling)
-        general = (scale is not None or bias is not None or res is not None or accumulate or act != 0 or Cout % tc != 0 or bnb is not None)
-        kind = call("mpn_conv_shared_tile", ctypes.byref(p))
-        name = ("conv_igemm_s3_kernel" if kind == 1 else "conv_igemm_kernel") + "<%s, %d, 128, %s, %s>" % (dtype_name(dt), tc,
-                                                          "true" if p.out_f32 else "false", "true" if general else "false")
-        if KERNEL_EVENTS.detail:
-            es = 2 if is16(dt) else 4
-            byts = x.B * H * W * Cin * es + x.B * Ho * Wo * p.Cout_store * (4 if out_f32 else es) * (2 if accumulate else 1) \
-                + (x.B * Ho * Wo * p.Cout_store * es if res is not None and res_mode == 1 else 0)
-            name = "%s %dx%d %d->%d @%dx%d s%d%s%s%s%s%s|%d" % (
-                ("dgrad s2 class(%d,%d)" % (_cls[0], _cls[1])) if _cls is not None else ("dgrad" if mode == 1 else "fwd"), R, S, Cin, Cout, Ho, Wo, stride,
-                " stats" if want_stats else "",
-                " bias" if bias is not None else "", " act%d" % act if act else "", " res%d" % res_mode if res is not None else "",
-                " acc" if accumulate else "", byts)
-        KERNEL_EVENTS.end(name, flops, e0)
-    else:
-        call("mpn_conv_forward", ctypes.byref(p), stream_ptr())
+        return 2.0 * x.B * Ho * Wo * Cout * live * min(Cin, x.C if x_geom is None else Cin)
+
+    def label():
+        es = 2 if is16(dt) else 4
+        byts = x.B * H * W * Cin * es + x.B * Ho * Wo * p.Cout_store * (4 if out_f32 else es) * (2 if accumulate else 1) \
+            + (x.B * Ho * Wo * p.Cout_store * es if res is not None and res_mode == 1 else 0)
+        return "%s %dx%d %d->%d @%dx%d s%d%s%s%s%s%s|%d" % (
+            ("dgrad s2 class(%d,%d)" % (_cls[0], _cls[1])) if _cls is not None else ("dgrad" if mode == 1 else "fwd"), R, S, Cin, Cout, Ho, Wo, stride,
+            " stats" if want_stats else "",
+            " bias" if bias is not None else "", " act%d" % act if act else "", " res%d" % res_mode if res is not None else "",
+            " acc" if accumulate else "", byts)
+
+    _launch_conv(p, flops, label)
     return out, stats
 
 
@@ -679,36 +662,10 @@ def conv_wgrad(x, dy, dw, Cout, R, S, stride, pad, cin=None, x_geom=None, db=Non
     p.Ho, p.Wo, p.Cout = dy.H, dy.W, Cout
     p.R, p.S, p.stride, p.pad = R, S, stride, pad
     p.dtype = dtype_code(dt)
-    p.chunks = 1
-    chunks = call("mpn_conv_wgrad_chunks", ctypes.byref(p))
-    p.chunks = chunks
-    if chunks > 1:
-        ws = workspace(chunks * Cout * R * S * Cin * 4, dev, slot=1)
-        p.ws = ws.data_ptr()
-    fused_db = False
-    if db is not None and (call("mpn_conv_wgrad_kernel_id", ctypes.byref(p)) & 1):
-        fused_db = True
-        p.db = db.data_ptr()
-        if chunks > 1:
-            p.db_ws = workspace(chunks * Cout * 4, dev, slot=4).data_ptr()
-    if KERNEL_EVENTS.on:
-        # bracket the MFMA kernel alone (the partial-sum reduction is launched separately) so the class time
-        # matches the kernel's own row in a rocprofv3 trace
-        kid = call("mpn_conv_wgrad_kernel_id", ctypes.byref(p))
-        e0 = KERNEL_EVENTS.begin()
-        call("mpn_conv_wgrad_partials" if chunks > 1 else "mpn_conv_wgrad", ctypes.byref(p), stream_ptr())
-        dts = dtype_name(dt)
-        name = ("conv_wgrad_dma%s%s_kernel<%d, %d>" % ("_lin" if (kid & 2) else "", {torch.float16: "_f16", torch.float32: "_f32"}.get(dt, ""), kid >> 16, (kid >> 4) & 0xfff) if (kid & 1)
-                else "conv_wgrad_kernel<%s, %d, %d>" % (dts, kid >> 16, (kid >> 4) & 0xfff))
-        if KERNEL_EVENTS.detail:
-            es = 2 if is16(dt) else 4
-            name = "wgrad %dx%d %d->%d @%dx%d s%d chunks=%d|%d" % (R, S, Cin, Cout, dy.H, dy.W, stride, chunks,
-                                                                 (x.B * H * W * Cin + x.B * dy.H * dy.W * dy.Cs) * es)
-        KERNEL_EVENTS.end(name, 2.0 * x.B * dy.H * dy.W * Cout * R * S * Cin, e0)
-        if chunks > 1:          # the reduction mpn_conv_wgrad runs (same kernels and order: the same bits as without events)
-            call("mpn_conv_wgrad_reduce", ctypes.byref(p), stream_ptr())
-    else:
-        call("mpn_conv_wgrad", ctypes.byref(p), stream_ptr())
+    fused_db = db is not None and bool(call("mpn_conv_wgrad_kernel_id", ctypes.byref(p)) & 1)
+    _launch_wgrad(p, dev, db if fused_db else None, lambda: 2.0 * x.B * dy.H * dy.W * Cout * R * S * Cin,
+                  lambda chunks: "wgrad %dx%d %d->%d @%dx%d s%d chunks=%d|%d" % (R, S, Cin, Cout, dy.H, dy.W, stride, chunks,
+                                                                               (x.B * H * W * Cin + x.B * dy.H * dy.W * dy.Cs) * (2 if is16(dt) else 4)))
     return fused_db
 
 
@@ -734,9 +691,6 @@ def cast_lowp(src, dst):
     call("mpn_cast_f32", ptr(src), ptr(dst), src.numel(), dtype_code(dst.dtype), stream_ptr())
 
 
-cast_bf16 = cast_lowp
-
-
 _fin_counters = {}
 # In-launch BatchNorm finalize (mpn.h: fin_*).  Up to FIN_MAX_TILES pixel tiles one workgroup per channel tile does the whole
 # reduction; beyond that a single reader behind an acquire is slower than the separate (wide) finalize launch (round 2: +0.85 ms at
@@ -749,10 +703,6 @@ def fin_in_launch(tiles, Cout=2):
     """The in-launch finalize reads the partial table as float4 pairs of channels: even widths only (every BatchNorm of the network is;
     an odd width takes the separate finalize launch instead of failing with BADARG — ADVICE r5)."""
     return tiles <= FIN_MAX_TILES and Cout % 2 == 0
-
-
-def fin_attach(p, tiles, Cout, device):
-    p.fin_counters = fin_counters(device).data_ptr()
 
 
 def fin_counters(device):

@@ -118,6 +118,15 @@ def test_entry_points_reject_bad_arguments_without_touching_the_gpu():
     w = WgradParams()
     assert L.mpn_conv_wgrad(ctypes.byref(w), nul) == BAD
     assert L.mpn_conv_wgrad_reduce(ctypes.byref(w), nul) == BAD          # no dw / ws, chunks 0
+    # the host-only name queries: a length on success, BADARG for a null argument or a buffer that cannot hold the name and its NUL
+    buf = ctypes.create_string_buffer(128)
+    for fn, blk in ((L.mpn_conv_kernel_name, p), (L.mpn_conv_wgrad_kernel_name, w)):
+        assert fn(None, buf, 128) == BAD and fn(ctypes.byref(blk), None, 128) == BAD and fn(ctypes.byref(blk), buf, 0) == BAD
+        n = fn(ctypes.byref(blk), buf, 128)
+        assert n == len(buf.value) > 0 and buf.value.endswith(b">")
+        assert fn(ctypes.byref(blk), buf, n) == BAD and fn(ctypes.byref(blk), buf, n + 1) == n
+    p.dtype = 7
+    assert L.mpn_conv_kernel_name(ctypes.byref(p), buf, 128) == BAD      # unknown dtype
     assert L.mpn_reduce_partials(nul, 4, 16, one, 1, nul) == BAD
     assert L.mpn_reduce_partials(one, 0, 16, one, 1, nul) == BAD
     assert L.mpn_weight_transpose(nul, one, 8, 1, 8, 8, 1, nul) == BAD

@@ -3,7 +3,7 @@
 conv_igemm.hip picks its instantiation from the launch size: pick_tc() the output-channel tile height, conv_uses_s3() the
 shared-pixel-tile 3x3 kernel, launch_conv() the plain / general / extended epilogue.  A test reaches a route only through the
 shape it launches, so every case of CASES names the route it must take, asserts it first (from the library's own
-mpn_conv_tile_rows / mpn_conv_shared_tile through ops.KERNEL_EVENTS, plus `ext` by conv_needs_ext()'s rule) and then compares
+mpn_conv_kernel_name through ops.KERNEL_EVENTS, plus `ext` by conv_needs_ext()'s rule) and then compares
 every element — outputs, pad lanes, per-tile statistics, BatchNorm-backward partials, the in-launch finalize — with a float64
 reference of the same operand values under helpers.check_elementwise's bound (half an output spacing plus the linear
 worst-case bound of the fp32 blocked summation).  Shapes carry the ragged edges: P not a multiple of 128, images that end
