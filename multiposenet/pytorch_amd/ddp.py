@@ -56,7 +56,6 @@ class GradReducer(object):
         # gloo (debug / single-GPU tests) reduces host memory: device buckets are staged through pinned buffers
         self.stage_host = backend == "gloo" and arena.device.type == "cuda"
         self.launch_stream = None      # set by the engine when weight gradients are produced on a side stream
-        self.pre_launch = None         # engine hook: hand over side-stream work still waiting for a fork point
         self._trainable_sig = tuple(p.requires_grad for p in arena.params)
         self.bucket_mb = float(bucket_mb)
         self.measure = False           # bench.py: bracket finish()'s waits with a pair of timing events (exposed_ms)
@@ -130,8 +129,6 @@ class GradReducer(object):
         bk = self.buckets[b]
         bk["pending"] -= 1
         if bk["pending"] == 0:
-            if self.pre_launch is not None:
-                self.pre_launch()              # side-stream work still waiting for a fork point (recorded on its own)
             gpu_op(self._launch, bk)           # (recordable: replay.py re-issues the collective at this point of the step)
 
     def _launch(self, bk):

@@ -34,7 +34,6 @@ class Ctx(object):
         self.uses = {}           # id(param) -> number of pending gradient contributions
         self.bn_train_ran = False
         self.side_keep = []      # operands of side-stream launches, kept alive until the streams join
-        self.side_pending = []   # closures waiting for the next fork point (Engine.fork_every > 1)
         self.wt_ready = None     # event: the transposed weight copies (made on the side stream) are complete
         self.bnb = {}            # id(BN output Act) -> per-tile backward statistics produced by the launch that completed its gradient
         self.fwd_side_join = False   # forward work is in flight on the side stream (Engine.det_pyramid): join before it is consumed
@@ -88,9 +87,6 @@ class Engine(object):
         self._side = None
         self._wt_plan_cache = None
         self.overlap_wgrad = os.environ.get("MPN_SIDE_STREAM", "1") != "0"
-        # side-stream work is handed over in groups of `fork_every` layers (one event record / wait per group): a captured
-        # hipGraph pays for every cross-stream edge, the eager tape does not care much
-        self.fork_every = max(1, int(os.environ.get("MPN_SIDE_FORK_EVERY", "1")))
         # the RetinaNet towers share their weights over p3..p7: one launch per layer over the whole pyramid instead of one per level
         self.pyramid_towers = os.environ.get("MPN_PYRAMID_TOWERS", "1") != "0"
         # BatchNorm-backward statistics ride in the epilogue of the dgrad launch that completes dz (no separate reduction pass)
@@ -125,49 +121,49 @@ class Engine(object):
             self._side = torch.cuda.Stream(device=device)
         return self._side
 
-    def _on_side(self, ctx, device, keep, fn, torch_ops=False):
-        """Run fn() on the side stream, ordered after everything enqueued so far on the current stream.  Our own
-        launches take the stream explicitly (ops.push_stream); only closures that also run torch ops (torch_ops=True)
-        pay for switching torch's current stream."""
+    def _on_side(self, ctx, device, keep, fn, torch_ops=False, done_event=False):
+        """THE fork: run fn() on the side stream, ordered after everything enqueued so far on the current stream (inline when
+        there is no side stream).  Our own launches take the stream explicitly (ops.push_stream); only closures that also run
+        torch ops (torch_ops=True) pay for switching torch's current stream.  ``keep`` stays alive until the streams join.
+        ``done_event``: return an event recorded on the side stream behind fn (None without a side stream)."""
         side = self.side_stream(device)
         if side is None:
             fn()
-            return
+            return None
         ctx.side_keep.append(keep)
-        ctx.side_pending.append((fn, torch_ops))
-        if len(ctx.side_pending) >= self.fork_every:
-            self.flush_side(ctx, device)
-
-    def flush_side(self, ctx, device):
-        """Fork point: everything enqueued so far on the current stream happens-before the pending side-stream closures."""
-        if not ctx.side_pending:
-            return
-        side = self.side_stream(device)
-        pending, ctx.side_pending = ctx.side_pending, []
         ev = torch.cuda.Event()
         gpu_op(ev.record, torch.cuda.current_stream(device))
         gpu_op(side.wait_event, ev)
-        for fn, torch_ops in pending:
-            if torch_ops:
-                with torch.cuda.stream(side):
-                    fn()
-                continue
+        if torch_ops:
+            with torch.cuda.stream(side):
+                fn()
+        else:
             ops.push_stream(side)
             try:
                 fn()
             finally:
                 ops.pop_stream()
+        if not done_event:
+            return None
+        done = torch.cuda.Event()
+        gpu_op(done.record, side)
+        return done
 
     # ------------------------------------------------------------------ weights
     @property
     def cdt(self):
         return self.m.compute_dtype
 
+    @property
+    def kc(self):
+        """Elements of one 64-byte K chunk in the compute dtype."""
+        return 32 if ops.is16(self.cdt) else 16
+
     def w_fwd(self, layer):
         """Forward operand [Cout][R][S][Cin] in the compute dtype (a view, never a copy in f32)."""
         ar = self.m._arena
         w = layer.weight
-        kc = 32 if ops.is16(self.cdt) else 16
+        kc = self.kc
         if w.dim() == 2 and w.shape[1] % kc != 0:
             # Linear layer whose fan-in is not a whole number of 64-byte K chunks (PRN with prn_coeff 1 or 3): zero-padded rows
             K, Kp = w.shape[1], round_up(w.shape[1], kc)
@@ -185,7 +181,7 @@ class Engine(object):
         plan = self._wt_plan_cache
         if plan is not None and plan["arena"] is ar and plan["dtype"] == self.cdt:
             return plan
-        kc = 32 if ops.is16(self.cdt) else 16
+        kc = self.kc
         rows, views, off, blk = [], {}, 0, 0
         stem = self.m.fpn.conv1.weight
         prn_w = {id(q) for q in self.m.prn.parameters()}      # the PRN's Linear layers (71 M parameters) are not part of the
@@ -217,8 +213,7 @@ class Engine(object):
         plan = self._wt_plan()
         if key not in plan["views"]:          # not an arena conv/linear weight: single transpose
             O, I, R, S, _, _ = _geom(layer)
-            kc = 32 if ops.is16(self.cdt) else 16
-            opad = round_up(O, kc)
+            opad = round_up(O, self.kc)
             wt = torch.empty((I, R, S, opad), dtype=self.cdt, device=layer.weight.device)
             ops.weight_transpose(self.m._arena.data_seg(layer.weight), wt, O, R * S, I, opad)
             ctx.wt[key] = wt
@@ -226,28 +221,15 @@ class Engine(object):
         if ctx.wt_buf is None:
             dev = plan["table"].device
             ctx.wt_buf = torch.empty(plan["total"], dtype=self.cdt, device=dev)
-            side = self.side_stream(dev)
-            if side is not None:
-                ctx.wt_buf.record_stream(side)
+            if self.side_stream(dev) is not None:
+                ctx.wt_buf.record_stream(self.side_stream(dev))
 
             def transpose_all():
                 call("mpn_weight_transpose_batched", ops.ptr(self.m._arena.flat), ops.ptr(ctx.wt_buf), ops.ptr(plan["table"]),
                      plan["n"], plan["blocks"], ops.dtype_code(self.cdt), ops.stream_ptr())
-            if side is None:
-                transpose_all()
-            else:
-                # only backward reads these copies: make them beside the forward pass (they depend on nothing but the last
-                # optimizer step, which the fork below orders) and let run_backward wait for the event
-                ev = torch.cuda.Event()
-                gpu_op(ev.record, torch.cuda.current_stream(dev))
-                gpu_op(side.wait_event, ev)
-                ops.push_stream(side)
-                try:
-                    transpose_all()
-                finally:
-                    ops.pop_stream()
-                ctx.wt_ready = torch.cuda.Event()
-                gpu_op(ctx.wt_ready.record, side)
+            # only backward reads these copies: make them beside the forward pass (they depend on nothing but the last
+            # optimizer step, which the fork orders) and let run_backward wait for the event
+            ctx.wt_ready = self._on_side(ctx, dev, ctx.wt_buf, transpose_all, done_event=True)
         off, shape = plan["views"][key]
         n = shape[0] * shape[1] * shape[2] * shape[3]
         wt = ctx.wt_buf[off: off + n].view(shape)
@@ -264,6 +246,52 @@ class Engine(object):
         if n == 0 and ctx.schedule is not None:
             ctx.schedule.param_ready(p)
 
+    def _taped(self, ctx, layer, xs, ys, bwd, res=None, wt=True):
+        """Forward half of a convolution layer's tape entry: do the outputs ``ys`` need a gradient?  If so count the layer's
+        parameters as pending, make the dgrad operand now when an input needs a gradient (the weights may change before
+        backward; ``wt=False``: the caller has its own transposed operands) and put ``bwd`` on the tape."""
+        bias = layer.bias
+        need_x = False
+        for x in xs:          # (a plain loop: this runs for every layer of an eager step)
+            need_x = need_x or x.needs_grad
+        need = bool(need_x or layer.weight.requires_grad or (bias is not None and bias.requires_grad)
+                    or (res is not None and res.needs_grad))
+        for y in ys:
+            y.needs_grad = need
+        if need:
+            self._note_use(ctx, layer.weight)
+            self._note_use(ctx, bias)
+            if need_x and wt:
+                self.w_t(ctx, layer)
+            ctx.tape.append(bwd)
+        return need
+
+    def _param_grads(self, ctx, layer, dys, keep=None, wgrad=None, first=None):
+        """Backward half: the parameter gradients of a convolution layer whose output gradients ``dys`` (one per level; None =
+        nothing flowed back) have arrived — on the side stream (``keep``: what its launches read), then the layer's parameters
+        are reported complete, weight before bias.  ``wgrad(dw, db, i)`` is the caller's weight-gradient launch for level i,
+        accumulating into the arena slices; it returns True when it summed the bias gradient into db as well.  ``first()``
+        runs in the same side-stream closure ahead of the gradients, also when no parameter is trainable."""
+        w, bias = layer.weight, layer.bias
+        wg = w.requires_grad
+        bg = bias is not None and bias.requires_grad
+        if dys is not None and (wg or bg or first is not None):
+            ar = self.m._arena
+
+            def side():
+                if first is not None:
+                    first()
+                dw = ar.grad_seg(w) if wg else None
+                db = ar.grad_seg(bias) if bg else None
+                for i, dy in enumerate(dys):      # the bias gradient rides along in the wgrad kernel where the LDS-DMA path serves it
+                    if not (wg and wgrad(dw, db, i)) and bg:
+                        ops.bias_grad(dy, db, w.shape[0])
+            self._on_side(ctx, dys[0].t.device, keep, side)
+        if wg:
+            self._grad_done(ctx, w)
+        if bg:
+            self._grad_done(ctx, bias)
+
     # ------------------------------------------------------------------ ops
     def _bn_fin(self, bn):
         """Arguments of the in-launch forward finalize for BatchNorm layer `bn` (train mode)."""
@@ -278,31 +306,20 @@ class Engine(object):
                                  act=act, res=res, res_mode=res_mode, want_stats=stats, out_f32=out_f32, tag=tag,
                                  bn_fin=self._bn_fin(bn) if stats else None)
         y.relu_out = act == 1
-        if ctx.train:
-            y.needs_grad = bool(x.needs_grad or layer.weight.requires_grad or (bias is not None and bias.requires_grad)
-                                or (res is not None and res.needs_grad))
-            if y.needs_grad:
-                self._note_use(ctx, layer.weight)
-                self._note_use(ctx, bias)
-                if x.needs_grad:
-                    self.w_t(ctx, layer)       # make the transposed operand now (weights may change before backward)
-                    x.cons += 1
-                    x.conv_cons += 1
-                if res is not None and res.needs_grad:
-                    res.cons += 1
-                    res.other_cons += 1
-                ctx.tape.append(lambda: self._conv_bwd(ctx, x, layer, y, act, res, res_mode))
+        if ctx.train and self._taped(ctx, layer, (x,), (y,), lambda: self._conv_bwd(ctx, x, layer, y, act, res, res_mode), res=res):
+            if x.needs_grad:
+                x.cons += 1
+                x.conv_cons += 1
+            if res is not None and res.needs_grad:
+                res.cons += 1
+                res.other_cons += 1
         return y, st
 
     def _conv_bwd(self, ctx, x, layer, y, act, res, res_mode):
         dy = ctx.pop_grad(y)
         O, I, R, S, stride, pad = _geom(layer)
-        bias = layer.bias
         if dy is None:       # nothing flowed back through this output (e.g. unused head)
-            if layer.weight.requires_grad:
-                self._grad_done(ctx, layer.weight)
-            if bias is not None and bias.requires_grad:
-                self._grad_done(ctx, bias)
+            self._param_grads(ctx, layer, None)
             if x.needs_grad:
                 x.cons -= 1
                 x.conv_cons -= 1
@@ -315,11 +332,11 @@ class Engine(object):
                 res.cons -= 1
             return
         if dy.t.dtype != self.cdt:
-            raise ops._lib.MpnError("gradient dtype mismatch for %s" % y.tag)
+            raise MpnError("gradient dtype mismatch for %s" % y.tag)
         if act == 1:
             dy = ops.relu_backward(dy, y)
         elif act == 2:
-            raise ops._lib.MpnError("sigmoid backward is handled at the detection edge")
+            raise MpnError("sigmoid backward is handled at the detection edge")
         if res is not None and res.needs_grad:
             res.cons -= 1
             g, existed = ctx.gbuf(res)
@@ -329,22 +346,7 @@ class Engine(object):
                 ops.add_inplace(g, dy)
             else:
                 ops.copy_act(g, dy)
-        ar = self.m._arena
-        wg = layer.weight.requires_grad
-        bg = bias is not None and bias.requires_grad
-        if wg or bg:
-            def param_grads():
-                done = False
-                if wg:           # the bias gradient rides along in the wgrad kernel where the LDS-DMA path serves it
-                    done = ops.conv_wgrad(x, dy, ar.grad_seg(layer.weight), O, R, S, stride, pad,
-                                          db=ar.grad_seg(bias) if bg else None)
-                if bg and not done:
-                    ops.bias_grad(dy, ar.grad_seg(bias), O)
-            self._on_side(ctx, dy.t.device, (x, dy), param_grads)
-            if wg:
-                self._grad_done(ctx, layer.weight)
-            if bg:
-                self._grad_done(ctx, bias)
+        self._param_grads(ctx, layer, (dy,), (x, dy), lambda dw, db, i: ops.conv_wgrad(x, dy, dw, O, R, S, stride, pad, db=db))
         if x.needs_grad:
             x.cons -= 1
             x.conv_cons -= 1
@@ -382,31 +384,17 @@ class Engine(object):
         for y in ys:
             y.relu_out = act == 1
         if ctx.train:
-            need = bool(any(x.needs_grad for x in xs) or layer.weight.requires_grad or (bias is not None and bias.requires_grad))
-            for y in ys:
-                y.needs_grad = need
-            if need:
-                self._note_use(ctx, layer.weight)
-                self._note_use(ctx, bias)
-                if any(x.needs_grad for x in xs):
-                    self.w_t(ctx, layer)
-                ctx.tape.append(lambda: self._conv_seg_bwd(ctx, xs, layer, ys, act))
+            self._taped(ctx, layer, xs, ys, lambda: self._conv_seg_bwd(ctx, xs, layer, ys, act))
         return ys
 
     def _conv_seg_bwd(self, ctx, xs, layer, ys, act):
         dys = [ctx.pop_grad(y) for y in ys]
         O, I, R, S, stride, pad = _geom(layer)
-        bias = layer.bias
-        wg = layer.weight.requires_grad
-        bg = bias is not None and bias.requires_grad
         if all(d is None for d in dys):
-            if wg:
-                self._grad_done(ctx, layer.weight)
-            if bg:
-                self._grad_done(ctx, bias)
+            self._param_grads(ctx, layer, None)
             return
         if any(d is None for d in dys):
-            raise ops._lib.MpnError("pyramid convolution: gradient missing for some levels")
+            raise MpnError("pyramid convolution: gradient missing for some levels")
         if act == 1:          # ReLU mask over the whole pyramid in one launch when both sides are single buffers
             fd, fy = ops.seg_flat(dys), ops.seg_flat(ys)
             if fd is not None and fy is not None and fd.numel() == fy.numel():
@@ -415,23 +403,13 @@ class Engine(object):
                 dys = out
             else:
                 dys = [ops.relu_backward(d, y) for d, y in zip(dys, ys)]
-        ar = self.m._arena
-        if wg or bg:
-            def param_grads():
-                handled, fused = (False, False)
-                if wg:
-                    handled, fused = ops.conv_wgrad_seg(xs, dys, ar.grad_seg(layer.weight), O, R, S, pad, db=ar.grad_seg(bias) if bg else None)
-                for x, d in zip(xs, dys):          # per-level path (exact-fp32 kernels) / separate bias gradient
-                    done = fused
-                    if wg and not handled:
-                        done = ops.conv_wgrad(x, d, ar.grad_seg(layer.weight), O, R, S, 1, pad, db=ar.grad_seg(bias) if bg else None)
-                    if bg and not done:
-                        ops.bias_grad(d, ar.grad_seg(bias), O)
-            self._on_side(ctx, dys[0].t.device, (xs, dys), param_grads)
-            if wg:
-                self._grad_done(ctx, layer.weight)
-            if bg:
-                self._grad_done(ctx, bias)
+        pyr = []
+
+        def wgrad(dw, db, i):
+            if i == 0:           # one launch over the whole pyramid -> (handled, bias gradient fused), else per level (exact-fp32 kernels)
+                pyr[:] = ops.conv_wgrad_seg(xs, dys, dw, O, R, S, pad, db=db)
+            return pyr[1] if pyr[0] else ops.conv_wgrad(xs[i], dys[i], dw, O, R, S, 1, pad, db=db)
+        self._param_grads(ctx, layer, dys, (xs, dys), wgrad)
         if any(x.needs_grad for x in xs):
             wt = self.w_t(ctx, layer)
             grouped = ops.seg_flat(xs) is not None
@@ -490,10 +468,7 @@ class Engine(object):
         dz = ctx.pop_grad(z)
         wg, bg = layer.weight.requires_grad, layer.bias.requires_grad
         if dz is None:
-            if wg:
-                self._grad_done(ctx, layer.weight)
-            if bg:
-                self._grad_done(ctx, layer.bias)
+            self._param_grads(ctx, layer, None)
             if res is not None and res.needs_grad:
                 res.cons -= 1
             return
@@ -515,10 +490,7 @@ class Engine(object):
                              dbeta=ar.grad_seg(layer.bias) if bg else None,
                              want_dy=want_dy, dres=dres, dres_acc=dres_acc, remask=bool(relu and res is None),
                              **self._bnb_args(ctx.bnb.pop(id(z), None)))
-        if wg:
-            self._grad_done(ctx, layer.weight)
-        if bg:
-            self._grad_done(ctx, layer.bias)
+        self._param_grads(ctx, layer, None)          # (dgamma / dbeta were written by the launch above: only the completion report)
         if want_dy:
             ctx.set_grad(y, dy)
 
@@ -610,43 +582,18 @@ class Engine(object):
         y = ops.conv_forward_cat(srcs, H, W, self.w_fwd(layer), O, bias=bias.data if bias is not None else None, act=act)
         y.relu_out = act == 1
         if ctx.train:
-            need_x = any(s.needs_grad for s in srcs)
-            y.needs_grad = bool(need_x or layer.weight.requires_grad or (bias is not None and bias.requires_grad))
-            if y.needs_grad:
-                self._note_use(ctx, layer.weight)
-                self._note_use(ctx, bias)
-                if need_x:
-                    self.w_t(ctx, layer)
-                ctx.tape.append(lambda: self._conv_cat_bwd(ctx, srcs, H, W, layer, y, act))
+            self._taped(ctx, layer, srcs, (y,), lambda: self._conv_cat_bwd(ctx, srcs, H, W, layer, y, act))
         return y
 
     def _conv_cat_bwd(self, ctx, srcs, H, W, layer, y, act):
         dy = ctx.pop_grad(y)
         O, I, R, S, stride, pad = _geom(layer)
-        bias = layer.bias
-        wg = layer.weight.requires_grad
-        bg = bias is not None and bias.requires_grad
         if dy is None:
-            if wg:
-                self._grad_done(ctx, layer.weight)
-            if bg:
-                self._grad_done(ctx, bias)
+            self._param_grads(ctx, layer, None)
             return
         if act == 1:
             dy = ops.relu_backward(dy, y)
-        ar = self.m._arena
-        if wg or bg:
-            def param_grads():
-                done = False
-                if wg:
-                    done = ops.conv_wgrad_cat(srcs, H, W, dy, ar.grad_seg(layer.weight), O, db=ar.grad_seg(bias) if bg else None)
-                if bg and not done:
-                    ops.bias_grad(dy, ar.grad_seg(bias), O)
-            self._on_side(ctx, dy.t.device, (srcs, dy), param_grads)
-            if wg:
-                self._grad_done(ctx, layer.weight)
-            if bg:
-                self._grad_done(ctx, bias)
+        self._param_grads(ctx, layer, (dy,), (srcs, dy), lambda dw, db, i: ops.conv_wgrad_cat(srcs, H, W, dy, dw, O, db=db))
         if any(s.needs_grad for s in srcs):
             wt = self.w_t(ctx, layer)
             # one buffer of all members' channels, then each member's slice summed down to its own resolution (writing the full-resolution
@@ -674,7 +621,7 @@ class Engine(object):
         C = I // 4
         dev = q5.t.device
         ar = self.m._arena
-        st = {"need_x": bool(ctx.train and (q5.needs_grad or q4.needs_grad))}
+        st = {}
 
         def classes():
             # (the transposed operands are made whenever a tape is being recorded: whether q3 / q2 need gradients is not known yet)
@@ -694,16 +641,7 @@ class Engine(object):
             st["e"] = ops.conv2cls_expand(m8, m4, q5.B, H, W, O, self.cdt)
         # The weight-gradient side stream carries it (behind the detection pyramid, forked earlier): a stream of its own measured
         # 0.2 ms SLOWER (profiles/r06_conv2_classes_ab.txt) — a third stream only adds contention.
-        side = self.side_stream(dev)
-        if side is not None:
-            self._on_side(ctx, dev, (q5, q4, st), classes)
-            self.flush_side(ctx, dev)
-        else:
-            classes()
-        if side is not None:
-            st["ev"] = torch.cuda.Event()
-            gpu_op(st["ev"].record, side)
-            ctx.side_keep.append(st)
+        st["ev"] = self._on_side(ctx, dev, (q5, q4, st), classes, done_event=True)
         return st
 
     def conv_cat_cls(self, ctx, srcs, H, W, layer, act, st):
@@ -714,8 +652,7 @@ class Engine(object):
         O, I, R, S, stride, pad = _geom(layer)
         bias = layer.bias
         dev = q2.t.device
-        need_x = ctx.train and any(s_.needs_grad for s_ in srcs)
-        if "ev" in st:
+        if st["ev"] is not None:
             gpu_op(torch.cuda.current_stream(dev).wait_event, st["ev"])
         wo = st["ops"]
         cat2 = None
@@ -729,12 +666,8 @@ class Engine(object):
             y, _ = ops.conv_forward(cat2, wo.wm, O, 3, 3, 1, 1, bias=bias.data if bias is not None else None, act=3 if act == 1 else act,
                                     res=st["e"], res_mode=1)
         y.relu_out = act == 1
-        if ctx.train:
-            y.needs_grad = bool(need_x or layer.weight.requires_grad or (bias is not None and bias.requires_grad))
-            if y.needs_grad:
-                self._note_use(ctx, layer.weight)
-                self._note_use(ctx, bias)
-                ctx.tape.append(lambda: self._conv_cat_cls_bwd(ctx, srcs, H, W, layer, y, act, wo, cat2))
+        if ctx.train:        # (wt=False: the transposed operands are wo's)
+            self._taped(ctx, layer, srcs, (y,), lambda: self._conv_cat_cls_bwd(ctx, srcs, H, W, layer, y, act, wo, cat2), wt=False)
         ctx.side_keep.append((st, y))
         return y
 
@@ -743,76 +676,64 @@ class Engine(object):
         dy = ctx.pop_grad(y)
         O, I, R, S, stride, pad = _geom(layer)
         C = I // 4
-        bias = layer.bias
-        wg = layer.weight.requires_grad
-        bg = bias is not None and bias.requires_grad
         if dy is None:
-            if wg:
-                self._grad_done(ctx, layer.weight)
-            if bg:
-                self._grad_done(ctx, bias)
+            self._param_grads(ctx, layer, None)
             return
         if act == 1:
             dy = ops.relu_backward(dy, y)
-        ar = self.m._arena
         dev = dy.t.device
-        need_x = any(s_.needs_grad for s_ in srcs)
-        g5 = g4 = None
-        if need_x:
-            g5 = Act(torch.empty_like(q5.t), q5.C)
-            g4 = Act(torch.empty_like(q4.t), q4.C)
+        g5 = Act(torch.empty_like(q5.t), q5.C) if q5.needs_grad else None
+        g4 = Act(torch.empty_like(q4.t), q4.C) if q4.needs_grad else None
+        tap = []          # (g8, g4t): the per-tap sums of the pooled dy, made by class_grads and read again by wgrad
 
-        def class_side():
-            # everything of the x8 / x4 members: class pooling of dy and the per-tap sums, their input gradients (1x1 over nine taps;
-            # consumed by the main stream a dozen launches later: ctx.cls_ev), the per-tap filter gradients, the main part's weight
-            # gradient and the fold into dW
+        def class_grads():
+            # the x8 / x4 members: class pooling of dy and the per-tap sums, then their input gradients (1x1 over nine taps; consumed
+            # by the main stream a dozen launches later — ctx.cls_ev is recorded HERE, the main stream must not wait for the
+            # weight gradients that follow in the same closure)
             p8, p4 = ops.conv2cls_pool(dy)
-            g8, g4t = ops.conv2cls_tapsum(p8), ops.conv2cls_tapsum(p4)
-            if need_x:
+            tap[:] = g8, g4t = ops.conv2cls_tapsum(p8), ops.conv2cls_tapsum(p4)
+            if g5 is not None:
                 ops.conv_forward(g8, wo.wtap_t[0], C, 1, 1, 1, 0, mode=1, out_hw=(q5.H, q5.W), cin=9 * O, out=g5)
+            if g4 is not None:
                 ops.conv_forward(g4t, wo.wtap_t[1], C, 1, 1, 1, 0, mode=1, out_hw=(q4.H, q4.W), cin=9 * O, out=g4)
-                ev = torch.cuda.Event()
-                gpu_op(ev.record, ops.stream_obj() if ops.stream_obj() is not None else torch.cuda.current_stream(dev))
-                ctx.cls_ev = ev
-            if wg or bg:
-                n = wo.nm + 2 * wo.nt
-                dcomb = torch.empty(n, dtype=torch.float32, device=dev)
-                call("mpn_fill_f32", ops.ptr(dcomb), 0.0, n, ops.stream_ptr())
-                done = False
-                if wg:
-                    if cat2 is None:
-                        done = ops.conv_wgrad_cat([q3, q2], H, W, dy, dcomb[: wo.nm], O, db=ar.grad_seg(bias) if bg else None)
-                    else:
-                        done = ops.conv_wgrad(cat2, dy, dcomb[: wo.nm], O, 3, 3, 1, 1, db=ar.grad_seg(bias) if bg else None)
-                    ops.conv_wgrad(q5, g8, dcomb[wo.nm: wo.nm + wo.nt], 9 * O, 1, 1, 1, 0)
-                    ops.conv_wgrad(q4, g4t, dcomb[wo.nm + wo.nt:], 9 * O, 1, 1, 1, 0)
-                    call("mpn_conv2cls_fold", ops.ptr(dcomb), ops.ptr(ar.grad_seg(layer.weight)), O, C, ops.stream_ptr())
-                if bg and not done:
-                    ops.bias_grad(dy, ar.grad_seg(bias), O)
-                ctx.side_keep.append((dcomb,))
+            if g5 is not None or g4 is not None:
+                ctx.cls_ev = torch.cuda.Event()
+                gpu_op(ctx.cls_ev.record, ops.launch_stream(dev))
             ctx.side_keep.append((p8, p4, g8, g4t))
-        self._on_side(ctx, dev, (srcs, dy, g5, g4, wo, cat2), class_side)
-        if self.side_stream(dev) is not None:
-            self.flush_side(ctx, dev)
-        if wg:
-            self._grad_done(ctx, layer.weight)
-        if bg:
-            self._grad_done(ctx, bias)
-        if need_x:
+
+        def wgrad(dw, db, i):
+            # the main part's weight gradient and the per-tap filter gradients into one f32 buffer, folded into dW
+            g8, g4t = tap
+            n = wo.nm + 2 * wo.nt
+            dcomb = torch.empty(n, dtype=torch.float32, device=dev)
+            call("mpn_fill_f32", ops.ptr(dcomb), 0.0, n, ops.stream_ptr())
+            if cat2 is None:
+                fused = ops.conv_wgrad_cat([q3, q2], H, W, dy, dcomb[: wo.nm], O, db=db)
+            else:
+                fused = ops.conv_wgrad(cat2, dy, dcomb[: wo.nm], O, 3, 3, 1, 1, db=db)
+            ops.conv_wgrad(q5, g8, dcomb[wo.nm: wo.nm + wo.nt], 9 * O, 1, 1, 1, 0)
+            ops.conv_wgrad(q4, g4t, dcomb[wo.nm + wo.nt:], 9 * O, 1, 1, 1, 0)
+            call("mpn_conv2cls_fold", ops.ptr(dcomb), ops.ptr(dw), O, C, ops.stream_ptr())
+            ctx.side_keep.append((dcomb,))
+            return fused
+        self._param_grads(ctx, layer, (dy,), (srcs, dy, g5, g4, wo, cat2), wgrad, first=class_grads)
+        if g5 is not None:
             ctx.set_grad(q5, g5)
+        if g4 is not None:
             ctx.set_grad(q4, g4)
+        if q3.needs_grad or q2.needs_grad:
             d_all = Act(torch.empty((dy.B, H, W, 2 * C), dtype=dy.t.dtype, device=dev), 2 * C)
             ops.conv_forward(dy, wo.wm_t, 2 * C, 3, 3, 1, 1, mode=1, out_hw=(H, W), cin=O, out=d_all)
             for s_, off in ((q3, 0), (q2, C)):
-                g = Act(torch.empty_like(s_.t), s_.C)
-                ops.upsample_slice_backward(d_all, g, off)
-                ctx.set_grad(s_, g)
+                if s_.needs_grad:
+                    g = Act(torch.empty_like(s_.t), s_.C)
+                    ops.upsample_slice_backward(d_all, g, off)
+                    ctx.set_grad(s_, g)
 
     def wait_class_grads(self, ctx, device):
         """Tape marker in front of the consumers of the class input gradients (keypoint_head): they were produced on the side stream."""
-        ev = getattr(ctx, "cls_ev", None)
-        if ev is not None:
-            gpu_op(torch.cuda.current_stream(device).wait_event, ev)
+        if ctx.cls_ev is not None:
+            gpu_op(torch.cuda.current_stream(device).wait_event, ctx.cls_ev)
             ctx.cls_ev = None
 
     def export(self, ctx, src, C, Ho, Wo, slot):
@@ -869,15 +790,15 @@ class Engine(object):
 
             def bwd():
                 dy = ctx.pop_grad(y)
-                if dy is not None:
-                    dwp = torch.empty((64, 7, 32), dtype=torch.float32, device=img.device)
+                if dy is None:
+                    return self._param_grads(ctx, f.conv1, None)
+                dwp = torch.empty((64, 7, 32), dtype=torch.float32, device=img.device)
 
-                    def stem_wgrad():
-                        call("mpn_fill_f32", ops.ptr(dwp), 0.0, dwp.numel(), ops.stream_ptr())
-                        ops.conv_wgrad(xa, dy, dwp, 64, 7, 1, 2, 0, cin=32, x_geom=geom)
-                        call("mpn_stem_unpack_wgrad", ops.ptr(dwp), ops.ptr(self.m._arena.grad_seg(w)), 64, ops.stream_ptr())
-                    self._on_side(ctx, dy.t.device, (xa, dy, dwp), stem_wgrad)
-                self._grad_done(ctx, w)
+                def wgrad(dw, db, i):          # in the packed layout, then unpacked onto the arena slice
+                    call("mpn_fill_f32", ops.ptr(dwp), 0.0, dwp.numel(), ops.stream_ptr())
+                    ops.conv_wgrad(xa, dy, dwp, 64, 7, 1, 2, 0, cin=32, x_geom=geom)
+                    call("mpn_stem_unpack_wgrad", ops.ptr(dwp), ops.ptr(dw), 64, ops.stream_ptr())
+                self._param_grads(ctx, f.conv1, (dy,), (xa, dy, dwp), wgrad)
             ctx.tape.append(bwd)
         z = self.bn(ctx, y, st, f.bn1, True)
         return self.maxpool(ctx, z)
@@ -943,7 +864,6 @@ class Engine(object):
                 if mode == 2:
                     rest(h)
             self._on_side(ctx, dev, (c3, c4, c5, h), branch)
-            self.flush_side(ctx, dev)
             ctx.fwd_side_join = True
             if mode != 2:
                 rest(h)
@@ -1014,31 +934,29 @@ class Engine(object):
         K = num_classes(cm)
         reg_all = torch.empty((B, A, 4), dtype=torch.float32, device=dev)
         cls_all = torch.empty((B, A, K), dtype=torch.float32, device=dev)
+
+        hidden = []          # the towers' last hidden levels stay allocated until the outputs are packed
+
+        def towers(xs, conv):
+            """The regression tower, then the class tower, over the levels ``xs``: four conv + ReLU layers and the output layer each."""
+            heads = []
+            for sub in (rm, cm):
+                h = xs
+                for layer in (sub.conv1, sub.conv2, sub.conv3, sub.conv4):
+                    h = conv(h, layer, act=1)
+                hidden.append(h)
+                heads.append(conv(h, sub.output, out_f32=True))
+            return heads
+        if self.pyramid_towers and len(feats) > 1:          # one launch per layer over the whole pyramid
+            ros, cos = towers(feats, lambda xs, layer, **kw: self.conv_seg(ctx, xs, layer, **kw))
+        else:                                               # level by level, each a one-element pyramid through the plain convolution
+            per_level = [towers([f], lambda xs, layer, **kw: [self.conv(ctx, xs[0], layer, **kw)[0]]) for f in feats]
+            ros, cos = [ro for (ro,), _ in per_level], [co for _, (co,) in per_level]
         outs = []
         off = 0
-        if self.pyramid_towers and len(feats) > 1:
-            r = c = feats
-            for layer in (rm.conv1, rm.conv2, rm.conv3, rm.conv4):
-                r = self.conv_seg(ctx, r, layer, act=1)
-            ros = self.conv_seg(ctx, r, rm.output, out_f32=True)
-            for layer in (cm.conv1, cm.conv2, cm.conv3, cm.conv4):
-                c = self.conv_seg(ctx, c, layer, act=1)
-            cos = self.conv_seg(ctx, c, cm.output, out_f32=True)
-            for ro, co, n in zip(ros, cos, cells):
-                outs.append((ro, co, off, n))
-                off += n * 9
-        else:
-            for f, n in zip(feats, cells):
-                r = f
-                for layer in (rm.conv1, rm.conv2, rm.conv3, rm.conv4):
-                    r, _ = self.conv(ctx, r, layer, act=1)
-                ro, _ = self.conv(ctx, r, rm.output, out_f32=True)
-                c = f
-                for layer in (cm.conv1, cm.conv2, cm.conv3, cm.conv4):
-                    c, _ = self.conv(ctx, c, layer, act=1)
-                co, _ = self.conv(ctx, c, cm.output, out_f32=True)
-                outs.append((ro, co, off, n))
-                off += n * 9
+        for ro, co, n in zip(ros, cos, cells):
+            outs.append((ro, co, off, n))
+            off += n * 9
         # pack the per-level outputs, then one sigmoid over [B,A,K] (its backward needs only p)
         for ro, co, o, n in outs:
             call("mpn_det_pack", ops.ptr(ro.t), 0, ctypes.c_void_p(reg_all.data_ptr() + o * 4 * 4), B, n, ro.Cs, 36, A * 4, ops.stream_ptr())
@@ -1083,7 +1001,6 @@ class Engine(object):
         sched = ctx.schedule = schedule if schedule is not None else m._reducer
         if sched is not None:
             sched.launch_stream = side
-            sched.pre_launch = (lambda: self.flush_side(ctx, dev)) if side is not None else None
             gpu_op(sched.begin, on_bucket)
         if ctx.wt_ready is not None:
             gpu_op(torch.cuda.current_stream(dev).wait_event, ctx.wt_ready)
@@ -1092,7 +1009,6 @@ class Engine(object):
         while tape:
             tape.pop()()
         if side is not None:
-            self.flush_side(ctx, dev)
             gpu_op(torch.cuda.current_stream(dev).wait_stream, side)      # join: parameter gradients are complete
         ctx.grads.clear()
         ctx.lazy_res.clear()
@@ -1101,6 +1017,5 @@ class Engine(object):
         ctx.wt.clear()
         ctx.wt_buf = None
         if sched is not None:
-            sched.pre_launch = None
             gpu_op(sched.finish)
         ctx.schedule = None

@@ -62,6 +62,11 @@ def stream_obj():
     return _STREAM_OVERRIDE[-1][1] if _STREAM_OVERRIDE else None
 
 
+def launch_stream(device):
+    """torch.cuda.Stream our launches go to right now: the pushed override, else torch's current stream."""
+    return _STREAM_OVERRIDE[-1][1] if _STREAM_OVERRIDE else torch.cuda.current_stream(device)
+
+
 def stream_ptr():
     return ctypes.c_void_p(stream_handle())
 
@@ -90,7 +95,7 @@ class Act(object):
         self.tag = tag
         self.seg = None          # (flat buffer, index) when this activation is one level of a pyramid group (alloc_seg)
         self.cons = 0            # gradient contributions still to come in backward (engine: last-contributor detection)
-        self.bn_src = None       # (y, BNState, relu, has_residual) when this is the output of a BatchNorm
+        self.bn_src = None       # output of a BatchNorm: (conv output y, BNState, relu, has_residual, wants_stats, the BN layer, train_stats)
         self.relu_out = False    # forward: this tensor is relu(conv(.)) (conv epilogue act 1)
         self.other_cons = 0      # consumers other than plain / pyramid convolutions (residual adds, relu, pooling)
         self.conv_cons = 0       # how many of the pending contributions are input gradients of plain convolutions (engine.conv)

@@ -171,8 +171,9 @@ def test_rank_that_cannot_rendezvous_exits_3_with_a_diagnosis():
 
 
 # ------------------------------------------------------------------------------------------------ conv2 by position classes
-def _head_run(m, feats, gs_pred, classes, overlap):
-    """keypoint_head forward + backward on fixed pyramid inputs / output gradient; returns (pred, input grads, conv2 dW, conv2 db, every head dparam)."""
+def _head_run(m, feats, gs_pred, classes, overlap, needs=(True, True, True, True)):
+    """keypoint_head forward + backward on fixed pyramid inputs (p2, p3, p4, p5; ``needs``: which of them need a gradient) / output
+    gradient; returns (pred, conv2 dW, conv2 db, every other head dparam)."""
     from multiposenet.pytorch_amd import ops
     from multiposenet.pytorch_amd.engine import Ctx
     eng = m._engine
@@ -181,7 +182,7 @@ def _head_run(m, feats, gs_pred, classes, overlap):
     m._arena.grad_flat.zero_()
     ctx = Ctx(True)
     dt = m.compute_dtype
-    xs = [ops.Act(f.permute(0, 2, 3, 1).contiguous().to(dt).cuda(), f.shape[1], needs_grad=True) for f in feats]
+    xs = [ops.Act(f.permute(0, 2, 3, 1).contiguous().to(dt).cuda(), f.shape[1], needs_grad=n) for f, n in zip(feats, needs)]
     pred, _ = eng.keypoint_head(ctx, xs, False, internal=True)
     g = ops.Act(torch.zeros(pred.t.shape, dtype=dt, device=pred.t.device), pred.C)          # the loss kernel hands gradients over in the compute dtype
     g.t[..., : pred.C] = gs_pred.permute(0, 2, 3, 1).to(dt).cuda()
@@ -237,6 +238,53 @@ def test_conv2_by_position_classes_equals_the_virtual_concatenation(dtype):
     # the four members really take different routes: the class filters' gradient slices are non-zero and differ from each other
     dw = cls[1].reshape(256, 3, 3, 512)
     assert all(float(dw[..., k * 128:(k + 1) * 128].abs().max()) > 0 for k in range(4))
+
+
+def test_conv2_class_backward_leaves_out_members_that_need_no_gradient():
+    """_conv_cat_cls_bwd guards each member of the concatenation with its own needs_grad.  With the p5 / p4 branches frozen
+    (convt1, convs1, convt2, convs2) and their inputs needing no gradient, q5 / q4 need none: the two tap input-gradient launches
+    (mode 1, contraction over 9 x 256 class channels) are not made, nothing is written for the frozen parameters, and every
+    gradient that is still computed has the bits of the all-trainable run.  Same two-stream schedule in both runs."""
+    from test_model_gpu import get_model
+    from test_round4_gpu import _bf16_randn
+    from multiposenet.pytorch_amd import _lib
+    B, S = 2, 64                                               # pyramid levels 64, 32, 16, 8 -> conv2 at 64 x 64
+    feats = [_bf16_randn(900 + i, B, 256, S >> i, S >> i, relu=True) for i in range(4)]
+    g_pred = _bf16_randn(910, B, 18, S, S, scale=0.05)
+    m = get_model(50, torch.bfloat16)
+    m.train()
+    saved = (m._engine.conv2_classes, m._engine.overlap_wgrad)
+    m._prepare(torch.zeros((B, 3, 4 * S, 4 * S), device="cuda"))
+    frozen = {n: p for n, p in m.named_parameters() if n.startswith(("convt1.", "convs1.", "convt2.", "convs2."))}
+    assert len(frozen) == 8 and all(p.requires_grad for p in frozen.values())
+
+    def run(needs):
+        _lib.TAPE = tape = []
+        try:
+            out = _head_run(m, feats, g_pred, True, True, needs)
+        finally:
+            _lib.TAPE = None
+        convs = [a[0]._obj for fn, a, is_c in tape if is_c and fn.__name__ == "mpn_conv_forward"]
+        return out, len(convs), sum(1 for c in convs if c.mode == 1 and c.Cin == 9 * 256)
+    try:
+        full, n_full, taps_full = run((True, True, True, True))
+        for p in frozen.values():
+            p.requires_grad = False
+        part, n_part, taps_part = run((True, True, False, False))
+        written = [n for n, p in frozen.items() if bool(m._arena.grad_seg(p).any())]
+    finally:
+        for p in frozen.values():
+            p.requires_grad = True
+        m._engine.conv2_classes, m._engine.overlap_wgrad = saved
+    report("conv2 by position classes, p5 / p4 branches frozen: %d -> %d mpn_conv_forward launches, tap input gradients %d -> %d"
+           % (n_full, n_part, taps_full, taps_part))
+    assert taps_full == 2, "the all-trainable run makes the two tap input gradients"
+    assert torch.equal(full[0], part[0]) and torch.equal(full[1], part[1]) and torch.equal(full[2], part[2]), "conv2 dW / db differ"
+    live = [k for k in full[3] if k.startswith(("convt3.", "convs3.", "convt4.", "convs4.", "convfin."))]
+    assert len(live) == 10 and all(torch.equal(full[3][k], part[3][k]) for k in live)
+    assert not written, "gradients were written for frozen parameters: %s" % written
+    assert taps_part == 0, "tap input gradients launched for members that need none"
+    assert n_part < n_full
 
 
 def test_conv2_by_position_classes_in_fp32_is_the_same_arithmetic():
