@@ -9,8 +9,8 @@
 //   * MFMA "B" operand cols  = output pixels   (NHWC activations: Cin contiguous per pixel/tap)
 //   so each lane ends up with 4 CONSECUTIVE output channels of one pixel -> 8/16-byte NHWC stores.
 //   * K is walked in 64-byte chunks (32 bf16 / 16 f32 channels of one tap); a chunk never straddles
-//     a tap, so the gather is one predicated 16-byte load per lane and halo pixels are zero-filled
-//     in registers (no im2col buffer, no padded copy of the activations).
+//     a tap, so the gather is one 16-byte DMA per lane and a halo pixel carries an out-of-range offset
+//     that the hardware fills with zeros (no im2col buffer, no padded copy of the activations).
 //   * 256 threads = 4 waves; block tile TC x 128 pixels; tiles travel HBM -> LDS by DMA (buffer_load ... lds)
 //     into a 3-deep ring with hand-counted vmcnt; 64-byte rows, 16-byte pieces XOR-swizzled against bank conflicts.
 //   * bf16: v_mfma_f32_16x16x32_bf16 (fp32 accumulate); f32: v_mfma_f32_16x16x4_f32 (exact fp32,
@@ -22,38 +22,11 @@
 // [Cin][R][S][Cout_pad] weight copy made by mpn_weight_transpose.
 // 3x3 / stride 1 / pad 1 launches with 16-bit operands take conv_igemm_s3_kernel (below): same tile, ring and epilogue, but the pixel
 // tile of a kernel row lands once for its three taps (the k-loop is bound by operand delivery, not by MFMA issue).
-#include "common.h"
+#include "conv_dma.h"
 #include <stdio.h>
-#include <stdlib.h>
 #include <type_traits>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
-
-template <typename T> struct Mma;
-template <> struct Mma<bf16_t> {
-    __device__ static __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                      __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-    }
-};
-template <> struct Mma<f16_t> {
-    __device__ static __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-    }
-};
-template <> struct Mma<float> {
-    __device__ static __forceinline__ void run(f32x4_t& acc, const u32x4_t& a, const u32x4_t& b) {
-        const f32x4_t fa = __builtin_bit_cast(f32x4_t, a);
-        const f32x4_t fb = __builtin_bit_cast(f32x4_t, b);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[0], fb[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[1], fb[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[2], fb[2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[3], fb[3], acc, 0, 0, 0);
-    }
-};
 
 template <typename OT> struct OutVec4;
 template <> struct OutVec4<float> {
@@ -539,28 +512,6 @@ __device__ __forceinline__ void conv_epilogue(const MpnConvParams& p, f32x4_t (&
     if (pk.fin_counters) fin_last_arriver<TC>(pk, c0, tc, tp, ntiles, lds);
 }
 
-// LDS-DMA plumbing (see conv_wgrad.hip for the probe-verified semantics): `buffer_load_dwordx4 ... lds` writes
-// 16 bytes per lane at M0 + lane*16, zero for lanes whose voffset + soffset is beyond num_records.
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ i32x4_t make_rsrc(const void* base, unsigned bytes) {
-    const uint64_t a = (uint64_t)base;
-    i32x4_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-__device__ __forceinline__ void lds_dma16(unsigned voff, i32x4_t rsrc, unsigned soff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
-}
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-
 // tools/kloop_profile.py only (PROF instantiations; production kernels compile none of it): per-wave s_memtime cycle sums of the
 // k-loop phases — own-DMA wait, barrier wait, DMA issue, fragment reads + MFMA issue — written to [workgroup][wave][8] at the end
 __device__ unsigned long long* d_igemm_prof = nullptr;
@@ -891,7 +842,7 @@ __global__ void __launch_bounds__(256, TC > 128 ? 2 : 3) conv_igemm_s3_kernel(co
                     const int hh = b_h[q] + dy;
                     const bool ok = b_ok[q] && (unsigned)hh < (unsigned)p.H;
                     const unsigned src = (unsigned)(((int)(b_wb[q] >> 16) * Hs + (hh >> sh)) * Ws + (int)((b_wb[q] & 0xffffu) >> sh));
-                    const unsigned voff = ok ? (src * (unsigned)pk.kseg_c + (unsigned)(u_piece_b * C::V)) * TS : 0x80000000u;
+                    const unsigned voff = ok ? (src * (unsigned)pk.kseg_c + (unsigned)(u_piece_b * C::V)) * TS : DMA_OOB;
                     lds_dma16(voff, rs, so, __builtin_amdgcn_readfirstlane(st + (wave_u * LB + q) * 1024u));
                 }
                 done = true;

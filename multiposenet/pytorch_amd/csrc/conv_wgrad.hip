@@ -16,23 +16,12 @@
 //   * the pixel contraction is split into `chunks` slices across workgroups; slices write f32
 //     partials to a workspace and mpn_reduce_partials adds them into dW in a fixed order
 //     (deterministic; no atomics).  chunks == 1 accumulates straight into dW.
-#include "common.h"
+#include "conv_dma.h"
 #include <stdio.h>
 #include <stdlib.h>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
-
-// 16x16x32 MFMA on 8 packed 16-bit values per lane, by element type
-template <typename T> __device__ __forceinline__ f32x4_t mma16(const u32x4_t& a, const u32x4_t& b, const f32x4_t& acc);
-template <> __device__ __forceinline__ f32x4_t mma16<bf16_t>(const u32x4_t& a, const u32x4_t& b, const f32x4_t& acc) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-}
-template <> __device__ __forceinline__ f32x4_t mma16<f16_t>(const u32x4_t& a, const u32x4_t& b, const f32x4_t& acc) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
-}
-template <> __device__ __forceinline__ f32x4_t mma16<float>(const u32x4_t&, const u32x4_t&, const f32x4_t& acc) { return acc; }   // never taken
 template <typename T> struct Ones16;
 template <> struct Ones16<bf16_t> { static constexpr unsigned kPair = 0x3F803F80u; };
 template <> struct Ones16<f16_t> { static constexpr unsigned kPair = 0x3C003C00u; };
@@ -230,7 +219,7 @@ __global__ void __launch_bounds__(256, 3) conv_wgrad_kernel(const MpnWgradParams
             for (int i = 0; i < C::MM; ++i)
 #pragma unroll
                 for (int j = 0; j < C::MN; ++j)
-                    acc[i][j] = mma16<T>(fa[i], fb[j], acc[i][j]);
+                    Mma<T>::run(acc[i][j], fa[i], fb[j]);
         } else {
 #pragma unroll
             for (int kq = 0; kq < 4; ++kq) {
@@ -298,35 +287,14 @@ __global__ void __launch_bounds__(256, 3) conv_wgrad_kernel(const MpnWgradParams
 // bf16 fast path: LDS-DMA + CDNA4 LDS transpose read.  Both operands arrive pixel-major ([k][channel]) while the
 // MFMA wants 8 consecutive k per lane.  Instead of re-packing in registers (generic kernel above), tiles land in
 // LDS exactly as they lie in memory and fragments are gathered with ds_read_b64_tr_b16, which hands lane i column
-// i of a 4(k) x 16(channel) block.  Tiles go HBM -> LDS with `buffer_load_dwordx4 ... lds` (no staging registers,
-// no ds_write pass) into a 3-deep ring, two k-steps ahead of the MFMAs.  The DMA destination is lane-linear
-// (M0 base + lane*16), so the bank swizzle of the tile image is applied on the SOURCE side: the lane that owns LDS
-// slot j of row k fetches channel chunk j ^ swz(k).  Out-of-range lanes (halo taps, channel tail, pixels past the
-// slice) carry an offset beyond num_records and the hardware writes zeros — the dY descriptor is clipped to the
-// slice end, so tail pixels need no per-step mask.  The loads are inline asm, invisible to the compiler's waitcnt
-// bookkeeping: completion is counted by hand (`s_waitcnt vmcnt(n)`, n = one k-step's loads per wave: everything but
-// the newest k-step has landed) and the barrier is the raw s_barrier, so the ring never drains inside the loop.
-// (semantics of the DMA and of the transpose read were pinned with tools/probe_dma.* and tools/probe_tr.*)
+// i of a 4(k) x 16(channel) block.  Tiles go HBM -> LDS by DMA (conv_dma.h) into a 3-deep ring, two k-steps ahead
+// of the MFMAs.  The DMA destination is lane-linear, so the bank swizzle of the tile image is applied on the SOURCE
+// side: the lane that owns LDS slot j of row k fetches channel chunk j ^ swz(k).  Out-of-range lanes (halo taps,
+// channel tail, pixels past the slice) arrive as zeros — the dY descriptor is clipped to the slice end, so tail
+// pixels need no per-step mask.  Completion is counted by hand: wait_vmcnt<one k-step's loads per wave>() =
+// everything but the newest k-step has landed.
+// (semantics of the transpose read were pinned with tools/probe_tr.*)
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ i32x4_t make_rsrc(const void* base, unsigned bytes) {
-    const uint64_t a = (uint64_t)base;
-    i32x4_t r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-__device__ __forceinline__ void lds_dma16(unsigned voff, i32x4_t rsrc, unsigned soff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
-}
-
-constexpr unsigned DMA_OOB = 0x80000000u;     // tensors are < 2 GB (launcher check): marker + soffset never wraps
 
 // Tile image in LDS: 32 pixel rows of ROWB = tile_channels * 2 bytes, back to back.  ds_read_b64_tr_b16 is serviced in
 // two 32-lane halves; one half touches 8 rows (k = {0..3} + 8*{0,1} + 4h) x 32 bytes, which must land on 8 distinct
@@ -347,17 +315,12 @@ template <typename T, int ROWB> __device__ __forceinline__ int dma_swz_t(int k) 
     return dma_swz<ROWB>(k);
 }
 
-__device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ const void* rfl_ptr(const void* q) {
-    const uint64_t a = (uint64_t)q;
-    return (const void*)(((uint64_t)(unsigned)rfl((int)(a >> 32)) << 32) | (unsigned)rfl((int)a));
-}
-
 // SEG = pyramid mode (MpnWgradParams::nseg > 0): a separate instantiation, so the single-tensor kernels keep their register
 // allocation (the level lookup costs ~30 VGPRs of address arithmetic that the compiler no longer proves uniform)
 // PROF (tools/kloop_profile.py only): a separate instantiation that accumulates, per wave, the s_memtime cycles spent in the four phases
 // of a k-step — waiting for its own DMA (s_waitcnt vmcnt), waiting at the barrier, issuing the next k-step's DMA, fragment reads + MFMA
-// issue — and writes them to `prof` [workgroup][wave][8] at the end.  Production instantiations compile none of it.
+// issue — and writes them to `prof` [workgroup][wave][8] at the end (the record layout of KProf, conv_igemm.hip).  Production instantiations
+// compile none of it.
 // What it showed (profiles/r04_kloop_phase_profile.txt): a k-step of a wave takes ~980 cycles — ~10 waiting for its DMA, ~45 at the
 // barrier, ~365 ISSUING four buffer_load ... lds (back-pressure of the CU's one texture path, 16 KB per k-step and workgroup), ~570 in
 // fragment reads + 16 MFMAs (256 cycles of matrix pipe).  Issuing the DMA between the MFMAs instead (built, measured, removed) moves
@@ -379,8 +342,8 @@ __device__ __forceinline__ void conv_wgrad_dma_body(const MpnWgradParams& pk, lo
     constexpr int QA = A_BYTES / 4096, QB = B_BYTES / 4096;  // DMA instructions (1 KiB each) per wave per k-step
     constexpr int RPA = 1024 / ROWA, RPB = 1024 / ROWB;      // tile rows covered by one instruction
     constexpr int MM = TM / 32, MN = TN / 32;                // 16x16 fragments per wave (2 x 2 waves)
-    static_assert((TM == 256 || TM == 128 || TM == 64) && (TN == 128 || TN == 64), "tile widths");
-    static_assert(ES == 2 || (TM <= 128 && !SEG), "f32: 64 / 128-wide tiles, single tensor");
+    static_assert((TM == 128 || TM == 64) && (TN == 128 || TN == 64), "tile widths");
+    static_assert(ES == 2 || !SEG, "f32: single tensor");
     __shared__ __attribute__((aligned(16))) unsigned char lds[NST * STAGE_BYTES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -572,10 +535,10 @@ __device__ __forceinline__ void conv_wgrad_dma_body(const MpnWgradParams& pk, lo
         for (int i = 0; i < MM; ++i)
 #pragma unroll
             for (int j = 0; j < MN; ++j)
-                acc[i][j] = mma16<T>(fa[i], fb[j], acc[i][j]);
+                Mma<T>::run(acc[i][j], fa[i], fb[j]);
         if (do_bias) {
 #pragma unroll
-            for (int j = 0; j < MN; ++j) accb[j] = mma16<T>(ones, fb[j], accb[j]);
+            for (int j = 0; j < MN; ++j) Mma<T>::run(accb[j], ones, fb[j]);
         }
     };
 
@@ -591,7 +554,7 @@ __device__ __forceinline__ void conv_wgrad_dma_body(const MpnWgradParams& pk, lo
     for (int it = 0; it < nsteps; ++it) {
         unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;
         if (PROF) t0 = __builtin_readcyclecounter();
-        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(QA + QB) : "memory");      // k-step `it` has landed (this wave's part)
+        wait_vmcnt<QA + QB>();                                 // k-step `it` has landed (this wave's part)
         if (PROF) t1 = __builtin_readcyclecounter();
         __builtin_amdgcn_s_barrier();                          // ... everyone's part; and slot `nxt` is no longer being read
         if (PROF) t2 = __builtin_readcyclecounter();
@@ -605,7 +568,7 @@ __device__ __forceinline__ void conv_wgrad_dma_body(const MpnWgradParams& pk, lo
         cur = (cur == NST - 1) ? 0u : cur + 1u;
         nxt = (nxt == NST - 1) ? 0u : nxt + 1u;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     const unsigned long long p_loop_end = PROF ? __builtin_readcyclecounter() : 0ull;
 
     const long NW = (long)p.Cout * taps * p.Cin;
@@ -645,27 +608,27 @@ __device__ __forceinline__ void conv_wgrad_dma_body(const MpnWgradParams& pk, lo
 }
 
 template <int TM, int TN>
-__global__ void __launch_bounds__(256, TM > 128 ? 2 : 3) conv_wgrad_dma_kernel(const MpnWgradParams p, long chunk_pixels) {
+__global__ void __launch_bounds__(256, 3) conv_wgrad_dma_kernel(const MpnWgradParams p, long chunk_pixels) {
     conv_wgrad_dma_body<bf16_t, TM, TN, false>(p, chunk_pixels);
 }
 template <int TM, int TN>
-__global__ void __launch_bounds__(256, TM > 128 ? 2 : 3) conv_wgrad_dma_prof_kernel(const MpnWgradParams p, long chunk_pixels, unsigned long long* prof) {
+__global__ void __launch_bounds__(256, 3) conv_wgrad_dma_prof_kernel(const MpnWgradParams p, long chunk_pixels, unsigned long long* prof) {
     conv_wgrad_dma_body<bf16_t, TM, TN, false, true>(p, chunk_pixels, prof);
 }
 template <int TM, int TN>
-__global__ void __launch_bounds__(256, TM > 128 ? 2 : 3) conv_wgrad_dma_lin_kernel(const MpnWgradParams p, long chunk_pixels) {
+__global__ void __launch_bounds__(256, 3) conv_wgrad_dma_lin_kernel(const MpnWgradParams p, long chunk_pixels) {
     conv_wgrad_dma_body<bf16_t, TM, TN, false, false, true>(p, chunk_pixels);
 }
 template <int TM, int TN>
-__global__ void __launch_bounds__(256, TM > 128 ? 2 : 3) conv_wgrad_dma_lin_f16_kernel(const MpnWgradParams p, long chunk_pixels) {
+__global__ void __launch_bounds__(256, 3) conv_wgrad_dma_lin_f16_kernel(const MpnWgradParams p, long chunk_pixels) {
     conv_wgrad_dma_body<f16_t, TM, TN, false, false, true>(p, chunk_pixels);
 }
 template <int TM, int TN>
-__global__ void __launch_bounds__(256, TM > 128 ? 2 : 3) conv_wgrad_dma_lin_prof_kernel(const MpnWgradParams p, long chunk_pixels, unsigned long long* prof) {
+__global__ void __launch_bounds__(256, 3) conv_wgrad_dma_lin_prof_kernel(const MpnWgradParams p, long chunk_pixels, unsigned long long* prof) {
     conv_wgrad_dma_body<bf16_t, TM, TN, false, true, true>(p, chunk_pixels, prof);
 }
 template <int TM, int TN>
-__global__ void __launch_bounds__(256, TM > 128 ? 2 : 3) conv_wgrad_dma_f16_kernel(const MpnWgradParams p, long chunk_pixels) {
+__global__ void __launch_bounds__(256, 3) conv_wgrad_dma_f16_kernel(const MpnWgradParams p, long chunk_pixels) {
     conv_wgrad_dma_body<f16_t, TM, TN, false>(p, chunk_pixels);
 }
 template <int TM, int TN>
@@ -677,11 +640,11 @@ __global__ void __launch_bounds__(256, 3) conv_wgrad_dma_lin_f32_kernel(const Mp
     conv_wgrad_dma_body<float, TM, TN, false, false, true>(p, chunk_pixels);
 }
 template <int TM, int TN>
-__global__ void __launch_bounds__(256, TM > 128 ? 2 : 3) conv_wgrad_dma_seg_kernel(const MpnWgradParams p, long chunk_pixels) {
+__global__ void __launch_bounds__(256, 3) conv_wgrad_dma_seg_kernel(const MpnWgradParams p, long chunk_pixels) {
     conv_wgrad_dma_body<bf16_t, TM, TN, true, false, true>(p, chunk_pixels);     // pyramid levels are dense stride-1 "same" convolutions (mpn_conv_wgrad checks)
 }
 template <int TM, int TN>
-__global__ void __launch_bounds__(256, TM > 128 ? 2 : 3) conv_wgrad_dma_seg_f16_kernel(const MpnWgradParams p, long chunk_pixels) {
+__global__ void __launch_bounds__(256, 3) conv_wgrad_dma_seg_f16_kernel(const MpnWgradParams p, long chunk_pixels) {
     conv_wgrad_dma_body<f16_t, TM, TN, true, false, true>(p, chunk_pixels);
 }
 
@@ -815,17 +778,6 @@ inline WgradRoute wgrad_route(const MpnWgradParams& p) {
     if (!r.dma) return r;
     if (r.tm < 64) r.tm = 64;
     if (r.tn < 64) r.tn = 64;
-    // A 256 x 128 tile moves a third less data per FLOP through the DMA/LDS path (it pays in conv_igemm), but here it
-    // measured SLOWER (3x3 256->256 @60x60: 243 vs 208 us, 512->256 @120x120: 1595 vs 1431 us): with two workgroups
-    // per CU the transpose reads are no longer hidden and the slice count (partial-sum traffic) doubles.  Kept behind
-    // MPN_WGRAD_TM256_MIN_STEPS (minimum k-steps per workgroup) for experiments, off by default.
-    static const long min_steps = mpn_tune("MPN_WGRAD_TM256_MIN_STEPS", 1L << 40);
-    if (p.dtype != MPN_F32 && p.Cin >= 256 && r.tn == 128) {        // (the f32 ring kernel has no 256-row instantiation)
-        const long tiles = (long)((p.Cin + 255) / 256) * ((p.Cout + 127) / 128) * p.R * p.S;
-        const long chunks = (kWgradTarget + tiles - 1) / tiles;
-        const long P = (long)p.B * p.Ho * p.Wo;
-        if (P / 32 / chunks >= min_steps) r.tm = 256;
-    }
     return r;
 }
 
@@ -847,23 +799,16 @@ int launch_wgrad(const MpnWgradParams& p, hipStream_t st, bool reduce = true) {
     if ((ablate & 1) && p.chunks > 1) reduce = false;
     int rc;
     const dim3 g((unsigned)grid), blk(256);
-    if (sizeof(T) == 4 && r.dma) {
-#define MPN_WGRAD_DMA_LAUNCH_F32(KERNEL)                                                                                 \
+#define MPN_WGRAD_DMA_LAUNCH(KERNEL)                                                                                     \
         if (tm == 128 && tn == 128) hipLaunchKernelGGL((KERNEL<128, 128>), g, blk, 0, st, p, chunk_pixels);              \
         else if (tm == 128) hipLaunchKernelGGL((KERNEL<128, 64>), g, blk, 0, st, p, chunk_pixels);                       \
         else if (tn == 128) hipLaunchKernelGGL((KERNEL<64, 128>), g, blk, 0, st, p, chunk_pixels);                       \
         else hipLaunchKernelGGL((KERNEL<64, 64>), g, blk, 0, st, p, chunk_pixels)
-        if (r.lin) { MPN_WGRAD_DMA_LAUNCH_F32(conv_wgrad_dma_lin_f32_kernel); }
-        else { MPN_WGRAD_DMA_LAUNCH_F32(conv_wgrad_dma_f32_kernel); }
-#undef MPN_WGRAD_DMA_LAUNCH_F32
+    if (sizeof(T) == 4 && r.dma) {
+        if (r.lin) { MPN_WGRAD_DMA_LAUNCH(conv_wgrad_dma_lin_f32_kernel); }
+        else { MPN_WGRAD_DMA_LAUNCH(conv_wgrad_dma_f32_kernel); }
         rc = mpn_launch_status();
     } else if (sizeof(T) == 2 && r.dma) {
-#define MPN_WGRAD_DMA_LAUNCH(KERNEL)                                                                                     \
-        if (tm == 256) hipLaunchKernelGGL((KERNEL<256, 128>), g, blk, 0, st, p, chunk_pixels);                           \
-        else if (tm == 128 && tn == 128) hipLaunchKernelGGL((KERNEL<128, 128>), g, blk, 0, st, p, chunk_pixels);         \
-        else if (tm == 128) hipLaunchKernelGGL((KERNEL<128, 64>), g, blk, 0, st, p, chunk_pixels);                       \
-        else if (tn == 128) hipLaunchKernelGGL((KERNEL<64, 128>), g, blk, 0, st, p, chunk_pixels);                       \
-        else hipLaunchKernelGGL((KERNEL<64, 64>), g, blk, 0, st, p, chunk_pixels)
 #if MPN_EXP
         if (g_wgrad_prof && !r.seg && p.dtype == MPN_BF16 && tm == 128 && tn == 128) {
             if (r.lin) hipLaunchKernelGGL((conv_wgrad_dma_lin_prof_kernel<128, 128>), g, blk, 0, st, p, chunk_pixels, g_wgrad_prof);
