@@ -60,12 +60,18 @@ def mse_backward_raw(pm, heat, wgt, gs, need):
     return grads
 
 
-def mse_train_supported(levels, heat):
+def mse_train_supported(levels, heat, wgt=None):
     """The one-pass form needs every intermediate level at an exact power-of-two fraction of a heat-map whose sides are multiples
-    of 8 (true of the reference's 480x480 / 384x384 training crops), and dense NCHW targets."""
-    B, C, H, W = heat.shape
-    if C != 18 or H % 8 or W % 8 or not heat.is_contiguous():
+    of 8 (true of the reference's 480x480 / 384x384 training crops), and dense NCHW f32 targets.  The kernel reads the weights with
+    the heat-map's strides and both targets with 16-byte loads: pass ``wgt`` to have it held to the same conditions."""
+    if heat.dim() != 4:
         return False
+    B, C, H, W = heat.shape
+    if C != 18 or H % 8 or W % 8:
+        return False
+    for t in (heat,) if wgt is None else (heat, wgt):
+        if t.dtype != torch.float32 or t.shape != heat.shape or not t.is_contiguous() or t.data_ptr() % 16:
+            return False
     geo = [(H >> s, W >> s) for s in (0, 1, 2, 3)] + [(H, W)]
     return all(a.B == B and (a.H, a.W) == g and a.Cs == 32 and a.t.dtype == torch.float32 for a, g in zip(levels, geo))
 
@@ -74,6 +80,10 @@ def mse_train_raw(levels, heat, wgt, gs, dtype):
     """Recorded step: heat-map loss and its gradients straight from the network's internal tensors.  levels: the five f32
     activations (k2..k5 at 1, 1/2, 1/4, 1/8 of the heat-map size, then the prediction); heat / wgt: the reference's NCHW f32 targets,
     read in place.  Returns (out[8] as mse_forward_raw, five internal gradient activations of ``dtype``)."""
+    if not mse_train_supported(levels, heat, wgt):
+        from .._lib import MpnError
+        raise MpnError("one-pass heat-map loss: levels or targets do not fit the kernel (see mse_train_supported); heat %s %s, wgt %s %s"
+                       % (tuple(heat.shape), heat.dtype, tuple(wgt.shape), wgt.dtype))
     B, _, H, W = heat.shape
     dev = heat.device
     blocks = call("mpn_mse_train_blocks", B, H, W)

@@ -108,7 +108,7 @@ class ReplayedTrainStep(object):
             fused_mse = self.fused_mse and tensors[0].shape == (hp.B, 18, hp.H, hp.W) and hp.H % 8 == 0 and hp.W % 8 == 0 \
                 and tensors[0].shape == tensors[1].shape
             pred, saved = eng.keypoint_head(ctx, kp_feats, True, internal=fused_mse)
-            if fused_mse and not losses.mse_train_supported(saved + [pred], tensors[0]):
+            if fused_mse and not losses.mse_train_supported(saved + [pred], tensors[0], tensors[1]):
                 raise _lib.MpnError("recorded train step: the keypoint head's internal geometry does not fit the one-pass loss kernel; "
                                     "construct ReplayedTrainStep(..., fused_mse=False)")
         if want_det:
