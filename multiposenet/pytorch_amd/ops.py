@@ -431,15 +431,43 @@ class Conv2ClsOperands(object):
         self.keep = comb32
 
 
+def _cls_operand(name, a, dtypes, groups, per_class=True):
+    """The conv2cls_* kernels read their operand as dense NHWC and take O from its channel storage: refuse, before anything is allocated,
+    what they would misread (a non-contiguous tensor, a width that is not 9 O or an O the vector width does not divide, an element type
+    the entry point rejects).  Returns O."""
+    if a.t.dtype not in dtypes:
+        raise _lib.MpnError("%s: unsupported dtype %s" % (name, a.t.dtype))
+    if not a.t.is_contiguous():
+        raise _lib.MpnError("%s: the operand must be dense NHWC (strides %s of shape %s)" % (name, tuple(a.t.stride()), tuple(a.t.shape)))
+    if per_class and a.Cs % 9:
+        raise _lib.MpnError("%s: %d stored channels are not nine class / tap planes" % (name, a.Cs))
+    O = a.Cs // 9 if per_class else a.Cs
+    if O <= 0 or O % groups:
+        raise _lib.MpnError("%s: %d channels per plane (need a positive multiple of %d)" % (name, O, groups))
+    return O
+
+
+_CLS_TYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
 def conv2cls_expand(m8, m4, B, H, W, O, dtype):
+    code = dtype_code(dtype)
+    if H <= 0 or W <= 0 or H % 8 or W % 8:
+        raise _lib.MpnError("conv2cls_expand: %d x %d is not a positive multiple of 8 x 8" % (H, W))
+    for a, s in ((m8, 8), (m4, 4)):
+        if _cls_operand("conv2cls_expand", a, (torch.float32,), 8) != O or tuple(a.t.shape[:3]) != (B, H // s, W // s):
+            raise _lib.MpnError("conv2cls_expand: class maps %s do not belong to a [%d, %d, %d, %d] output at 1/%d" % (tuple(a.t.shape), B, H, W, O, s))
     e = Act(torch.empty((B, H, W, O), dtype=dtype, device=m8.t.device), O)
-    call("mpn_conv2cls_expand", ptr(m8.t), ptr(m4.t), ptr(e.t), B, H, W, O, dtype_code(dtype), stream_ptr())
+    call("mpn_conv2cls_expand", ptr(m8.t), ptr(m4.t), ptr(e.t), B, H, W, O, code, stream_ptr())
     return e
 
 
 def conv2cls_pool(dy):
     """(P8 [B, H/8, W/8, 9 O], P4 [B, H/4, W/4, 9 O]): per-class sums of dy over 8 x 8 / 4 x 4 blocks (one pass over dy)."""
-    B, H, W, O = dy.B, dy.H, dy.W, dy.Cs
+    B, H, W = dy.B, dy.H, dy.W
+    O = _cls_operand("conv2cls_pool", dy, _CLS_TYPES, 8, per_class=False)
+    if H <= 0 or W <= 0 or H % 8 or W % 8:
+        raise _lib.MpnError("conv2cls_pool: %d x %d is not a positive multiple of 8 x 8" % (H, W))
     p8 = Act(torch.empty((B, H // 8, W // 8, 9 * O), dtype=dy.t.dtype, device=dy.t.device), 9 * O)
     p4 = Act(torch.empty((B, H // 4, W // 4, 9 * O), dtype=dy.t.dtype, device=dy.t.device), 9 * O)
     call("mpn_conv2cls_pool", ptr(dy.t), ptr(p8.t), ptr(p4.t), B, H, W, O, dtype_code(dy.t.dtype), stream_ptr())
@@ -448,15 +476,17 @@ def conv2cls_pool(dy):
 
 def conv2cls_classsum(t):
     """Per-tap products (f32 [B, h, w, 9 O]) -> class maps of the same shape (csrc/conv2cls.hip: conv2cls_classsum_kernel)."""
+    O = _cls_operand("conv2cls_classsum", t, (torch.float32,), 4)
     m = Act(torch.empty_like(t.t), t.C)
-    call("mpn_conv2cls_classsum", ptr(t.t), ptr(m.t), t.B, t.H, t.W, t.Cs // 9, stream_ptr())
+    call("mpn_conv2cls_classsum", ptr(t.t), ptr(m.t), t.B, t.H, t.W, O, stream_ptr())
     return m
 
 
 def conv2cls_tapsum(pc):
     """Class sums [B, h, w, 9 O] -> per-tap sums of the same shape (csrc/conv2cls.hip: conv2cls_tapsum_kernel)."""
+    O = _cls_operand("conv2cls_tapsum", pc, _CLS_TYPES, 8)
     g = Act(torch.empty_like(pc.t), pc.C)
-    call("mpn_conv2cls_tapsum", ptr(pc.t), ptr(g.t), pc.B, pc.H, pc.W, pc.Cs // 9, dtype_code(pc.t.dtype), stream_ptr())
+    call("mpn_conv2cls_tapsum", ptr(pc.t), ptr(g.t), pc.B, pc.H, pc.W, O, dtype_code(pc.t.dtype), stream_ptr())
     return g
 
 
