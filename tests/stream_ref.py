@@ -229,12 +229,16 @@ def bwd_coef_ref(part, count, gamma, mean, istd, k3_sign=-1.0):
 
 
 def check_bwd_finalize(tag, part, count, gamma, mean, istd, dg0, db0, train, dgamma, dbeta, coef, route):
+    """coef None: a frozen finalize that returns no coefficient tensor (the conv epilogue's: k1 is the forward scale) — dgamma / dbeta only."""
     S1, S2, k1, k2, k3, k3mag, n1, n2 = bwd_coef_ref(part, count, gamma, mean, istd)
     gi = k1.abs()
     is_, mu = istd.double(), mean.double()
     w = [check_rows(tag + "dbeta", dbeta, db0.double() + S1, db0.double().abs() + S1.abs(), F32, route, "c", extra_abs=n1, **roundings(2)),
-         check_rows(tag + "dgamma", dgamma, dg0.double() + S2, dg0.double().abs() + S2.abs(), F32, route, "c", extra_abs=n2, **roundings(2)),
-         check_rows(tag + "k1", coef[0], k1, k1.abs(), F32, route, "c", **roundings(1))]
+         check_rows(tag + "dgamma", dgamma, dg0.double() + S2, dg0.double().abs() + S2.abs(), F32, route, "c", extra_abs=n2, **roundings(2))]
+    if coef is None:
+        assert not train
+        return max(w)
+    w.append(check_rows(tag + "k1", coef[0], k1, k1.abs(), F32, route, "c", **roundings(1)))
     if train:
         w.append(check_rows(tag + "k2", coef[1], k2, k2.abs(), F32, route, "c", extra_abs=gi * is_ * n2 / count, **roundings(4)))
         w.append(check_rows(tag + "k3", coef[2], k3, k3mag, F32, route, "c", extra_abs=gi * ((mu * is_).abs() * n2 + n1) / count,

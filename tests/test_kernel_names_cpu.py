@@ -30,42 +30,68 @@ def _hw(H, W, k, stride, pad):
 
 # ------------------------------------------------------------------------------------------- forward / input-gradient blocks
 def conv_block(dtype, B, H, W, Cin, Cout, k, mode=0, out_f32=False, bias=False, scale=False, act=0, res=None, acc=False, stats=False,
-               fin=False, bnb=None, **_):
-    """ops.conv_forward(stride 1, 'same') as tests/test_conv_tiles_gpu.py::_conv_case calls it."""
+               fin=False, bnb=None, stride=1, out_hw=None, stem=False, res_mask=False, bnb_fin=None, **_):
+    """ops.conv_forward as tests/test_conv_tiles_gpu.py::_conv_case (stride 1, 'same') and tests/test_conv_small_tiles_gpu.py::_conv_case
+    (any stride, the strided mode 1 gather into out_hw, the stem's packed row convolution through x_geom, the loaded dgrad epilogue) call it."""
+    from multiposenet.pytorch_amd import ops
     from multiposenet.pytorch_amd._lib import ConvParams
     p = ConvParams()
-    xs, ys = round_up(Cin, 32), round_up(Cout, 32)
+    pad = (k - 1) // 2
+    if stem:        # 7x7 / stride 2 / pad 3 over the NHWC4 zero-bordered image: R = 7, S = 1 over 32 'channels' (engine.stem)
+        Ho, Wo = _hw(H, W, 7, 2, 3)
+        H, W, xs, Cin, Cout, R, S, stride, pad, cin = H + 6, W + 8, 4, 32, 64, 7, 1, 2, 0, 32
+    else:
+        Ho, Wo = _hw(H, W, k, stride, pad) if mode == 0 else (out_hw or (H, W))
+        xs, R, S = round_up(Cin, 32), k, k
+        cin = round_up(Cin, 32 if (mode == 1 or dtype != F32) else 16)
+    ys = round_up(Cout, 32)
     p.x, p.w, p.y = PTR, PTR, PTR
-    p.B, p.H, p.W, p.Ho, p.Wo = B, H, W, H, W
-    p.Cin = round_up(Cin, 32 if (mode == 1 or dtype != F32) else 16)
+    p.B, p.H, p.W, p.Ho, p.Wo = B, H, W, Ho, Wo
+    p.Cin = cin
     p.Cout, p.Cout_store = Cout, ys
     p.x_sW, p.x_sH, p.x_sB = xs, W * xs, H * W * xs
-    p.y_sP, p.y_sB = ys, H * W * ys
-    p.R, p.S, p.stride, p.pad = k, k, 1, (k - 1) // 2
+    p.y_sP, p.y_sB = ys, Ho * Wo * ys
+    p.R, p.S, p.stride, p.pad = R, S, stride, pad
     p.mode, p.act, p.accumulate, p.dtype = mode, act, 1 if acc else 0, DT[dtype]
     p.out_f32 = 1 if (out_f32 and dtype != F32) else 0
     p.bias, p.scale = (PTR if bias else None), (PTR if scale else None)
     if res:
-        p.res, p.res_mode, p.res_H, p.res_W = PTR, (1 if tuple(res) == (H, W) else 2), res[0], res[1]
+        p.res, p.res_mode, p.res_H, p.res_W = PTR, (1 if tuple(res) == (Ho, Wo) else 2), res[0], res[1]
         p.res_sP, p.res_sB = ys, res[0] * res[1] * ys
+        if res_mask:
+            p.res_mask = PTR
+    tiles = (B * Ho * Wo + 127) // 128
     if stats:
         p.stats = PTR
-    if fin:
-        p.fin_counters, p.fin_gamma, p.fin_beta, p.fin_out, p.fin_count = PTR, PTR, PTR, PTR, float(B * H * W)
+    if fin and ops.fin_in_launch(tiles, Cout):
+        p.fin_counters, p.fin_gamma, p.fin_beta, p.fin_out, p.fin_count = PTR, PTR, PTR, PTR, float(B * Ho * Wo)
     if bnb:
-        p.bnb_partial, p.bnb_y, p.bnb_mean, p.bnb_invstd, p.bnb_scale, p.bnb_shift, p.bnb_relu = PTR, PTR, PTR, PTR, PTR, PTR, 1
-        if bnb == "mask":
-            p.bnb_mask = PTR
-        else:
-            p.bnb_z = PTR
+        _bnb_fields(p, bnb)
+        if bnb_fin and ops.fin_in_launch(tiles, Cout):
+            p.fin_counters, p.fin_gamma, p.fin_dgamma, p.fin_dbeta, p.fin_count = PTR, PTR, PTR, PTR, float(B * Ho * Wo)
+            p.fin_train = 1 if bnb_fin == "train" else 0
+            p.fin_out = PTR if bnb_fin == "train" else None
     return p
 
 
-def class_block(dtype, B, H, W, Cin, Cout, a=1, c=1, acc=False, **_):
+def _bnb_fields(p, bnb):
+    """BatchNorm-backward statistics in the epilogue: the ReLU mask from z ('z'), from its sign bits ('mask'), recomputed from
+    y * scale + shift ('re'), or none ('norelu')."""
+    p.bnb_partial, p.bnb_y, p.bnb_mean, p.bnb_invstd, p.bnb_scale, p.bnb_shift = PTR, PTR, PTR, PTR, PTR, PTR
+    p.bnb_relu = 0 if bnb == "norelu" else 1
+    if bnb == "mask":
+        p.bnb_mask = PTR
+    elif bnb == "z":
+        p.bnb_z = PTR
+
+
+def class_block(dtype, B, H, W, Cin, Cout, a=1, c=1, acc=False, k=3, bnb=None, **_):
     """Parity class (a, c) of the 3x3 / stride 2 / pad 1 input gradient of _ystep_case (ops._conv_dgrad_s2_classes): dx [B, H, W, Cout] from
-    dy with Cin channels."""
+    dy with Cin channels.  k = 1: the one-tap class (0, 0) of a 1x1 / stride 2 input gradient into an existing dx."""
     from multiposenet.pytorch_amd._lib import ConvParams
     p = ConvParams()
+    if k == 1:
+        a = c = 0
     Hy, Wy = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     xs, ys = round_up(Cin, 32), round_up(Cout, 32)
     p.x, p.w, p.y = PTR, PTR, PTR
@@ -75,7 +101,12 @@ def class_block(dtype, B, H, W, Cin, Cout, a=1, c=1, acc=False, **_):
     p.y_sP, p.y_sB, p.y_H, p.y_W = ys, H * W * ys, H, W
     p.R, p.S, p.stride, p.pad, p.dtype, p.accumulate = 1 + a, 1 + c, 1, 0, DT[dtype], 1 if acc else 0
     p.y_step, p.y_oh, p.y_ow = 2, a, c
-    p.w_taps, p.wtap0, p.wtap_dr, p.wtap_ds = 9, (a + 1) * 3 + (c + 1), -6, -2
+    if k == 1:
+        p.w_taps, p.wtap0, p.wtap_dr, p.wtap_ds = 1, 0, 0, 0
+    else:
+        p.w_taps, p.wtap0, p.wtap_dr, p.wtap_ds = 9, (a + 1) * 3 + (c + 1), -6, -2
+    if bnb:
+        _bnb_fields(p, bnb)
     return p
 
 
@@ -96,14 +127,15 @@ def kseg_block(dtype, B, H, W, Cout, **_):
     return p
 
 
-def pyramid_block(dtype, B, Cin, Cout, levels, **_):
-    """ops.conv_forward_seg: 3x3 tower over the pyramid levels, bias + ReLU (_pyramid_case)."""
+def pyramid_block(dtype, B, Cin, Cout, levels, act=1, out_f32=False, **_):
+    """ops.conv_forward_seg: 3x3 tower over the pyramid levels, bias + ReLU (_pyramid_case) or bias + sigmoid into f32 (the class head)."""
     from multiposenet.pytorch_amd._lib import ConvParams
     p = ConvParams()
     p.w, p.bias = PTR, PTR
     p.B, p.Cin, p.Cout, p.Cout_store = B, round_up(Cin, 32), Cout, round_up(Cout, 32)
     p.x_sW, p.y_sP = round_up(Cin, 32), round_up(Cout, 32)
-    p.R, p.S, p.stride, p.pad, p.act, p.dtype = 3, 3, 1, 1, 1, DT[dtype]
+    p.R, p.S, p.stride, p.pad, p.act, p.dtype = 3, 3, 1, 1, act, DT[dtype]
+    p.out_f32 = 1 if (out_f32 and dtype != F32) else 0
     p.nseg = len(levels)
     tile0 = 0
     for l, s in enumerate(levels):
