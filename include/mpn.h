@@ -420,7 +420,8 @@ int mpn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_av
 /* The same update with every scalar read from DEVICE memory, so that a captured hipGraph of the training step replays
  * correct Adam steps: hyper[0..7] = {lr, beta1, beta2, eps, weight_decay, grad_scale, bias_correction1,
  * sqrt(bias_correction2)} (floats), hyper[8] = step count (int32 bits).  mpn_adam_advance does step += 1 and recomputes
- * hyper[6..7] (double-precision pow, the values torch computes on the host); mpn_adam_step_dev applies one update to a
+ * hyper[6..7] (double-precision pow of the FLOAT betas in hyper[1..2]: Adam with the float32-rounded betas, within 2.4e-7 /
+ * 6.5e-6 relative of the values torch forms from the host doubles, see weight_prep.hip); mpn_adam_step_dev applies one update to a
  * 16-byte aligned run of the arena.  The host only rewrites hyper[0] when the scheduler changes the learning rate. */
 int mpn_adam_advance(float* hyper, void* stream);
 int mpn_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hyper,

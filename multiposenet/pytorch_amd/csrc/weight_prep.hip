@@ -161,8 +161,13 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 
 // Device-resident optimizer state (so that a captured hipGraph replays correct steps): hyper[0..7] =
 // {lr, beta1, beta2, eps, weight_decay, grad_scale, bias_correction1, sqrt(bias_correction2)}, hyper[8] = step (as float
-// bits of an int32).  adam_advance increments the step and refreshes the two bias corrections in double precision,
-// exactly the values torch.optim.Adam computes on the host.
+// bits of an int32).  adam_advance increments the step and refreshes the two bias corrections in double precision from the
+// FLOAT betas in hyper[1..2] widened to double.  The update kernels read the same float betas, so the weights 1 - b and the
+// corrections 1 - b^t belong to one beta: this is exact Adam with the float32-rounded betas (0.9f = 0.89999998, 0.999f =
+// 0.99900001).  torch.optim.Adam raises the Python doubles 0.9 / 0.999 on the host instead; over t = 1 .. 10^5 the float32
+// corrections differ from torch's by at most 2.4e-7 relative for bias_correction1 (t = 2; at t = 1 it is 1 - 0.9f = 0.10000002,
+// three float spacings above 0.1f) and 6.5e-6 for sqrt(bias_correction2) (t = 4), and by nothing once b^t has decayed
+// (tests/param_ref.py beta_rounding_distance).
 __global__ void adam_advance_kernel(float* __restrict__ hyper) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int* stepp = reinterpret_cast<int*>(hyper + 8);
@@ -232,7 +237,7 @@ extern "C" int mpn_cast_f32(const float* src, void* dst, int64_t n, int dtype, v
 }
 
 extern "C" int mpn_weight_transpose(const float* w, void* wt, int Cout, int RS, int Cin, int Cout_pad, int dtype, void* stream) {
-    MPN_CHECK_ARG(w && wt && Cout > 0 && RS > 0 && Cin > 0 && Cout_pad >= Cout);
+    MPN_CHECK_ARG(w && wt && Cout > 0 && RS > 0 && Cin > 0 && Cout_pad >= Cout && mpn_dtype_ok(dtype));
     dim3 grid((Cin + 31) / 32, (Cout_pad + 31) / 32, RS), block(32, 8);
     MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((weight_transpose_kernel<T>), grid, block, 0, (hipStream_t)stream, w, (T*)wt, Cout, RS, Cin, Cout_pad));
     return mpn_launch_status();
@@ -240,21 +245,21 @@ extern "C" int mpn_weight_transpose(const float* w, void* wt, int Cout, int RS, 
 
 extern "C" int mpn_weight_transpose_batched(const float* arena, void* dst, const int64_t* table, int nlayers, int64_t nblocks,
                                             int dtype, void* stream) {
-    MPN_CHECK_ARG(arena && dst && table && nlayers > 0 && nblocks > 0 && nblocks < 0x7fffffffLL);
+    MPN_CHECK_ARG(arena && dst && table && nlayers > 0 && nblocks > 0 && nblocks < 0x7fffffffLL && mpn_dtype_ok(dtype));
     dim3 grid((unsigned)nblocks), block(32, 8);
     MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((weight_transpose_batched_kernel<T>), grid, block, 0, (hipStream_t)stream, arena, (T*)dst, (const long*)table, nlayers));
     return mpn_launch_status();
 }
 
 extern "C" int mpn_weight_pad_k(const float* w, void* dst, int Cout, int K, int Kpad, int dtype, void* stream) {
-    MPN_CHECK_ARG(w && dst && Cout > 0 && K > 0 && Kpad >= K);
+    MPN_CHECK_ARG(w && dst && Cout > 0 && K > 0 && Kpad >= K && mpn_dtype_ok(dtype));
     const long n = (long)Cout * Kpad;
     MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((weight_pad_k_kernel<T>), dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, w, (T*)dst, Cout, K, Kpad));
     return mpn_launch_status();
 }
 
 extern "C" int mpn_stem_pack_weight(const float* w, void* packed, int Cout, int dtype, void* stream) {
-    MPN_CHECK_ARG(w && packed && Cout > 0);
+    MPN_CHECK_ARG(w && packed && Cout > 0 && mpn_dtype_ok(dtype));
     const long n = (long)Cout * 7 * 32;
     MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((stem_pack_weight_kernel<T>), dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, w, (T*)packed, Cout));
     return mpn_launch_status();
@@ -268,7 +273,7 @@ extern "C" int mpn_stem_unpack_wgrad(const float* dpacked, float* dw, int Cout, 
 
 extern "C" int mpn_stem_pack_image(const float* img, int64_t sB, int64_t sC, int64_t sH, int64_t sW, void* dst,
                                    int B, int H, int W, int dtype, void* stream) {
-    MPN_CHECK_ARG(img && dst && B > 0 && H > 0 && W > 0);
+    MPN_CHECK_ARG(img && dst && B > 0 && H > 0 && W > 0 && mpn_dtype_ok(dtype));
     const long n = (long)B * (H + 6) * (W + 8);
     MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((stem_pack_image_kernel<T>), dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, img, (long)sB, (long)sC, (long)sH, (long)sW, (T*)dst, B, H, W));
     return mpn_launch_status();
