@@ -351,6 +351,19 @@ int mpn_bce_mean_backward(const float* p, const float* label, float* dp, int64_t
 int mpn_dropout(const void* x, void* y, int64_t n, uint64_t seed, float p, int dtype, void* stream);
 int mpn_bce_chunks(int64_t n);
 int mpn_bce_mean_forward(const float* p, const float* label, int64_t n, float* partial, int chunks, float* out, void* stream);
+/* The recorded PRN training step (replay.py).
+ * mpn_dropout_dev = mpn_dropout with seed = state[0] + k (wrapping 64-bit), state a device uint64[1] (8-byte aligned): a
+ * launch list that holds `state` and `k` draws new masks on every replay.  mpn_dropout_advance: state[0] += inc. */
+int mpn_dropout_dev(const void* x, void* y, int64_t n, const uint64_t* state, uint64_t k, float p, int dtype, void* stream);
+int mpn_dropout_advance(uint64_t* state, uint64_t inc, void* stream);
+/* y[rows][npad] (dtype) = x[rows][n] (f32) rounded to nearest even, columns n .. npad zero: the PRN's input activation */
+int mpn_prn_pack(const float* x, void* y, int rows, int n, int npad, int dtype, void* stream);
+/* mpn_add_softmax_rows(relu = 1) -> mpn_bce_mean_forward / _backward -> mpn_softmax_rows_backward -> cast, in one launch per
+ * row plus the mean finalize: dl[rows][npad] (dtype; columns cols .. npad zero) holds the gradient of mean BCE with respect to
+ * the pre-activation o (row stride o_stride), bit-equal to that chain's; loss[0] = mean BCE from `rows` f32 partials (differs
+ * from mpn_bce_mean_forward in summation order only).  gscale: device float (NULL = 1).  The probabilities are not stored. */
+int mpn_prn_head_train(const float* o, int64_t o_stride, const float* res, const float* label, const float* gscale, void* dl,
+                       int rows, int cols, int npad, int dtype, float* partial, float* loss, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Boxes (network/utils.py:19-61, network/posenet.py:266-271)

@@ -146,6 +146,10 @@ SIGNATURES = {
     "mpn_dropout": (_i, [_vp, _vp, _i64, ctypes.c_uint64, _f, _i, _vp]),
     "mpn_bce_chunks": (_i, [_i64]),
     "mpn_bce_mean_forward": (_i, [_vp, _vp, _i64, _vp, _i, _vp, _vp]),
+    "mpn_dropout_dev": (_i, [_vp, _vp, _i64, _vp, ctypes.c_uint64, _f, _i, _vp]),
+    "mpn_dropout_advance": (_i, [_vp, ctypes.c_uint64, _vp]),
+    "mpn_prn_pack": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "mpn_prn_head_train": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mpn_box_decode_clip": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
     "mpn_box_decode_clip_ms": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, ctypes.POINTER(ctypes.c_float), _vp]),
     "mpn_clip_boxes": (_i, [_vp, _i64, _f, _f, _vp]),

@@ -721,6 +721,114 @@ __global__ void mean_finalize_kernel(const float* __restrict__ partial, int chun
     if (threadIdx.x == 0) { double t = 0.0; for (int i = 0; i < 256; ++i) t += sh[i]; out[0] = (float)(t / n); }
 }
 
+// ---- recorded PRN step (replay.py): dropout seeded from device memory, input packing, loss head in one launch ----------------
+// dropout_kernel with seed = state[0] + k (wrapping): the recorded launch list holds the pointer and k, the word moves on by
+// dropout_advance_kernel once per step, so every replay draws the masks the eager step's host-made seeds would give.
+template <typename T>
+__global__ void dropout_dev_kernel(const T* __restrict__ x, T* __restrict__ y, long n, const unsigned long long* __restrict__ state,
+                                   unsigned long long k, float p, float scale) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned long long seed = state[0] + k;
+    const unsigned long long h = mix64(mix64(seed) ^ (unsigned long long)i);
+    const float u = (float)(h >> 40) * (1.0f / 16777216.0f);
+    Elem<T>::st(y + i, u >= p ? Elem<T>::ld(x + i) * scale : 0.f);
+}
+
+__global__ void dropout_advance_kernel(unsigned long long* __restrict__ state, unsigned long long inc) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    state[0] = state[0] + inc;
+}
+
+// y[r][c] = (T) x[r][c] for c < n, 0 for n <= c < npad: the PRN's input row as the first Linear layer reads it
+template <typename T>
+__global__ void prn_pack_kernel(const float* __restrict__ x, T* __restrict__ y, long total, int n, int npad) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const long r = i / npad; const int c = (int)(i - r * npad);
+    Elem<T>::st(y + i, c < n ? x[r * n + c] : 0.f);
+}
+
+// The values add_softmax_rows_kernel stores and bce_bwd_kernel / softmax_rows_bwd_kernel read back are f32 in memory; here they
+// stay in registers, so the products that were rounded by that store must not fuse with the operation that consumes them.
+__device__ __forceinline__ float prn_prob(float e, float inv) {
+#pragma clang fp contract(off)
+    const float p = e * inv;
+    return p;
+}
+__device__ __forceinline__ float prn_dprob(float gs, float pv, float y) {
+#pragma clang fp contract(off)
+    const float d = gs * (pv - y) / fmaxf(pv * (1.f - pv), 1e-12f);
+    return d;
+}
+__device__ __forceinline__ float prn_dlogit(float pv, float dp, float dot) {
+#pragma clang fp contract(off)
+    const float g = pv * (dp - dot);
+    return g;
+}
+
+// add_softmax_rows (relu = 1) -> BCE mean forward / backward -> softmax_rows_backward -> cast, one workgroup per row; p and dp
+// are recomputed per pass instead of stored (four passes over o / res, two over label).  Each pass keeps the producing kernel's
+// lane-strided accumulation, wave reduction and four-wave combine, so dl carries the chain's bits; the loss leaves as one f32
+// partial per row (mean_finalize_kernel sums them in double).
+template <typename T>
+__global__ void __launch_bounds__(256) prn_head_train_kernel(const float* __restrict__ a, long a_stride, const float* __restrict__ res,
+                                                             const float* __restrict__ label, const float* __restrict__ gscale,
+                                                             T* __restrict__ dl, int cols, int npad, long ntotal,
+                                                             float* __restrict__ partial) {
+    __shared__ float sh[4];
+    __shared__ float sl[4];
+    __shared__ float bc;
+    const long row = blockIdx.x;
+    const float* pa = a + row * a_stride; const float* pr = res + row * cols; const float* py = label + row * cols;
+    T* po = dl + row * npad;
+    float mx = -INFINITY;
+    const float lo = 0.f;
+    for (int i = threadIdx.x; i < cols; i += 256) mx = fmaxf(mx, fmaxf(pa[i], lo) + pr[i]);
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) bc = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+    __syncthreads();
+    mx = bc;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < cols; i += 256) s += expf(fmaxf(pa[i], lo) + pr[i] - mx);
+    s = wave_sum(s);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) bc = sh[0] + sh[1] + sh[2] + sh[3];
+    __syncthreads();
+    const float inv = 1.0f / bc;
+    const float gs = (gscale ? gscale[0] : 1.f) / (float)ntotal;
+    s = 0.f;
+    float ls = 0.f;
+    for (int i = threadIdx.x; i < cols; i += 256) {
+        const float pv = prn_prob(expf(fmaxf(pa[i], lo) + pr[i] - mx), inv);
+        const float yv = py[i];
+        const float dp = prn_dprob(gs, pv, yv);
+        s += pv * dp;
+        const float lp = fmaxf(logf(pv), -100.f), lq = fmaxf(logf(1.f - pv), -100.f);
+        ls += -(yv * lp + (1.f - yv) * lq);
+    }
+    s = wave_sum(s);
+    ls = wave_sum(ls);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = s; sl[threadIdx.x >> 6] = ls; }
+    __syncthreads();
+    if (threadIdx.x == 0) { bc = sh[0] + sh[1] + sh[2] + sh[3]; partial[row] = sl[0] + sl[1] + sl[2] + sl[3]; }
+    __syncthreads();
+    const float dot = bc;
+    for (int i = threadIdx.x; i < cols; i += 256) {
+        const float av = pa[i];
+        const float pv = prn_prob(expf(fmaxf(av, lo) + pr[i] - mx), inv);
+        const float dp = prn_dprob(gs, pv, py[i]);
+        const float g = prn_dlogit(pv, dp, dot);
+        Elem<T>::st(po + i, av > 0.f ? g : 0.f);      // relu mask of the pre-activation
+    }
+    for (int i = cols + threadIdx.x; i < npad; i += 256) Elem<T>::st(po + i, 0.f);
+}
+
 }  // namespace
 
 extern "C" int mpn_mse_chunks(int64_t npix) { return (int)((npix * 18 + MSE_CHUNK - 1) / MSE_CHUNK); }
@@ -891,5 +999,41 @@ extern "C" int mpn_bce_mean_forward(const float* p, const float* label, int64_t 
     MPN_CHECK_ARG(p && label && partial && out && n > 0 && chunks == mpn_bce_chunks(n));
     hipLaunchKernelGGL(bce_partial_kernel, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream, p, label, (long)n, partial);
     hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, chunks, (double)n, out);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_dropout_dev(const void* x, void* y, int64_t n, const uint64_t* state, uint64_t k, float p, int dtype, void* stream) {
+    MPN_CHECK_ARG(x && y && state && n > 0 && p >= 0.f && p < 1.f && mpn_dtype_ok(dtype));
+    const uintptr_t esz = dtype == MPN_F32 ? 4 : 2;
+    MPN_CHECK_ARG(((uintptr_t)state & 7) == 0 && ((uintptr_t)x & (esz - 1)) == 0 && ((uintptr_t)y & (esz - 1)) == 0);
+    const float scale = 1.0f / (1.0f - p);
+    MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((dropout_dev_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T*)x, (T*)y, (long)n,
+                                             (const unsigned long long*)state, (unsigned long long)k, p, scale));
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_dropout_advance(uint64_t* state, uint64_t inc, void* stream) {
+    MPN_CHECK_ARG(state && ((uintptr_t)state & 7) == 0);
+    hipLaunchKernelGGL(dropout_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)state, (unsigned long long)inc);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_prn_pack(const float* x, void* y, int rows, int n, int npad, int dtype, void* stream) {
+    MPN_CHECK_ARG(x && y && rows > 0 && n > 0 && npad >= n && mpn_dtype_ok(dtype));
+    MPN_CHECK_ARG(((uintptr_t)x & 3) == 0 && ((uintptr_t)y & (dtype == MPN_F32 ? 3 : 1)) == 0);
+    const long total = (long)rows * npad;
+    MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((prn_pack_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, (T*)y, total, n, npad));
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_prn_head_train(const float* o, int64_t o_stride, const float* res, const float* label, const float* gscale, void* dl,
+                                  int rows, int cols, int npad, int dtype, float* partial, float* loss, void* stream) {
+    MPN_CHECK_ARG(o && res && label && dl && partial && loss && rows > 0 && cols > 0 && npad >= cols && o_stride >= cols && mpn_dtype_ok(dtype));
+    MPN_CHECK_ARG((((uintptr_t)o | (uintptr_t)res | (uintptr_t)label | (uintptr_t)gscale | (uintptr_t)partial | (uintptr_t)loss) & 3) == 0);
+    MPN_CHECK_ARG(((uintptr_t)dl & (dtype == MPN_F32 ? 3 : 1)) == 0);
+    const long ntotal = (long)rows * cols;
+    MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((prn_head_train_kernel<T>), dim3(rows), dim3(256), 0, (hipStream_t)stream, o, (long)o_stride, res, label, gscale,
+                                             (T*)dl, cols, npad, ntotal, partial));
+    hipLaunchKernelGGL(mean_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, rows, (double)ntotal, loss);
     return mpn_launch_status();
 }

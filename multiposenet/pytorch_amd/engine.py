@@ -80,10 +80,25 @@ def _geom(layer):
     return w.shape[0], w.shape[1], w.shape[2], w.shape[3], layer.stride[0], layer.padding[0]
 
 
+def drop_state_step(mirror, initial_seed, drop_calls, d):
+    """Host side of the device-seeded dropout (mpn_dropout_dev), as pure integer arithmetic.
+
+    The eager ``Engine.dropout`` seeds its j-th call ever with ``initial_seed * 1000003 + j`` (mod 2^64).  A recorded step with
+    ``d`` dropouts reads ``word + k`` for k = 1 .. d and ends with ``word += d`` on the device, so before the step the word must
+    equal ``initial_seed * 1000003 + drop_calls``.  ``mirror`` is what the device word holds now (None: unknown).  Returns
+    ``(upload, mirror_after)``: the value to write to the device before the step (None when it already holds it) and the word
+    after the step's advance.  The caller adds ``d`` to its call counter."""
+    mask = (1 << 64) - 1
+    want = (int(initial_seed) * 1000003 + int(drop_calls)) & mask
+    return (None if mirror == want else want), (want + int(d)) & mask
+
+
 class Engine(object):
     def __init__(self, model):
         self.m = model
         self._drop_calls = 0
+        self._drop_state = None      # device uint64[1]: seed base of the recorded step's dropouts (begin_drop_step)
+        self._drop_mirror = None     # what that word holds, kept on the host (drop_state_step)
         self._side = None
         self._wt_plan_cache = None
         self.overlap_wgrad = os.environ.get("MPN_SIDE_STREAM", "1") != "0"
@@ -512,6 +527,43 @@ class Engine(object):
                 ctx.set_grad(x, g)
             ctx.tape.append(bwd)
         return y
+
+    # ---- dropout of a recorded step: the seed comes from a device word, so the launch list draws new masks on every replay
+    def begin_drop_step(self, device, d):
+        """Called OUTSIDE the launch list, before a step whose ``d`` forward dropouts are ``dropout_dev(k = 1 .. d)``: make the
+        device word hold what the eager formula gives for the step about to run (uploaded only when the host's mirror of the word
+        disagrees: first use, ``torch.manual_seed`` between steps, eager dropouts in between) and count the step's dropouts."""
+        st = self._drop_state
+        if st is None or st.device != device:
+            st = self._drop_state = torch.zeros(1, dtype=torch.int64, device=device)      # the 64 bits of the unsigned word
+            self._drop_mirror = None
+        upload, self._drop_mirror = drop_state_step(self._drop_mirror, torch.initial_seed(), self._drop_calls, d)
+        if upload is not None:
+            st.copy_(torch.tensor([upload - (1 << 64) if upload >> 63 else upload], dtype=torch.int64))
+        self._drop_calls += d
+        return st
+
+    def dropout_dev(self, ctx, x, p, k):
+        """``dropout`` with seed = device word + k (mpn_dropout_dev): the k-th dropout of a step begun with begin_drop_step."""
+        st = self._drop_state
+        y = Act(torch.empty_like(x.t), x.C)
+        call("mpn_dropout_dev", ops.ptr(x.t), ops.ptr(y.t), x.t.numel(), ops.ptr(st), k, float(p), ops.dtype_code(x.t.dtype), ops.stream_ptr())
+        if ctx.train and x.needs_grad:
+            y.needs_grad = True
+
+            def bwd():
+                dy = ctx.pop_grad(y)
+                if dy is None:
+                    return
+                g = Act(torch.empty_like(dy.t), x.C)
+                call("mpn_dropout_dev", ops.ptr(dy.t), ops.ptr(g.t), dy.t.numel(), ops.ptr(st), k, float(p), ops.dtype_code(dy.t.dtype), ops.stream_ptr())
+                ctx.set_grad(x, g)
+            ctx.tape.append(bwd)
+        return y
+
+    def end_drop_step(self, d):
+        """Last launch of the step (after the update, main stream): the device word moves on by the step's ``d`` dropouts."""
+        call("mpn_dropout_advance", ops.ptr(self._drop_state), d, ops.stream_ptr())
 
     def relu(self, ctx, x):
         z = ops.relu_forward(x)

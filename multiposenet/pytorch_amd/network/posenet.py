@@ -16,6 +16,7 @@ Internals differ completely: parameters are views into one flat f32 arena (conv 
 forward/backward is a tape of fused kernel launches (engine.py) entered by autograd through a single
 node.  If ``libmpn_hip.so`` is missing every forward raises ``MpnError`` — there is no fallback.
 """
+import ctypes
 import math
 import weakref
 from collections import OrderedDict
@@ -479,6 +480,52 @@ class poseNet(nn.Module):
         self._finish_forward(ctx)
         return [[ops.export_f32(a, a.C, a.H, a.W) for a in kp], [ops.export_f32(a, a.C, a.H, a.W) for a in det]]
 
+    def _prn_layers(self, ctx, xin, drop):
+        """The PRN's layer sequence from the packed input to the f32 pre-activation of dens2 — one implementation for the eager
+        forward below and the recorded step (prn_train_body).  ``drop(ctx, h, k)`` is the k-th dropout of the pass (k = 1, 2):
+        the eager path seeds it on the host (Engine.dropout), the recorded one from device memory (Engine.dropout_dev)."""
+        eng, prn = self._engine, self.prn
+        h, _ = eng.conv(ctx, xin, prn.dens1, act=1)
+        if prn.drop.training:
+            h = drop(ctx, h, 1)
+        h, _ = eng.conv(ctx, h, prn.bneck, act=1)
+        if prn.drop.training:
+            h = drop(ctx, h, 2)
+        o, _ = eng.conv(ctx, h, prn.dens2, out_f32=True)            # its ReLU is folded into the softmax kernel
+        return o
+
+    def prn_train_body(self, x, label, logv, gscale=None):
+        """Forward, loss and backward of one PRN training step without autograd and without torch compute ops, for the recorded
+        launch list (replay.ReplayedTrainStep): pack -> the layers of prn_forward with device-seeded dropout -> softmax + BCE +
+        both backward kernels in one launch (mpn_prn_head_train; same gradient bits as the chain prn_forward / _BCEMean run) ->
+        the reverse tape.  ``x``: contiguous f32 [B, h, w, 17] (or any shape with B * n elements), ``label`` likewise; the mean
+        BCE lands in ``logv[11]``; ``gscale``: device float scaling the gradient (None = 1).  Returns the pass's Ctx with the gradient of the pre-activation set: the caller, who has begun
+        the step's dropouts (Engine.begin_drop_step), zeroes the gradients, runs Engine.run_backward, the optimizer and
+        Engine.end_drop_step."""
+        self._prepare(x, prn=True)
+        eng, prn = self._engine, self.prn
+        cdt = self.compute_dtype
+        B = x.shape[0]
+        n = prn.height * prn.width * 17
+        if x.numel() != B * n or label.numel() != B * n:
+            raise ValueError("PRN step: input %s / label %s do not hold %d x %d values" % (tuple(x.shape), tuple(label.shape), B, n))
+        npad = ops.round_up(n, 32)
+        if npad != n or ops.is16(cdt):
+            xin = torch.empty((B, 1, 1, npad), dtype=cdt, device=x.device)
+            call("mpn_prn_pack", ops.ptr(x), ops.ptr(xin), B, n, npad, ops.dtype_code(cdt), ops.stream_ptr())
+        else:
+            xin = x.view(B, 1, 1, n)
+        ctx = Ctx(True)
+        o = self._prn_layers(ctx, ops.Act(xin, n), lambda c, h, k: eng.dropout_dev(c, h, prn.drop.p, k))
+        if not o.needs_grad:
+            raise MpnError("PRN step: no parameter of the PRN is trainable")
+        dl = torch.empty((B, 1, 1, npad), dtype=cdt, device=x.device)
+        part = torch.empty(B, dtype=torch.float32, device=x.device)
+        call("mpn_prn_head_train", ops.ptr(o.t), o.Cs, ops.ptr(x), ops.ptr(label), ops.ptr(gscale), ops.ptr(dl), B, n, npad, ops.dtype_code(cdt),
+             ops.ptr(part), ctypes.c_void_p(logv.data_ptr() + 4 * 11), ops.stream_ptr())
+        ctx.set_grad(o, ops.Act(dl, n))
+        return ctx
+
     def prn_forward(self, img_batch):
         """posenet.py:337-350: flatten -> relu(fc) -> drop -> relu(fc) -> drop -> relu(fc) + residual -> softmax over
         all 34272 entries -> [B, h, w, 17].  The three Linear layers run on the conv kernels (1x1 image)."""
@@ -502,13 +549,7 @@ class poseNet(nn.Module):
             xin = res.view(B, 1, 1, n)
         train = torch.is_grad_enabled() and any(p.requires_grad for p in prn.parameters())
         ctx = Ctx(train)
-        h, _ = eng.conv(ctx, ops.Act(xin, n), prn.dens1, act=1)
-        if prn.drop.training:
-            h = eng.dropout(ctx, h, prn.drop.p)
-        h, _ = eng.conv(ctx, h, prn.bneck, act=1)
-        if prn.drop.training:
-            h = eng.dropout(ctx, h, prn.drop.p)
-        o, _ = eng.conv(ctx, h, prn.dens2, out_f32=True)            # its ReLU is folded into the softmax kernel
+        o = self._prn_layers(ctx, ops.Act(xin, n), lambda c, h, k: eng.dropout(c, h, prn.drop.p))
         out = torch.empty((B, n), dtype=torch.float32, device=x.device)
         call("mpn_add_softmax_rows", ops.ptr(o.t), o.Cs, ops.ptr(res), ops.ptr(out), B, n, 1, ops.stream_ptr())
         if ctx.train and o.needs_grad:

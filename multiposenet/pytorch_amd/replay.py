@@ -31,7 +31,17 @@ The parameters after a step are bit-identical to the eager step's (same kernels,
 loss runs as one launch over the internal tensors whose gradients round exactly as the API path's export -> loss -> import chain,
 and whose logged loss values agree to f32 summation order: tests/test_replay_gpu.py).
 Re-recorded when the model moves, the set of trainable parameters / BN modes / compute dtype changes, or a new input
-signature arrives.  'prn_subnet' (host-made dropout seeds) stays on the eager path.
+signature arrives.
+
+'prn_subnet' is recorded like the others (``_body_prn``): mpn_prn_pack -> the three Linear layers with dropout seeded from a
+device word (mpn_dropout_dev: seed = word + k, the word advanced by the step's last launch, so every replay draws the masks the
+eager step's host-made seeds would give; Engine.begin_drop_step keeps the word in step with ``torch.manual_seed`` and with eager
+dropouts in between, outside the list) -> softmax, BCE and both their backward kernels in one launch (mpn_prn_head_train) -> the
+reverse tape -> FusedAdam.  Its key is (subnet, input shape, label shape); the dropout mode and probability are part of the state
+signature.  Three cases of 'prn_subnet' still go to ``batch_processor.train_step`` (the Python tape):
+  * ``max_grad_norm`` set: the call raises ValueError (train_step does not clip; training.trainer._Stepper clips it eagerly);
+  * a data-parallel reducer attached to the model;
+  * an optimizer without FusedAdam's interface (``sync_hyper``), or no trainable PRN parameter.
 """
 import itertools
 import math
@@ -86,7 +96,23 @@ class ReplayedTrainStep(object):
         self.evictions = 0
 
     # ------------------------------------------------------------------ the autograd-free step body
+    def _body_prn(self, x, label):
+        """pack -> dens1 -> dropout(k=1) -> bneck -> dropout(k=2) -> dens2 -> loss head (poseNet.prn_train_body), gradient zeroing,
+        the reverse tape, Adam, and the advance of the dropout seed word.  No torch compute op, no autograd."""
+        m = self.model
+        eng = m._engine
+        logv = torch.zeros(12, dtype=torch.float32, device=x.device)
+        ctx = m.prn_train_body(x, label, logv, self._ones(x.device))          # d(loss)/d(loss) = 1, read on the device
+        self.opt.zero_grad()
+        eng.run_backward(ctx, {})
+        self.opt.step()
+        if self._prn_drops:
+            eng.end_drop_step(self._prn_drops)
+        return logv, "prn", False
+
     def _body(self, img, subnet, tensors):
+        if subnet == "prn_subnet":
+            return self._body_prn(img, tensors[0])
         m = self.model
         eng = m._engine
         want_kp = subnet in ("keypoint_subnet", "train_both")
@@ -172,6 +198,8 @@ class ReplayedTrainStep(object):
     @staticmethod
     def _log_names(want_kp, want_det, clip=False):
         names = []
+        if want_kp == "prn":
+            return [("PRN loss", 11)]
         if want_kp:
             kn = losses.build_names()
             names += [(kn[j * 2], j) for j in range(5)] + [("max_ht", 6), ("min_ht", 7)]
@@ -186,7 +214,7 @@ class ReplayedTrainStep(object):
         ar = m._arena
         return (id(ar), id(ar.grad_flat), tuple(p.requires_grad for p in ar.params), tuple(b.training for b in m._bns),
                 m.compute_dtype, id(m._reducer), m._engine.overlap_wgrad, id(self.opt._m), self.bucketed_update,
-                m._engine.conv2_classes, m._engine.virtual_concat, self._clip_sig())
+                m._engine.conv2_classes, m._engine.virtual_concat, self._clip_sig(), m.prn.drop.training, float(m.prn.drop.p))
 
     def _clip_sig(self):
         """Clipping on/off and which parameters hold a gradient (a parameter frozen after a step keeps its .grad, and the clip
@@ -202,7 +230,8 @@ class ReplayedTrainStep(object):
         if gts[0] != subnet:
             raise ValueError("inputs and gts name different subnets (%r vs %r)" % (subnet, gts[0]))
         tensors = gts[1:]
-        if subnet not in ("keypoint_subnet", "detection_subnet", "train_both"):
+        prn = subnet == "prn_subnet"
+        if subnet not in ("keypoint_subnet", "detection_subnet", "train_both") and not (prn and self._prn_recordable()):
             if self.max_grad_norm is not None:
                 raise ValueError("recorded train step: %r is not recorded and train_step does not clip; clip it on the eager path "
                                  "(training.trainer._Stepper does)" % (subnet,))
@@ -220,6 +249,26 @@ class ReplayedTrainStep(object):
             if ai < len(tensors) and tensors[ai].dim() == 3:
                 tensors[ai] = self._bucket_annotations(tensors[ai])
         key = (subnet, tuple(img.shape), img.dtype, tuple((tuple(t.shape), t.dtype) for t in tensors))
+        if prn:
+            # host half of the device-seeded dropout, outside the launch list: the seed word is (re)uploaded when the host's mirror
+            # disagrees with the eager formula, and the host call counter moves on by the step's dropouts
+            drop = self.model.prn.drop
+            self._prn_drops = 2 if drop.training else 0
+            if self._prn_drops:
+                self.model._engine.begin_drop_step(img.device, self._prn_drops)
+            try:
+                return self._run(key, img, subnet, tensors)
+            except BaseException:
+                self.model._engine._drop_mirror = None          # the step's advance may not have run: upload again next time
+                raise
+        return self._run(key, img, subnet, tensors)
+
+    def _prn_recordable(self):
+        m = self.model
+        return (self.max_grad_norm is None and getattr(m, "_reducer", None) is None and hasattr(self.opt, "sync_hyper")
+                and hasattr(m, "prn_train_body") and any(p.requires_grad for p in m.prn.parameters()))
+
+    def _run(self, key, img, subnet, tensors):
         ent = self._entries.get(key)
         if ent is not None and ent.sig != self._state_sig():
             ent = None

@@ -10,8 +10,9 @@ What is built differently, for one process per GPU and a device that runs a step
 
   * **the step** is the recorded launch list (``replay.ReplayedTrainStep``): forward, losses, both backward streams, gradient
     buckets and FusedAdam are re-issued from one list (host cost 5 ms instead of 19), gradient clipping (``max_grad_norm``)
-    included: its norm, coefficient and scaling stay on the device; the eager tape is used when the optimizer is not
-    ``FusedAdam`` or the subnet is the PRN;
+    included: its norm, coefficient and scaling stay on the device.  The PRN subnet is recorded too (dropout seeded from device
+    memory, one-launch loss head).  The eager tape is used when the optimizer is not ``FusedAdam``, and for the PRN subnet
+    with ``max_grad_norm`` set or a data-parallel reducer attached;
   * **no per-step host sync**: the loss and the log values are fetched with asynchronous copies (``losses.LazyFloat``) and
     only become floats when a log line is formatted (every ``print_freq`` steps) — the reference reads ``loss.item()``
     and seven more ``.item()`` values per step;
@@ -252,7 +253,7 @@ class _Stepper(object):
             self.fast = ReplayedTrainStep(model, optimizer, max_grad_norm=self.clip)
 
     def __call__(self, inputs, gts):
-        # the recorded step clips on the device; the PRN subnet is not recorded, and clipping it stays on the path below
+        # the recorded step clips on the device; the PRN subnet is recorded without clipping only, and clipping it stays on the path below
         if self.fast is not None and (self.clip is None or gts[0] != 'prn_subnet'):
             return self.fast(inputs, gts)
         model = self.model
