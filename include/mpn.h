@@ -524,6 +524,35 @@ int mpn_augment_image(const uint8_t* src, int64_t src_bytes, const double* table
 int mpn_augment_mask(const uint8_t* src, int64_t src_bytes, const double* table, int B, float* out, int gh, int gw, int stride,
                      int crop_x, void* stream);
 
+/* Boxes of the instance masks of a detection batch (ImageAugmentation.py:234-340 aug_*_bbox on the masks,
+ * COCO_data_pipeline.py:382-405 get_ground_truth, :444-458 bbox_collater) without any warped mask.
+ *
+ * table: double [n_inst][MPN_AUGB_COLS] (device), one row per non-crowd instance: columns 0 .. MPN_AUG_COLS - 1 are the
+ * row of the instance's SAMPLE (H, W = the full source size; the IMG columns are not read), except that MASK_OFF /
+ * MASK_PITCH address the instance's own bounding rectangle in the packed buffer src (uint8, non-zero = 1, src_bytes
+ * long); columns MPN_AUGB_RX0 .. RH place that rectangle in the H x W source (0 <= rx0, rx0 + rw <= W, rw >= 1; same
+ * for y).  Outside the rectangle the mask is 0 by construction, so a tap there reads 0 and is not dereferenced.
+ *
+ * Scan launch (grid z = instance): pixel (u, v) of the (crop_y + 1) x (crop_x + 1) mask frame is un-flipped over crop_x
+ * (u -> crop_x - u), moved by (ox, oy), mapped and sampled as mpn_augment_mask does (float64 coordinates, float32 cubic
+ * weights, the same accumulation order); it is ON when the sum is >= 0.5f; outside the canvas or the scaled image it is
+ * OFF.  Per (instance, tile of 64 x 16 pixels) one int32 record {min x, max x, min y, max y, flag} goes to workspace
+ * (mpn_augment_boxes_workspace_bytes(n_inst, crop_y, crop_x) bytes, device, caller-owned, no initialisation needed).
+ * Finalize launch (one wave per output row): row_inst int32 [n_rows] (device) names the instance of output row
+ * b * N + r or -1; out f32 [n_rows][5] = {x1, y1, x2 + 1, y2 + 1, 0} over the ON pixels, five -1 for an instance
+ * with no ON pixel and for a -1 row, five NaN for an instance whose rectangle does not lie inside its source or
+ * inside [0, src_bytes) (never dereferenced) and for a row_inst entry >= n_inst.  n_inst == 0 and n_rows == 0 are
+ * allowed (the launch is skipped).  Nothing is allocated or synchronised.
+ */
+#define MPN_AUGB_RX0 20
+#define MPN_AUGB_RY0 21
+#define MPN_AUGB_RW 22
+#define MPN_AUGB_RH 23
+#define MPN_AUGB_COLS 24
+int64_t mpn_augment_boxes_workspace_bytes(int n_inst, int crop_y, int crop_x);
+int mpn_augment_boxes(const uint8_t* src, int64_t src_bytes, const double* table, int n_inst, const int32_t* row_inst, int n_rows,
+                      float* out, int crop_y, int crop_x, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * PRN training pairs from raw COCO annotations (datasets/coco_data/prn_data_pipeline.py:33-111), one launch per batch.
  * Per sample b: box[b] = the annotation's raw (x, y, w, h); own_kp[b] = its 17 (x, y, v) keypoints; the annotations of its image

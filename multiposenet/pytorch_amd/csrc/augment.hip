@@ -12,6 +12,10 @@
 //
 // One launch covers the batch: blockIdx.z is the image, so every read of the per-sample table (MPN_AUG_* columns, doubles) is
 // wave-uniform.  Traffic: sources of <= ~1 MB each gathered through L2; 12 bytes per image pixel / 72 bytes per mask cell out.
+//
+// mpn_augment_boxes (detection batches) samples the same way from packed instance-mask rectangles, but writes no pixel: a scan
+// launch reduces the extents of the ON pixels to one int32 record per (instance, tile), a finalize launch folds them into the
+// [B][N][5] box tensor.  Both reductions are min / max over integers in a fixed order: no atomics, the same bytes every time.
 #include "common.h"
 
 namespace {
@@ -163,6 +167,139 @@ __global__ void __launch_bounds__(256) augment_mask_kernel(const uint8_t* __rest
     for (int k = 0; k < 18; ++k) o[k * cells] = val;
 }
 
+// ---- boxes of instance masks (mpn_augment_boxes) -------------------------------------------------------------------------------
+// The reference warps every instance mask through the chain and reads its box off the final (crop + 1)^2 mask with np.any
+// (COCO_data_pipeline.py:382-405).  Here no warped mask exists: every pixel of that frame is sampled once from the instance's own
+// bounding rectangle of the binary source mask, thresholded at 0.5, and only the extents of the ON pixels leave the workgroup.
+constexpr int BOX_ROWS = 4;                   // rows per lane: a workgroup of 64 x 4 lanes covers a 64 x 16 tile
+constexpr int BOX_TILE_Y = 4 * BOX_ROWS;
+constexpr int BOX_REC = 5;                    // int32 per partial record: min x, max x, min y, max y, flag (0 none, 1 any, -1 bad row)
+constexpr int BOX_EMPTY_MIN = 0x7fffffff;
+
+struct Rect { int x0, y0, w, h; };
+
+// The instance row is a sample row (MASK_OFF / MASK_PITCH address the packed rectangle, H / W are the full source) plus the
+// rectangle.  load_geo's guard speaks about an H x W source at MASK_OFF; what is stored there is the rectangle, so the guard is
+// re-stated for it: the rectangle lies inside the source and its rh rows of rw bytes lie inside the packed buffer.
+__device__ __forceinline__ Geo load_geo_rect(const double* __restrict__ row, long src_bytes, Rect& r) {
+    Geo g = load_geo(row, true, src_bytes, 1);
+    const double H = row[MPN_AUG_H], W = row[MPN_AUG_W];
+    const double x0 = row[MPN_AUGB_RX0], y0 = row[MPN_AUGB_RY0], w = row[MPN_AUGB_RW], h = row[MPN_AUGB_RH];
+    bool ok = H >= 1.0 && H <= 65536.0 && W >= 1.0 && W <= 65536.0;
+    ok = ok && x0 >= 0.0 && y0 >= 0.0 && w >= 1.0 && h >= 1.0 && x0 + w <= W && y0 + h <= H;
+    r.x0 = ok ? (int)x0 : 0; r.y0 = ok ? (int)y0 : 0; r.w = ok ? (int)w : 1; r.h = ok ? (int)h : 1;
+    g.ok = ok && g.off >= 0 && g.pitch >= (long)r.w && g.off <= src_bytes && g.pitch <= src_bytes &&
+           (long)(r.h - 1) * g.pitch + (long)r.w <= src_bytes - g.off;
+    return g;
+}
+
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+    return v;
+}
+
+__global__ void __launch_bounds__(256) augment_box_scan_kernel(const uint8_t* __restrict__ src, long src_bytes, const double* __restrict__ table,
+                                                               int32_t* __restrict__ partial, int crop_y, int crop_x) {
+    // block = 64 x 16 pixels of the (crop_y + 1) x (crop_x + 1) mask frame of instance blockIdx.z; a wave is 64 consecutive pixels
+    // of one row and walks BOX_ROWS rows.  Lanes past the frame stay OFF: no early return, every lane takes part in the reduction.
+    __shared__ int red[4][4];
+    const int u = blockIdx.x * 64 + threadIdx.x, inst = blockIdx.z;
+    Rect rc;
+    const Geo g = load_geo_rect(table + (long)inst * MPN_AUGB_COLS, src_bytes, rc);
+    int x_lo = BOX_EMPTY_MIN, x_hi = -1, y_lo = BOX_EMPTY_MIN, y_hi = -1;
+    if (g.ok && u <= crop_x) {
+        const uint8_t* base = src + g.off;
+        const int up = g.flip ? crop_x - u : u;                       // the mask is flipped over its OWN width, crop_x + 1
+#pragma unroll 1
+        for (int j = 0; j < BOX_ROWS; ++j) {
+            const int v = blockIdx.y * BOX_TILE_Y + j * 4 + threadIdx.y;
+            if (v > crop_y) break;
+            const Taps t = map_point(g, g.ox + (double)up, g.oy + (double)v);
+            if (!t.inside) continue;                                  // border 0, pad 0
+            // a tap outside the rectangle reads 0 (the mask is 0 there) and is not dereferenced
+            int cx[4];
+            bool inx[4];
+#pragma unroll
+            for (int l = 0; l < 4; ++l) {
+                cx[l] = t.x[l] - rc.x0;
+                inx[l] = cx[l] >= 0 && cx[l] < rc.w;
+            }
+            float acc = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int cy = t.y[k] - rc.y0;
+                const bool iny = cy >= 0 && cy < rc.h;
+                const uint8_t* r = base + (long)(iny ? cy : 0) * g.pitch;
+                float p[4];
+#pragma unroll
+                for (int l = 0; l < 4; ++l) p[l] = (iny && inx[l] && r[cx[l]] != 0) ? 1.0f : 0.0f;
+                float row = p[0] * t.wx[0];
+#pragma unroll
+                for (int l = 1; l < 4; ++l) row = row + p[l] * t.wx[l];
+                acc = k == 0 ? row * t.wy[0] : acc + row * t.wy[k];
+            }
+            if (acc >= 0.5f) {
+                x_lo = min(x_lo, u); x_hi = max(x_hi, u);
+                y_lo = min(y_lo, v); y_hi = max(y_hi, v);
+            }
+        }
+    }
+    // stage 1: in the wave; stage 2: the four waves through LDS; one record per (instance, tile), ordinary stores
+    x_lo = wave_min(x_lo); x_hi = wave_max(x_hi); y_lo = wave_min(y_lo); y_hi = wave_max(y_hi);
+    if (threadIdx.x == 0) {
+        red[threadIdx.y][0] = x_lo; red[threadIdx.y][1] = x_hi; red[threadIdx.y][2] = y_lo; red[threadIdx.y][3] = y_hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && threadIdx.y == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) {
+            x_lo = min(x_lo, red[w][0]); x_hi = max(x_hi, red[w][1]); y_lo = min(y_lo, red[w][2]); y_hi = max(y_hi, red[w][3]);
+        }
+        const long tiles = (long)gridDim.x * gridDim.y;
+        int32_t* o = partial + ((long)inst * tiles + (long)blockIdx.y * gridDim.x + blockIdx.x) * BOX_REC;
+        o[0] = x_lo; o[1] = x_hi; o[2] = y_lo; o[3] = y_hi;
+        o[4] = !g.ok ? -1 : (x_hi >= 0 ? 1 : 0);
+    }
+}
+
+// one wave per output row (b, r) of the [B][N][5] box tensor: folds the tiles of its instance (row_inst, -1 = padding row)
+__global__ void __launch_bounds__(64) augment_box_finalize_kernel(const int32_t* __restrict__ partial, const int32_t* __restrict__ row_inst,
+                                                                  float* __restrict__ out, int n_inst, int tiles) {
+    const int row = blockIdx.x, inst = row_inst[row];
+    float* o = out + (long)row * 5;
+    if (inst < 0 || inst >= n_inst) {
+        // bbox_collater pads with -1; a map entry that names no instance cannot come from the host wrapper: NaN
+        if (threadIdx.x < 5) o[threadIdx.x] = inst < 0 ? -1.0f : __builtin_nanf("");
+        return;
+    }
+    int x_lo = BOX_EMPTY_MIN, x_hi = -1, y_lo = BOX_EMPTY_MIN, y_hi = -1, bad = 0;
+    const int32_t* p = partial + (long)inst * tiles * BOX_REC;
+    for (int t = threadIdx.x; t < tiles; t += 64) {
+        const int32_t* q = p + (long)t * BOX_REC;
+        if (q[4] > 0) {
+            x_lo = min(x_lo, q[0]); x_hi = max(x_hi, q[1]); y_lo = min(y_lo, q[2]); y_hi = max(y_hi, q[3]);
+        }
+        bad = max(bad, q[4] < 0 ? 1 : 0);
+    }
+    x_lo = wave_min(x_lo); x_hi = wave_max(x_hi); y_lo = wave_min(y_lo); y_hi = wave_max(y_hi); bad = wave_max(bad);
+    if (threadIdx.x == 0) {
+        if (bad) {
+            for (int k = 0; k < 5; ++k) o[k] = __builtin_nanf("");
+        } else if (x_hi >= 0) {
+            // COCO_data_pipeline.py:393-398: x2 and y2 are not part of the box, class 0
+            o[0] = (float)x_lo; o[1] = (float)y_lo; o[2] = (float)(x_hi + 1); o[3] = (float)(y_hi + 1); o[4] = 0.0f;
+        } else {
+            for (int k = 0; k < 5; ++k) o[k] = -1.0f;                 // :399-402: warped out of the crop
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int mpn_augment_image(const uint8_t* src, int64_t src_bytes, const double* table, int B, float* out, int crop_y, int crop_x,
@@ -189,4 +326,29 @@ extern "C" int mpn_augment_mask(const uint8_t* src, int64_t src_bytes, const dou
     hipLaunchKernelGGL(augment_mask_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, (long)src_bytes, table, out, gh, gw,
                        (double)stride, (double)crop_x);
     return mpn_launch_status();
+}
+
+static inline long box_tiles(int crop_y, int crop_x) { return (long)((crop_x + 1 + 63) / 64) * (long)((crop_y + 1 + BOX_TILE_Y - 1) / BOX_TILE_Y); }
+
+extern "C" int64_t mpn_augment_boxes_workspace_bytes(int n_inst, int crop_y, int crop_x) {
+    if (n_inst < 0 || n_inst > 65535 || crop_y <= 0 || crop_x <= 0 || crop_y > 65535 || crop_x > 65535) return 0;
+    return (int64_t)n_inst * box_tiles(crop_y, crop_x) * BOX_REC * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int mpn_augment_boxes(const uint8_t* src, int64_t src_bytes, const double* table, int n_inst, const int32_t* row_inst, int n_rows,
+                                 float* out, int crop_y, int crop_x, void* workspace, void* stream) {
+    MPN_CHECK_ARG(n_inst >= 0 && n_inst <= 65535 && n_rows >= 0 && crop_y > 0 && crop_x > 0 && crop_y <= 65535 && crop_x <= 65535);
+    MPN_CHECK_ARG(n_inst == 0 || (src && table && workspace && src_bytes > 0));
+    MPN_CHECK_ARG(n_rows == 0 || (row_inst && out));
+    const long tiles = box_tiles(crop_y, crop_x);
+    MPN_CHECK_ARG(tiles <= 0x7fffffffL / BOX_REC);
+    if (n_inst > 0) {
+        dim3 grid((unsigned)((crop_x + 1 + 63) / 64), (unsigned)((crop_y + 1 + BOX_TILE_Y - 1) / BOX_TILE_Y), (unsigned)n_inst);
+        hipLaunchKernelGGL(augment_box_scan_kernel, grid, dim3(64, 4), 0, (hipStream_t)stream, src, (long)src_bytes, table,
+                           (int32_t*)workspace, crop_y, crop_x);
+    }
+    if (n_rows > 0)
+        hipLaunchKernelGGL(augment_box_finalize_kernel, dim3((unsigned)n_rows), dim3(64), 0, (hipStream_t)stream,
+                           (const int32_t*)workspace, row_inst, out, n_inst, (int)tiles);
+    return (n_inst > 0 || n_rows > 0) ? mpn_launch_status() : 0;
 }

@@ -15,6 +15,11 @@ Two halves:
   rounding (DESIGN.md section 7 states the deviation).  :class:`DeviceAugmenter` packs a batch, launches the two kernels and
   renders the heat-maps with :func:`..heatmap.put_gaussian_maps`.
 
+Detection batches (``Cocobbox``, ``COCO_data_pipeline.py:296-458``) go through the ``aug_*_bbox`` chain
+(``ImageAugmentation.py:234-340``), whose geometry is NOT the keypoint chain's: ``aug_rotate_bbox`` never rotates ``objpos``, so the
+crop is centred elsewhere.  :func:`augment_meta_bbox` restates that chain, :class:`DeviceBBoxAugmenter` packs the instance masks'
+bounding rectangles and ``mpn_augment_boxes`` reads every instance's box off the composed transform without warping a mask.
+
 Decoding the image files and reading the COCO json stay with the loader.
 """
 import ctypes
@@ -52,6 +57,8 @@ N_DICE = 6
 # columns of the per-sample table the kernels read (include/mpn.h: MPN_AUG_*)
 T_IMG_OFF, T_IMG_PITCH, T_MASK_OFF, T_MASK_PITCH, T_H, T_W, T_SCALE, T_NW, T_NH, T_CW, T_CH = range(11)
 T_MINV, T_OX, T_OY, T_FLIP, T_COLS = 11, 17, 18, 19, 20
+# columns an instance row of mpn_augment_boxes adds (MPN_AUGB_*): the instance's bounding rectangle inside its H x W source
+TB_RX0, TB_RY0, TB_RW, TB_RH, TB_COLS = 20, 21, 22, 23, 24
 
 
 def draw_dice(rng, params=None):
@@ -239,6 +246,72 @@ def augment_meta(H, W, scale_provided, objpos, joint_self, joint_others, dice, c
             "center": (int(center[0]), int(center[1]))}
 
 
+def augment_meta_bbox(H, W, scale_provided, objpos, dice, crop_x, crop_y, params=None):
+    """The meta-data side of aug_scale_bbox -> aug_rotate_bbox -> aug_croppad_bbox -> aug_flip_bbox (ImageAugmentation.py:234-340)
+    for one sample, op for op.  Same geometry keys as :func:`augment_meta`.  Where the chain differs from the keypoint chain:
+
+    * ``objpos`` is scaled and then moved by NOTHING: aug_rotate_bbox drops rotate_bound's matrix (:330), aug_croppad_bbox centres
+      the crop on the unrotated point on the rotated canvas and does not write it back, aug_flip_bbox does not touch it;
+    * every instance mask is sliced ``crop + 1`` long in BOTH axes (:296-297) while the image slice is ``crop`` long, and is flipped
+      over its own width: mask column x becomes ``crop_x - x`` where image column u becomes ``crop_x - 1 - u``.  Boxes therefore
+      live in the ``(crop + 1)``-wide mask frame and may reach ``crop + 1``.
+
+    Masks and image share the resize rule (``cv2.resize(fx=scale)``: dsize = round(size * scale)) and ``M``."""
+    p = DEFAULT_PARAMS if params is None else params
+    dice = np.asarray(dice, dtype=np.float64)
+    if dice.shape != (N_DICE,):
+        raise MpnError("dice must hold %d draws per sample" % N_DICE)
+    crop_x, crop_y = int(crop_x), int(crop_y)
+    objpos = np.array(objpos, dtype=np.float64)
+    if objpos.shape != (2,):
+        raise MpnError("objpos must be [2]")
+
+    # --- aug_scale_bbox (:234-257)
+    if dice[0] > p["scale_prob"]:
+        scale_multiplier = 1
+    else:
+        if np.isnan(dice[1]):
+            raise MpnError("dice[1] (aug_scale_bbox's dice2) is needed when dice[0] <= scale_prob")
+        scale_multiplier = (p["scale_max"] - p["scale_min"]) * float(dice[1]) + p["scale_min"]
+    scale_abs = p["target_dist"] / scale_provided
+    scale = scale_abs * scale_multiplier
+    if not (scale > 0 and math.isfinite(scale)):
+        raise MpnError("scale_provided gives a non-positive or non-finite scale")
+    nh, nw = int(round(H * scale)), int(round(W * scale))
+    if nh < 1 or nw < 1:
+        raise MpnError("the scaled image is empty")
+    objpos *= scale
+
+    # --- aug_rotate_bbox (:325-340) with rotate_bound (:179-202); the matrix goes to warpAffine only
+    degree = (float(dice[2]) - 0.5) * 2 * p["max_rotate_degree"]
+    cX, cY = nw // 2, nh // 2
+    M = rotation_matrix((cX, cY), -degree, 1.0)
+    cos, sin = np.abs(M[0, 0]), np.abs(M[0, 1])
+    nW = int((nh * sin) + (nw * cos))
+    nH = int((nh * cos) + (nw * sin))
+    M[0, 2] += (nW / 2) - cX
+    M[1, 2] += (nH / 2) - cY
+
+    # --- aug_croppad_bbox (:260-304)
+    x_offset = int((float(dice[3]) - 0.5) * 2 * p["center_perterb_max"])
+    y_offset = int((float(dice[4]) - 0.5) * 2 * p["center_perterb_max"])
+    center = objpos + np.array([x_offset, y_offset])
+    if not np.all(np.isfinite(center)):
+        raise MpnError("objpos is not finite")
+    center = center.astype(int)
+    # the mask slices [center + int(crop / 2), ... + crop + 1) of the canvas padded by crop on every side must lie inside it
+    x0, y0 = int(center[0]) + int(crop_x / 2), int(center[1]) + int(crop_y / 2)
+    if x0 < 0 or y0 < 0 or x0 + crop_x + 1 > nW + 2 * crop_x or y0 + crop_y + 1 > nH + 2 * crop_y:
+        raise MpnError("crop centre (%d, %d) is too far outside the %d x %d canvas: the reference's slices would wrap or truncate"
+                       % (center[0], center[1], nW, nH))
+    ox, oy = x0 - crop_x, y0 - crop_y
+
+    # --- aug_flip_bbox (:307-322)
+    flip = bool(dice[5] <= p["flip_prob"])
+    return {"objpos": objpos, "scale": float(scale), "nh": nh, "nw": nw, "nH": nH, "nW": nW, "M": M, "Minv": invert_affine(M),
+            "ox": ox, "oy": oy, "flip": flip, "degree": degree, "center": (int(center[0]), int(center[1]))}
+
+
 def table_row(geo, H, W, img_off, img_pitch, mask_off=0, mask_pitch=0):
     """One row of the per-sample table of mpn_augment_image / mpn_augment_mask (float64; every integer in it is exact)."""
     row = np.zeros(T_COLS, dtype=np.float64)
@@ -270,6 +343,94 @@ def augment_mask(src, table, gh, gw, stride, crop_x):
     return out
 
 
+def augment_boxes(src, table, row_inst, B, N, crop_y, crop_x):
+    """mpn_augment_boxes: packed instance-mask rectangles (uint8, device; None when there is no instance) + instance table
+    [n_inst, 24] float64 + row map int32 [B * N] (instance of each output row, -1 = padding) -> float32 [B, N, 5]."""
+    n_inst = 0 if table is None else int(table.shape[0])
+    dev = row_inst.device
+    out = torch.empty((B, N, 5), dtype=torch.float32, device=dev)
+    if B * N == 0:
+        return out
+    ws = torch.empty(max(int(call("mpn_augment_boxes_workspace_bytes", n_inst, crop_y, crop_x)), 16), dtype=torch.uint8, device=dev)
+    call("mpn_augment_boxes", ops.ptr(src) if n_inst else None, src.numel() if n_inst else 0, ops.ptr(table) if n_inst else None, n_inst,
+         ops.ptr(row_inst), B * N, ops.ptr(out), crop_y, crop_x, ops.ptr(ws), ops.stream_ptr())
+    return out
+
+
+def _mask_array(m, H, W):
+    if isinstance(m, torch.Tensor):
+        if m.is_cuda or m.dtype not in (torch.uint8, torch.bool):
+            raise MpnError("an instance mask must be a uint8 or bool CPU tensor or array")
+        m = m.numpy()
+    if not isinstance(m, np.ndarray) or m.dtype not in (np.uint8, np.bool_):
+        raise MpnError("an instance mask must be a uint8 or bool CPU tensor or array")
+    if m.shape != (H, W):
+        raise MpnError("an instance mask must have the image's [H, W]")
+    return m.view(np.uint8)
+
+
+def instance_rects(sample, H, W):
+    """``Cocobbox.get_instance_mask`` / ``get_ground_truth`` on the host (COCO_data_pipeline.py:342-405): an all-zero mask is dropped
+    (:354), a crowd counts for the list being non-empty but yields no row (:386-389), an empty list raises (the reference:
+    IndexError at ``instance_mask_list[0]``).  Returns [(mask as uint8 array, rx0, ry0, rw, rh)] of the instances that get a row;
+    the np.any scans that find the rectangle replace the reference's ``m.max() < 1``."""
+    inst, crowd = sample.get("instances"), sample.get("iscrowd")
+    if inst is None or crowd is None or len(inst) != len(crowd):
+        raise MpnError("a sample needs 'instances' and an 'iscrowd' entry for each of them")
+    rects, kept = [], 0
+    for m, c in zip(inst, crowd):
+        m = _mask_array(m, H, W)
+        cols = np.flatnonzero(m.any(axis=0))
+        if cols.size == 0:
+            continue
+        kept += 1
+        if int(c):
+            continue
+        rws = np.flatnonzero(m.any(axis=1))
+        rects.append((m, int(cols[0]), int(rws[0]), int(cols[-1]) - int(cols[0]) + 1, int(rws[-1]) - int(rws[0]) + 1))
+    if kept == 0:
+        raise MpnError("a sample has no instance with a non-zero mask")
+    return rects
+
+
+def boxes_from_rects(rects, metas, S, row_multiple, dev, sample_rows=None):
+    """Packs the rectangles of a batch (rects[b] from :func:`instance_rects`, metas[b] the sample's geometry with H, W) and launches
+    mpn_augment_boxes.  One pinned buffer and one H2D copy for the rectangles; one pinned block of doubles and one H2D copy for the
+    tables: the sample table ``sample_rows`` [B, 20] when given (returned as a device tensor), the instance table, and the int32
+    row map in the tail.  Returns (bbox [B, N, 5], device sample table or None)."""
+    B = len(rects)
+    N = max(len(r) for r in rects)
+    N = (N + row_multiple - 1) // row_multiple * row_multiple
+    n_inst = sum(len(r) for r in rects)
+    nbytes = sum((r[3] * r[4] + 15) // 16 * 16 for rs in rects for r in rs)
+    stage = _pinned(max(nbytes, 16), torch.uint8)
+    t0 = 0 if sample_rows is None else B * T_COLS
+    t1 = t0 + n_inst * TB_COLS
+    tab = _pinned(max(t1 + (B * N + 1) // 2, 1), torch.float64)
+    if t0:
+        tab[:t0] = torch.from_numpy(np.ascontiguousarray(sample_rows, dtype=np.float64).reshape(-1))
+    table = tab[t0:t1].view(n_inst, TB_COLS)
+    rowmap = tab[t1:].view(torch.int32)[:B * N].view(B, N)
+    rowmap.fill_(-1)
+    off, i = 0, 0
+    for b, (rs, g) in enumerate(zip(rects, metas)):
+        for r, (m, rx0, ry0, rw, rh) in enumerate(rs):
+            stage[off: off + rw * rh].view(rh, rw).copy_(torch.from_numpy(m[ry0:ry0 + rh, rx0:rx0 + rw]))
+            row = np.zeros(TB_COLS, dtype=np.float64)
+            row[:T_COLS] = table_row(g, g["H"], g["W"], 0, 0, off, rw)
+            row[TB_RX0:TB_COLS] = (rx0, ry0, rw, rh)
+            table[i] = torch.from_numpy(row)
+            rowmap[b, r] = i
+            off += (rw * rh + 15) // 16 * 16
+            i += 1
+    d_tab = tab.to(dev, non_blocking=True)
+    d_samples = d_tab[:t0].view(B, T_COLS) if t0 else None
+    d_table = d_tab[t0:t1].view(n_inst, TB_COLS) if n_inst else None
+    d_rowmap = d_tab[t1:].view(torch.int32)[:B * N]
+    d_src = stage.to(dev, non_blocking=True) if n_inst else None
+    return augment_boxes(d_src, d_table, d_rowmap, B, N, S, S), d_samples
+
+
 class DeviceAugmenter(object):
     """``DeviceAugmenter(inp_size, feat_stride)(samples)`` -> ``(img, heatmaps, heat_mask, meta)``: the reference's training triple
     for ``keypoint_subnet`` (float32, contiguous, on the current device) plus the host-side geometry of every sample.
@@ -281,8 +442,9 @@ class DeviceAugmenter(object):
          "objpos_other": [n, 2] (optional)}
 
     ``joint_self`` / ``joint_others`` with 18 rows are taken as already in this work's order (no neck is added).  With
-    ``mask_miss`` None in every sample the image-only form is returned: ``heat_mask`` is None (the ``aug_*_bbox`` chain of the
-    detection loader is the identical image chain).  ``dice`` [B, 6] makes the draws explicit; otherwise they come from ``rng``
+    ``mask_miss`` None in every sample the image-only form is returned: ``heat_mask`` is None.  (The ``aug_*_bbox`` chain of the
+    detection loader is NOT this chain with the mask left out: it never rotates ``objpos`` and so crops elsewhere; see
+    :func:`augment_meta_bbox` and :class:`DeviceBBoxAugmenter`.)  ``dice`` [B, 6] makes the draws explicit; otherwise they come from ``rng``
     (a ``random.Random``; default the ``random`` module, as in the reference) through :func:`draw_dice`."""
 
     def __init__(self, inp_size, feat_stride, params=None):
@@ -299,15 +461,17 @@ class DeviceAugmenter(object):
         if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.is_cuda or t.dim() != dims or not t.is_contiguous():
             raise MpnError("%s must be a contiguous uint8 CPU tensor with %d dimensions" % (what, dims))
 
-    def geometry(self, samples, dice=None, rng=None):
+    def geometry(self, samples, dice=None, rng=None, mask_frame=False):
         """Part 1 for a batch: list of per-sample dicts of :func:`augment_meta` with the final (``remove_illegal_joint``) joints
-        under ``joint_self_out`` / ``joint_others_out``.  Needs no GPU."""
+        under ``joint_self_out`` / ``joint_others_out``.  Needs no GPU.  ``mask_frame`` asks for the ``crop + 1`` slice test of
+        the masks even when the batch carries no ``mask_miss`` (instance masks take the same slices)."""
         B = len(samples)
         if B == 0:
             raise MpnError("empty batch")
         with_mask = [s.get("mask_miss") is not None for s in samples]
         if any(with_mask) != all(with_mask):
             raise MpnError("either every sample of a batch has a mask_miss or none has")
+        frame = with_mask[0] or mask_frame
         if dice is None:
             rng = random if rng is None else rng
             dice = np.stack([draw_dice(rng, self.params) for _ in range(B)])
@@ -333,7 +497,7 @@ class DeviceAugmenter(object):
                 raise MpnError("joint_self must be [17, 3] (COCO order) or [18, 3]")
             jo = jo.reshape(-1, 18, 3)
             geo = augment_meta(H, W, s["scale_provided"], s["objpos"], js, jo, d, self.inp_size, self.inp_size, self.params,
-                               s.get("objpos_other"), with_mask=with_mask[0])
+                               s.get("objpos_other"), with_mask=frame)
             geo["joint_self_out"], geo["joint_others_out"] = remove_illegal_joint(geo["joint_self"], geo["joint_others"],
                                                                                   self.inp_size, self.inp_size)
             geo["dice"], geo["H"], geo["W"] = d.copy(), H, W
@@ -341,9 +505,18 @@ class DeviceAugmenter(object):
         return metas
 
     def __call__(self, samples, dice=None, rng=None):
+        return self._run(samples, dice, rng, False)
+
+    def call_with_boxes(self, samples, dice=None, rng=None):
+        """For ``train_both``: ``(img, heatmaps, heat_mask, bbox, metas)``.  The samples also carry ``instances`` / ``iscrowd`` as for
+        :class:`DeviceBBoxAugmenter`; the boxes are read under THIS chain's geometry (rotated ``objpos``), through the same kernel."""
+        return self._run(samples, dice, rng, True)
+
+    def _run(self, samples, dice, rng, boxes):
         if not torch.cuda.is_available():
             raise MpnError("DeviceAugmenter runs on the MI355X only; there is no CPU path")
-        metas = self.geometry(samples, dice, rng)
+        metas = self.geometry(samples, dice, rng, mask_frame=boxes)
+        rects = [instance_rects(s, g["H"], g["W"]) for s, g in zip(samples, metas)] if boxes else None
         B, S = len(samples), self.inp_size
         has_mask = samples[0].get("mask_miss") is not None
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -381,4 +554,75 @@ class DeviceAugmenter(object):
                                      self.params["sigma"])
         # the pinned staging buffers may go out of scope here: torch's caching host allocator records the stream of a non_blocking
         # copy and hands a block out again only after that copy has finished
+        if boxes:
+            return img, heatmaps, heat_mask, boxes_from_rects(rects, metas, S, 1, dev)[0], metas
         return img, heatmaps, heat_mask, metas
+
+
+class DeviceBBoxAugmenter(object):
+    """``DeviceBBoxAugmenter(inp_size, feat_stride)(samples)`` -> ``(img, bbox, metas)``: the reference's training pair for
+    ``detection_subnet`` (``Cocobbox.__getitem__`` + ``bbox_collater``, COCO_data_pipeline.py:407-458) plus the host geometry.
+
+    A sample is a dict::
+
+        {"img": uint8 tensor [H, W, 3] (BGR, CPU, contiguous), "objpos": (x, y), "scale_provided": s,
+         "instances": [uint8 or bool [H, W] masks (CPU tensors or arrays)], "iscrowd": [0 / 1 per instance]}
+
+    ``img`` is float32 [B, 3, S, S] from mpn_augment_image under the bbox chain's geometry (:func:`augment_meta_bbox`); ``bbox`` is
+    float32 [B, N, 5] on the device, rows ``[x1, y1, x2, y2, 0]`` in the ``(S + 1)``-wide mask frame, ``-1`` rows for an instance
+    warped out of the crop and for padding.  ``N`` is the batch maximum of rows rounded up to ``row_multiple`` (1: bbox_collater's
+    shape, ``[B, 0, 5]`` when no image has a row; 8: nothing left to pad for ReplayedTrainStep's ``anno_bucket``)."""
+
+    def __init__(self, inp_size, feat_stride, params=None, row_multiple=1):
+        self.inp_size, self.stride, self.row_multiple = int(inp_size), int(feat_stride), int(row_multiple)
+        if self.inp_size <= 0 or self.stride <= 0 or int(self.inp_size / self.stride) <= 0 or self.row_multiple <= 0:
+            raise MpnError("inp_size, feat_stride and row_multiple must be positive, inp_size >= feat_stride")
+        self.params = dict(DEFAULT_PARAMS)
+        if params:
+            self.params.update(params)
+
+    def geometry(self, samples, dice=None, rng=None):
+        """List of per-sample dicts of :func:`augment_meta_bbox` plus ``H``, ``W``, ``dice`` and ``rects`` (the instances that get a
+        row, from :func:`instance_rects`).  Needs no GPU."""
+        B = len(samples)
+        if B == 0:
+            raise MpnError("empty batch")
+        if dice is None:
+            rng = random if rng is None else rng
+            dice = np.stack([draw_dice(rng, self.params) for _ in range(B)])
+        dice = np.asarray(dice, dtype=np.float64)
+        if dice.shape != (B, N_DICE):
+            raise MpnError("dice must be [B, %d]" % N_DICE)
+        metas = []
+        for s, d in zip(samples, dice):
+            img = s["img"]
+            DeviceAugmenter._check_u8(img, "img", 3)
+            if img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+                raise MpnError("img must be [H, W, 3]")
+            H, W = int(img.shape[0]), int(img.shape[1])
+            geo = augment_meta_bbox(H, W, s["scale_provided"], s["objpos"], d, self.inp_size, self.inp_size, self.params)
+            geo["dice"], geo["H"], geo["W"] = d.copy(), H, W
+            geo["rects"] = instance_rects(s, H, W)
+            metas.append(geo)
+        return metas
+
+    def __call__(self, samples, dice=None, rng=None):
+        if not torch.cuda.is_available():
+            raise MpnError("DeviceBBoxAugmenter runs on the MI355X only; there is no CPU path")
+        metas = self.geometry(samples, dice, rng)
+        B, S = len(samples), self.inp_size
+        dev = torch.device("cuda", torch.cuda.current_device())
+        img_off, ni = [], 0
+        for g in metas:
+            img_off.append(ni)
+            ni += (g["H"] * g["W"] * 3 + 15) // 16 * 16
+        stage_i = _pinned(ni, torch.uint8)
+        rows = np.zeros((B, T_COLS), dtype=np.float64)
+        for b, (s, g) in enumerate(zip(samples, metas)):
+            H, W = g["H"], g["W"]
+            stage_i[img_off[b]: img_off[b] + H * W * 3] = s["img"].view(-1)
+            rows[b] = table_row(g, H, W, img_off[b], W * 3)
+        # three H2D copies in all: the images, the mask rectangles, the tables
+        bbox, d_table = boxes_from_rects([g["rects"] for g in metas], metas, S, self.row_multiple, dev, rows)
+        img = augment_image(stage_i.to(dev, non_blocking=True), d_table, S, S)
+        return img, bbox, metas
