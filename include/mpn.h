@@ -622,6 +622,10 @@ int mpn_resize(const float* src, int64_t sY, int64_t sX, int64_t sC, int Hs, int
  * as prn_gaussian.crop does, in np.sum's own float32 order (pairwise over the row-major flattened window: exact ties between
  * candidates exist and the reference resolves them by sort order; tester.py:418-419); N odd, <= 15; argmax[b][t] = first row-major maximum of
  * the plane (tester.py:480).  H*W <= 4096.
+ * Preconditions the entry points do not check: mpn_prn_build_maps refuses H*W > 4096 (MPN_E_UNSUPPORTED, nothing launched), but
+ * mpn_prn_scores and mpn_prn_scores_compact do not look at H*W themselves — the caller keeps occ / prn_out / score at the size it
+ * passes; and argmax[b][t] is defined only for a plane that holds a finite value or +inf: for a plane of nothing but -inf and NaN
+ * no element compares greater than the initial -inf and the value written is not an index of the plane.
  * -------------------------------------------------------------------------------------------*/
 int mpn_prn_build_maps(const double* peaks, const int32_t* joint_off, const double* boxes, const int32_t* box_img, int nboxes,
                        int H, int W, double in_thres, const double* weights9, int32_t* occ, float* prn_in, int32_t* err,
