@@ -8,9 +8,11 @@ refinement on a bicubically up-sampled 5x5 patch, running peak id).
 Pinning: `find_peaks` and `NMS(..., bool_refine_center=False)` are pinned bit-exactly to the REAL reference functions
 (tests/golden/g10_peaks.npz, made by tests/golden/make_golden_peaks.py; they use only numpy/scipy).  The refinement
 branch calls cv2.resize(INTER_CUBIC), and cv2 is not in this image: `cv_resize_cubic` below restates OpenCV's published
-algorithm (float32, A = -0.75, source x = (dx + 0.5)/f - 0.5, taps clamped to the patch) — that branch is
-PARITY UNPINNED until a box with cv2 regenerates the goldens (make_golden_peaks.py does it automatically when cv2
-imports).
+algorithm (float32, A = -0.75, source x = (dx + 0.5)/f - 0.5, taps clamped to the patch).  The restatement is pinned to an
+independent float64 implementation of the same rule (torch's CPU bicubic / bilinear, tests/postproc_ref.py) within bounds
+derived from the float32 roundings: tests/test_postproc_parity_cpu.py holds `cv_resize`, `cv_resize_cubic` and
+`nms_peaks(refine=True)` to it, and twelve modelled misreadings fail there.  Bit equality with a real cv2 build stays open
+until a box with cv2 regenerates g10_peaks.npz (make_golden_peaks.py does it automatically when cv2 imports).
 """
 import numpy as np
 
@@ -116,7 +118,8 @@ def cv_resize(img, out_hw, cubic, inv_scale=None):
     """cv2.resize(img, (out_w, out_h), interpolation=INTER_CUBIC | INTER_LINEAR) for a float32 [H, W, C] array, restated
     (evaluate/tester.py:67,213,296-299 call sites).  Source coordinate s = (d + 0.5) * (src/dst) - 0.5; cubic: taps
     floor(s)-1..floor(s)+2 clamped; linear: OpenCV clamps the coordinate (s < 0 -> 0, s >= n-1 -> n-1, weight 0).
-    Horizontal then vertical pass, float32 accumulation in tap order.  PARITY UNPINNED (cv2 is not in this image)."""
+    Horizontal then vertical pass, float32 accumulation in tap order.  Pinned to torch's float64 CPU resize within derived bounds
+    (tests/postproc_ref.py); bit equality with a real cv2 build stays open (cv2 is not in this image)."""
     img = np.asarray(img, dtype=np.float32)
     Hs, Ws, C = img.shape
     Hd, Wd = int(out_hw[0]), int(out_hw[1])
