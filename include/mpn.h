@@ -601,6 +601,24 @@ int mpn_heatmap_peaks(const float* heat, int64_t sB, int64_t sJ, int64_t sY, int
                       float thre1, double upsamp, int refine, double* peaks, int32_t* counts, int cap, void* workspace,
                       void* stream);
 
+/* mpn_heatmap_peaks with the reference's bool_gaussian_filt=True (joint_utils.py:115-116): the up-sampled float32 patch of every peak
+ * goes through scipy.ndimage.gaussian_filter before the arg-max, and the score is the SMOOTHED value at the first row-major maximum.
+ * taps: HOST pointer to the 2*radius + 1 float64 weights (scipy's _gaussian_kernel1d; sigma 3 -> radius 12, 25 weights); they are
+ * copied into the launch.  The smoothing, restated op for op:
+ *   - axis 0 (columns) first, then axis 1 (rows); each pass works line by line on values widened to float64;
+ *   - a line of n values is extended by `radius` at both ends with scipy's 'reflect' rule applied periodically: index i maps to
+ *     m = i mod 2n (non-negative), and m >= n maps to 2n - 1 - m — with n <= radius the extension wraps more than once;
+ *   - output l is  t = x[l]*w[radius];  then for k = radius, ..., 1:  t += (x[l-k] + x[l+k]) * w[radius-k]  in exactly this order,
+ *     float64, no contraction;
+ *   - one rounding to float32 at the end of each pass (the array between the passes is float32).
+ * Same workspace (mpn_heatmap_peaks_workspace_bytes), same flags and compaction launches; the third launch is the smoothed refinement
+ * kernel (one workgroup per peak, both planes in LDS).  With refine == 0 the taps are validated and the call is mpn_heatmap_peaks.
+ * MPN_E_BADARG before any HIP call for a null taps pointer, radius < 1 or > 16, or taps that are not bitwise symmetric;
+ * MPN_E_UNSUPPORTED when refine != 0 and rint(5 * upsamp) > 64 (the widest patch the LDS planes hold). */
+int mpn_heatmap_peaks_smooth(const float* heat, int64_t sB, int64_t sJ, int64_t sY, int64_t sX, int B, int J, int H, int W,
+                             float thre1, double upsamp, int refine, const double* taps, int radius, double* peaks,
+                             int32_t* counts, int cap, void* workspace, void* stream);
+
 /* cv2.resize for float32 images / heat-map stacks (evaluate/tester.py:67,213,296-299): src element (y, x, c) at
  * src[y*sY + x*sX + c*sC]; dst dense [Hd][Wd][C]; cubic != 0 -> INTER_CUBIC, else INTER_LINEAR (OpenCV's coordinate rule
  * (d + 0.5)*scale - 0.5, clamped taps, horizontal then vertical pass, float32).  scale = src/dst (the dsize call form) unless

@@ -6,6 +6,7 @@
 // The refinement restates cv2.resize(INTER_CUBIC) (float32, A = -0.75, s = (d + 0.5)/f - 0.5, taps clamped to the patch,
 // horizontal then vertical pass) op for op with oracle/joint_oracle.py; built with -ffp-contract=off.
 #include "common.h"
+#include <string.h>
 
 namespace {
 
@@ -288,6 +289,145 @@ __global__ void __launch_bounds__(PK_THREADS) peaks_refine_kernel(const float* _
     }
 }
 
+// ---- smoothed refinement: NMS(..., bool_gaussian_filt=True), joint_utils.py:115-116 ------------------------------------------
+// scipy.ndimage.gaussian_filter(map_upsamp, sigma) of the up-sampled float32 patch before the arg-max, restated op for op:
+// axis 0 then axis 1; per line the values widened to float64, both ends extended by the radius with the periodic 'reflect' rule
+// (i -> m = i mod 2n, m >= n -> 2n - 1 - m: a line shorter than the radius wraps more than once), correlate1d's symmetric sum
+//   t = x[l] w[R];  for k = R .. 1: t += (x[l - k] + x[l + k]) w[R - k]
+// in float64 without contraction, ONE rounding to float32 per pass (the plane between the passes is float32).
+// One WORKGROUP per list entry: the up-sampled patch and the axis-0 result are whole planes in LDS (2 x 16 KB at the widest factor), so
+// a wave-private slice for each of a block's four waves would hold a CU to one block = one wave per SIMD; with the block sharing one
+// pair of planes four blocks fit a CU (16 waves), and the 400 cells of the common 20 x 20 patch take two rounds of 256 threads instead of
+// seven of 64.  The price is a __syncthreads() between the phases.  The weights travel by value (scalar registers), indexed by distance.
+constexpr int PK_GAUSS_RMAX = 16;
+struct GaussW { double d[PK_GAUSS_RMAX + 1]; };               // d[k]: the weight at distance k from the centre (taps are symmetric)
+
+__device__ __forceinline__ int reflect_index(int i, int n) {
+    if (n < 1) return 0;
+    const int p = 2 * n;
+    int m = i % p;
+    if (m < 0) m += p;
+    return m >= n ? p - 1 - m : m;
+}
+
+// one output of a correlate1d line: `ext` points at the extension table entry of the output's own index, element i of the line is src[i * stride]
+__device__ __forceinline__ double gauss_line_sum(const float* __restrict__ src, int stride, const unsigned char* __restrict__ ext, const GaussW& g, int R) {
+    double t = (double)src[(int)ext[0] * stride] * g.d[0];
+    // enters the descending chain at k = R (one jump, no per-tap test); every weight index is a constant: scalar registers
+#define PK_GAUSS_TERM(k) case k: t = t + ((double)src[(int)ext[-k] * stride] + (double)src[(int)ext[k] * stride]) * g.d[k]; [[fallthrough]];
+    switch (R) {
+        PK_GAUSS_TERM(16) PK_GAUSS_TERM(15) PK_GAUSS_TERM(14) PK_GAUSS_TERM(13) PK_GAUSS_TERM(12) PK_GAUSS_TERM(11) PK_GAUSS_TERM(10) PK_GAUSS_TERM(9)
+        PK_GAUSS_TERM(8) PK_GAUSS_TERM(7) PK_GAUSS_TERM(6) PK_GAUSS_TERM(5) PK_GAUSS_TERM(4) PK_GAUSS_TERM(3) PK_GAUSS_TERM(2) PK_GAUSS_TERM(1)
+        default: break;
+    }
+#undef PK_GAUSS_TERM
+    static_assert(PK_GAUSS_RMAX == 16, "the chain above is written out for 16 distances");
+    return t;
+}
+
+#define PK_TO_VGPR(x) asm volatile("" : "+v"(x))
+// grid-stride over the work list, one workgroup per peak (refinement is on: the plain kernel serves refine == 0); 5 * f <= PK_ROW_W.
+__global__ void __launch_bounds__(PK_THREADS) peaks_refine_smooth_kernel(const float* __restrict__ heat, long sB, long sJ, long sY, long sX, int J, int H,
+                                                                          int W, double f, double* __restrict__ peaks, const int* __restrict__ counts,
+                                                                          int cap, const int* __restrict__ list, const int* __restrict__ list_n,
+                                                                          GaussW g, int R) {
+    // The 17 weights take 34 scalar registers for the whole launch.  What is only used in per-thread address arithmetic is moved to vector
+    // registers here (plentiful at this LDS-bound occupancy), so that no scalar register is spilled.
+    PK_TO_VGPR(sB); PK_TO_VGPR(sJ); PK_TO_VGPR(sY); PK_TO_VGPR(sX); PK_TO_VGPR(f); PK_TO_VGPR(J); PK_TO_VGPR(cap);
+    __shared__ float rows[5 * PK_ROW_W];                         // horizontal bicubic pass of the <= 5 source rows
+    __shared__ float up[PK_ROW_W * PK_ROW_W];                    // up-sampled patch, dense [dh][dw]
+    __shared__ float mid[PK_ROW_W * PK_ROW_W];                   // after the axis-0 Gaussian pass, dense [dh][dw]
+    __shared__ unsigned char exty[PK_ROW_W + 2 * PK_GAUSS_RMAX]; // reflected source index of line position i - R, per axis
+    __shared__ unsigned char extx[PK_ROW_W + 2 * PK_GAUSS_RMAX];
+    __shared__ float red_v[PK_THREADS / 64];
+    __shared__ int red_i[PK_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int n = *list_n;
+    for (int e = blockIdx.x; e < n; e += gridDim.x) {            // block-uniform: every barrier below is reached by all threads
+        const int entry = list[e];
+        const int plane = entry / cap, pk = entry - plane * cap;
+        const int b = plane / J, j = plane - b * J;
+        const float* __restrict__ m = heat + (long)b * sB + (long)j * sJ;
+        auto at = [&](int y, int x) { return m[(long)y * sY + (long)x * sX]; };
+        double* __restrict__ out = peaks + (long)plane * cap * 4;
+        const int px = (int)out[pk * 4 + 0], py = (int)out[pk * 4 + 1];          // read by all before thread 0 rewrites the row (barriers between)
+        int prefix = 0;                                          // ids run over the joint types of an image in order
+        for (int jj = lane; jj < j; jj += 64) prefix += counts[(long)b * J + jj];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) prefix += __shfl_xor(prefix, off);
+        const int x_min = px - 2 < 0 ? 0 : px - 2, y_min = py - 2 < 0 ? 0 : py - 2;
+        const int x_max = px + 2 > W - 1 ? W - 1 : px + 2, y_max = py + 2 > H - 1 ? H - 1 : py + 2;
+        const int sw = x_max - x_min + 1, sh = y_max - y_min + 1;
+        const int dw = (int)rint((double)sw * f), dh = (int)rint((double)sh * f);   // <= PK_ROW_W (checked by the entry point)
+        const double scale = 1.0 / f;
+        // horizontal bicubic pass (same products and sums as peaks_refine_kernel) and the two extension tables
+        for (int q = t; q < sh * dw; q += PK_THREADS) {
+            const int sy = q / dw, dx = q - sy * dw;
+            int xi[4]; float xc[4];
+            cubic_taps(dx, scale, sw, xi, xc);
+            const int yy = y_min + sy;
+            float a = at(yy, x_min + xi[0]) * xc[0];
+            a = a + at(yy, x_min + xi[1]) * xc[1];
+            a = a + at(yy, x_min + xi[2]) * xc[2];
+            a = a + at(yy, x_min + xi[3]) * xc[3];
+            rows[sy * PK_ROW_W + dx] = a;
+        }
+        for (int i = t; i < dh + 2 * R; i += PK_THREADS) exty[i] = (unsigned char)reflect_index(i - R, dh);
+        for (int i = t; i < dw + 2 * R; i += PK_THREADS) extx[i] = (unsigned char)reflect_index(i - R, dw);
+        __syncthreads();
+        // vertical bicubic pass: the whole up-sampled patch
+        for (int d = t; d < dh * dw; d += PK_THREADS) {
+            const int dy = d / dw, dx = d - dy * dw;
+            int yi[4]; float yc[4];
+            cubic_taps(dy, scale, sh, yi, yc);
+            float v = rows[yi[0] * PK_ROW_W + dx] * yc[0];
+            v = v + rows[yi[1] * PK_ROW_W + dx] * yc[1];
+            v = v + rows[yi[2] * PK_ROW_W + dx] * yc[2];
+            v = v + rows[yi[3] * PK_ROW_W + dx] * yc[3];
+            up[d] = v;
+        }
+        __syncthreads();
+        // Gaussian along axis 0 (columns)
+        for (int d = t; d < dh * dw; d += PK_THREADS) {
+            const int dy = d / dw, dx = d - dy * dw;
+            mid[d] = (float)gauss_line_sum(up + dx, dw, exty + R + dy, g, R);
+        }
+        __syncthreads();
+        // Gaussian along axis 1 (rows), fused with the first-maximum search: the smoothed plane is never stored
+        float best = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int d = t; d < dh * dw; d += PK_THREADS) {
+            const int dy = d / dw, dx = d - dy * dw;
+            const float v = (float)gauss_line_sum(mid + dy * dw, 1, extx + R + dx, g, R);
+            if (v > best) { best = v; bi = d; }                  // d ascends per thread: keeps the thread's first maximum
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {                 // first maximum in row-major order = (max value, min index)
+            const float ov = __shfl_xor(best, off);
+            const int oi = __shfl_xor(bi, off);
+            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+        }
+        if (lane == 0) { red_v[wave] = best; red_i[wave] = bi; }
+        __syncthreads();                                         // also: every read of this peak's planes and tables is done
+        if (t == 0) {
+#pragma unroll
+            for (int w = 1; w < PK_THREADS / 64; ++w) {
+                const float ov = red_v[w];
+                const int oi = red_i[w];
+                if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+            }
+            const int by = bi / dw, bx = bi - by * dw;
+            const double cy = ((double)(py - y_min) + 0.5) * f - 0.5, cx = ((double)(px - x_min) + 0.5) * f - 0.5;
+            const double ry = (double)by - cy, rx = (double)bx - cx;
+            out[pk * 4 + 0] = rint((((double)px + 0.5) * f - 0.5) + rx);
+            out[pk * 4 + 1] = rint((((double)py + 0.5) * f - 0.5) + ry);
+            out[pk * 4 + 2] = (double)best;
+            out[pk * 4 + 3] = (double)(prefix + pk);
+        }
+        // red_v / red_i are next written three barriers on; rows / up / mid / ext* of the next peak are written only after the barrier above
+    }
+}
+
 // cv2.resize of a float32 [Hs, Ws, C] image to [Hd, Wd, C] (evaluate/tester.py:67,213,296-299): INTER_CUBIC (cubic != 0: A = -0.75,
 // four clamped taps per axis) or INTER_LINEAR (two taps; source coordinate clamped as OpenCV does), horizontal pass then
 // vertical pass, float32, left-to-right sums.  One thread per destination element.
@@ -344,9 +484,9 @@ extern "C" int64_t mpn_heatmap_peaks_workspace_bytes(int B, int J, int H, int W,
     return pk_align((int64_t)B * J * H * wpr * 8) + pk_align((int64_t)B * J * cap * 4) + 256;
 }
 
-extern "C" int mpn_heatmap_peaks(const float* heat, int64_t sB, int64_t sJ, int64_t sY, int64_t sX, int B, int J, int H, int W,
-                                 float thre1, double upsamp, int refine, double* peaks, int32_t* counts, int cap, void* workspace,
-                                 void* stream) {
+// the three launches of both entry points; gw != nullptr: the smoothed refinement kernel takes the third
+static int peaks_launch(const float* heat, int64_t sB, int64_t sJ, int64_t sY, int64_t sX, int B, int J, int H, int W, float thre1, double upsamp,
+                        int refine, double* peaks, int32_t* counts, int cap, void* workspace, void* stream, const GaussW* gw, int radius) {
     MPN_CHECK_ARG(heat && peaks && counts && workspace && B > 0 && J > 0 && H > 0 && W > 0 && cap > 0 && upsamp > 0.0);
     MPN_CHECK_ARG((long)H * W < 0x7fffffffL && (long)B * J * cap < 0x7fffffffL && B <= 65535 && J <= 65535);
     const int wpr = (W + 63) / 64;
@@ -372,9 +512,39 @@ extern "C" int mpn_heatmap_peaks(const float* heat, int64_t sB, int64_t sJ, int6
     // enough waves to fill the chip on a dense (noise) workload; idle waves of a sparse one read the list length and leave
     long want = ((long)B * J * (cap < 16 ? cap : 16) + PK_THREADS / 64 - 1) / (PK_THREADS / 64);
     const unsigned grid = (unsigned)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+    if (gw) {
+        // one workgroup per peak (not one wave): four times the blocks for the same number of peaks in flight
+        want = (long)B * J * (cap < 16 ? cap : 16);
+        const unsigned sgrid = (unsigned)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+        hipLaunchKernelGGL(peaks_refine_smooth_kernel, dim3(sgrid), dim3(PK_THREADS), 0, st, heat, (long)sB, (long)sJ, (long)sY, (long)sX, J, H, W, upsamp,
+                           peaks, (const int*)counts, cap, (const int*)list, (const int*)list_n, *gw, radius);
+        return mpn_launch_status();
+    }
     hipLaunchKernelGGL(peaks_refine_kernel, dim3(grid), dim3(PK_THREADS), 0, st, heat, (long)sB, (long)sJ, (long)sY, (long)sX, J, H, W, upsamp, refine,
                        peaks, (const int*)counts, cap, (const int*)list, (const int*)list_n);
     return mpn_launch_status();
+}
+
+extern "C" int mpn_heatmap_peaks(const float* heat, int64_t sB, int64_t sJ, int64_t sY, int64_t sX, int B, int J, int H, int W,
+                                 float thre1, double upsamp, int refine, double* peaks, int32_t* counts, int cap, void* workspace,
+                                 void* stream) {
+    return peaks_launch(heat, sB, sJ, sY, sX, B, J, H, W, thre1, upsamp, refine, peaks, counts, cap, workspace, stream, nullptr, 0);
+}
+
+extern "C" int mpn_heatmap_peaks_smooth(const float* heat, int64_t sB, int64_t sJ, int64_t sY, int64_t sX, int B, int J, int H, int W,
+                                        float thre1, double upsamp, int refine, const double* taps, int radius, double* peaks, int32_t* counts,
+                                        int cap, void* workspace, void* stream) {
+    MPN_CHECK_ARG(taps && radius >= 1 && radius <= PK_GAUSS_RMAX);
+    GaussW gw;
+    for (int k = 0; k <= PK_GAUSS_RMAX; ++k) gw.d[k] = 0.0;
+    for (int k = 0; k <= radius; ++k) {
+        MPN_CHECK_ARG(memcmp(&taps[radius - k], &taps[radius + k], sizeof(double)) == 0);       // bitwise symmetric
+        gw.d[k] = taps[radius - k];
+    }
+    MPN_CHECK_ARG(heat && peaks && counts && workspace && B > 0 && J > 0 && H > 0 && W > 0 && cap > 0 && upsamp > 0.0);
+    if (!refine) return peaks_launch(heat, sB, sJ, sY, sX, B, J, H, W, thre1, upsamp, 0, peaks, counts, cap, workspace, stream, nullptr, 0);
+    if (!(rint(5.0 * upsamp) <= (double)PK_ROW_W)) return MPN_E_UNSUPPORTED;                      // the LDS planes hold PK_ROW_W x PK_ROW_W cells
+    return peaks_launch(heat, sB, sJ, sY, sX, B, J, H, W, thre1, upsamp, 1, peaks, counts, cap, workspace, stream, &gw, radius);
 }
 
 extern "C" int mpn_resize(const float* src, int64_t sY, int64_t sX, int64_t sC, int Hs, int Ws, int C, float* dst, int Hd, int Wd,

@@ -53,6 +53,7 @@ class TestParams(object):
     subnet_name = 'keypoint_subnet'
     batch_size = 32
     print_freq = 20
+    gaussian_filt = False             # NMS(..., bool_gaussian_filt=True): smooth every up-sampled peak patch (sigma 3) before its arg-max
 
 
 def resize(img, out_hw, cubic, inv_scale=None):
@@ -212,7 +213,7 @@ class Tester(object):
         with torch.no_grad():
             heatmaps, (scores, classification, transformed_anchors) = self.model([img_input, 'both'])
         param = {'thre1': 0.1, 'thre2': 0.05, 'thre3': 0.5}
-        joint_list = get_joint_list(img_resized, param, heatmaps[0].permute(1, 2, 0), scale)
+        joint_list = get_joint_list(img_resized, param, heatmaps[0].permute(1, 2, 0), scale, bool_gaussian_filt=self.params.gaussian_filt)
         bboxs = self._boxes(scores, classification, transformed_anchors, scale)
         return self.prn_process(self._body_joints(joint_list), bboxs, file_name, image_id)
 
@@ -283,7 +284,7 @@ class Tester(object):
         multi = cls.shape[-1] > 1
         det = self.model.detect_padded(anchors, cls, return_class=multi)
         boxes, scores, kept = det[:3]
-        pk, cnt = NMS_batch_arrays({'thre1': 0.1}, heat, float(S) / heat.shape[2])
+        pk, cnt = NMS_batch_arrays({'thre1': 0.1}, heat, float(S) / heat.shape[2], bool_gaussian_filt=self.params.gaussian_filt)
         peaks_xy, joint_off = body_peaks_flat(pk, cnt)
         sc = np.asarray(scales)
         per_img = np.diff(np.concatenate([joint_off[:, 0], joint_off[-1:, 17]]))          # peaks per image
@@ -386,6 +387,9 @@ class Tester(object):
         return (normal_heat + flipped_heat.flip(1)[:, :, SWAP_HEAT]) / 2.
 
     def infer_image_multiscale(self, img, file_name='', image_id=0):
+        """tester.py:143-175 for one image.  The float64 averaged maps are rounded to float32 once before the peak kernel; with
+        ``params.gaussian_filt`` the smoothing then follows the float32 semantics of ``NMS`` (float32 up-sampled patch, float64 sums,
+        one float32 rounding per axis), where the reference would filter a float64 patch."""
         img = _to_device_image(img, self.dev)
         multiplier = self._get_multiplier(img)
         orig_heat, orig_bbox_all = self._get_outputs(multiplier, img)
@@ -394,7 +398,7 @@ class Tester(object):
         param = {'thre1': 0.1, 'thre2': 0.05, 'thre3': 0.5}
         # the averaged maps are float64 as in the reference (np.zeros accumulator); the peak kernel takes float32, so they are
         # rounded ONCE here (the reference's find_peaks / cv2 refinement run on the float64 maps: a <= 1 ulp(f32) deviation)
-        joint_list = get_joint_list(img, param, heatmaps[:, :, :18].float().contiguous(), 1)
+        joint_list = get_joint_list(img, param, heatmaps[:, :, :18].float().contiguous(), 1, bool_gaussian_filt=self.params.gaussian_filt)
         results = self.prn_process(self._body_joints(joint_list), orig_bbox_all[1], file_name, image_id)
         for result in results:                                    # tester.py:167-175: COCO keypoint order
             kp = result['keypoints']
