@@ -663,6 +663,47 @@ int mpn_prn_match_host(int nimg, const int32_t* box_start, const double* boxes, 
                        const int32_t* cand_n, const int32_t* cand_id, const float* cand_score, int cap, const int32_t* argmax,
                        int H, int W, double* out_kp, uint8_t* tie_flags);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO keypoint AP / AR on the device (evaluate/tester.py:179-186: COCOeval(coco, res, 'keypoints') evaluate + accumulate; the
+ * published algorithm restated, pycocotools is not linked).  All arithmetic float64.  Every pointer is a device pointer except
+ * img_tab_host; doubles 8-byte aligned.  The caller builds the constant tables with numpy and passes them in: var [17] =
+ * (2 sigma)^2, area_rng [n_area][2] (inclusive bounds), iou_thrs [n_thr], rec_thrs [n_rec].
+ *
+ * Images are described by img_tab [n_img + 1][4] int64, row i = (first detection, first ground truth, first kept detection,
+ * first OKS element) of image i in ascending image-id order, row n_img = the totals (D, G, K, size of oks).  img_tab_host is the
+ * same table in host memory: it is validated before any HIP call (row 0 zero, rows ascending, kept = min(detections, max_dets),
+ * OKS block = kept x ground truths) and must equal the device copy the kernels read.
+ *   det_kp [D][17][3] (x, y, anything), det_score [D] (finite): an image's detections in input order;
+ *   gt_kp [G][17][3] (x, y, visibility), gt_area [G], gt_bbox [G][4] (x, y, w, h), gt_flags [G]: bit 0 = ignored (iscrowd or
+ *   num_keypoints == 0), bit 1 = iscrowd.
+ * mpn_oks_matrix (one launch, one workgroup per image): per image the stable descending-score order (ties: lower input index
+ *   first) truncated to max_dets -> kept_src [K] (index into the D detections), kept_score [K], kept_area [K] = (max x - min x) *
+ *   (max y - min y) over the detection's own 17 joints; oks [kept x G block per image, row-major, at the table's offsets] =
+ *   mean over the joints with visibility > 0 of exp(-(dx^2 + dy^2) / var / (area + 2^-52) / 2), or, for a ground truth without a
+ *   visible joint, over all 17 with dx, dy the distances to its box doubled about its centre.
+ * mpn_oks_match (one launch, one wave per image x area range x threshold): COCOeval.evaluateImg.  gt_ig [n_area][G] = ignored or
+ *   area outside [lo, hi]; det_match [n_area][n_thr][K] = matched ground truth (index into G) or -1; det_ig [n_area][n_thr][K] =
+ *   the matched ground truth's ignore flag, or for an unmatched detection "own area outside [lo, hi]"; gt_match
+ *   [n_area][n_thr][G] = the last kept detection (index into K) matched to the ground truth, or -1.
+ * mpn_oks_accumulate (two launches): COCOeval.accumulate.  order [K] = kept detections in the stable descending-score order over
+ *   all images (a rank sort: K^2 compares, no scratch); precision [n_thr][n_rec][n_area] and recall [n_thr][n_area], -1 where an
+ *   area range has no non-ignored ground truth.  workspace: mpn_oks_eval_workspace_bytes(K, n_area, n_thr) bytes, contents need no
+ *   initialisation.
+ * MPN_E_BADARG before any HIP call: null pointer, n_img <= 0, max_dets outside 1..128, n_area outside 1..8, n_thr outside 1..64,
+ * n_rec outside 1..4096, negative totals, a misaligned double array, a table that fails the checks above.
+ * -------------------------------------------------------------------------------------------*/
+int64_t mpn_oks_eval_workspace_bytes(int64_t n_kept, int n_area, int n_thr);
+int mpn_oks_matrix(const double* det_kp, const double* det_score, const double* gt_kp, const double* gt_area,
+                   const double* gt_bbox, const int64_t* img_tab_host, const int64_t* img_tab, int n_img, int max_dets,
+                   const double* var, int32_t* kept_src, double* kept_score, double* kept_area, double* oks, void* stream);
+int mpn_oks_match(const double* oks, const double* kept_area, const double* gt_area, const int32_t* gt_flags,
+                  const int64_t* img_tab_host, const int64_t* img_tab, int n_img, int max_dets, const double* area_rng,
+                  int n_area, const double* iou_thrs, int n_thr, int32_t* det_match, int32_t* det_ig, int32_t* gt_ig,
+                  int32_t* gt_match, void* stream);
+int mpn_oks_accumulate(const double* kept_score, const int32_t* det_match, const int32_t* det_ig, const int32_t* gt_ig,
+                       int64_t n_kept, int64_t n_gt, int n_area, int n_thr, const double* rec_thrs, int n_rec,
+                       int32_t* order, double* precision, double* recall, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,7 @@ class Tester(object):
         self.val_data = val_data
         self.batch_processor = batch_processor
         self.model = model
+        self.last_eval = None             # coco_eval(..., annotations=...): the KeypointEval result dict
         if self.params.ckpt is not None:
             self._load_ckpt(self.params.ckpt)
             logger.info('Load ckpt from {}'.format(self.params.ckpt))
@@ -328,13 +329,15 @@ class Tester(object):
                 json.dump(out, f)
         return out
 
-    def coco_eval(self, images, coco=None):
+    def coco_eval(self, images, coco=None, annotations=None):
         """tester.py:131-191 from the decoded images on: ``images`` yields (image_id, file_name, [H, W, 3] BGR array) — what the
         reference reads with pycocotools + cv2.imread.  Every image runs the 5-scale, flipped test-time augmentation; the results
         (keypoints in COCO order) are written to ``params.coco_result_filename`` (indent 4, :176-178).  With pycocotools present
         and ``coco`` the loaded annotation object, the keypoint evaluation runs as in :179-186 and the file is removed unless
         ``params.testresult_write_json`` (:188-189); without it (this image has none) the file is the product and is kept.
-        Returns the result list."""
+        With ``annotations`` (the annotation json's ``annotations`` list, what PRNSampleSet takes) the evaluation of :179-186 runs on
+        the device instead (oks_eval.KeypointEval over the evaluated image ids): the ten COCO lines are logged, the result dict is
+        kept in ``self.last_eval`` and the file is removed unless ``params.testresult_write_json``.  Returns the result list."""
         results, img_ids = [], []
         for image_id, file_name, img in images:
             img_ids.append(image_id)
@@ -342,6 +345,14 @@ class Tester(object):
         ann_filename = self.params.coco_result_filename
         with open(ann_filename, "w") as f:
             json.dump(results, f, indent=4)
+        if annotations is not None:
+            from .oks_eval import KeypointEval
+            ev = KeypointEval(annotations)
+            self.last_eval = ev.evaluate(results, img_ids=img_ids)
+            ev.summarize()
+            if not self.params.testresult_write_json:
+                os.remove(ann_filename)
+            return results
         if coco is not None:
             try:
                 from pycocotools.cocoeval import COCOeval

@@ -1068,3 +1068,54 @@ def score_filter(boxes0, scores0, thresh):
     call("mpn_score_filter", ptr(boxes0), ptr(scores0), A, float(thresh), ptr(dets), ptr(src), ptr(cnt), stream_ptr())
     n = int(cnt.item())
     return dets[:n], src[:n]
+
+
+# ---------------------------------------------------------------- keypoint AP / AR (csrc/oks_eval.hip; evaluate/oks_eval.py packs the arrays)
+def oks_matrix(det_kp, det_score, gt_kp, gt_area, gt_bbox, tab_host, tab, max_dets, var):
+    """Stage 1: (kept_src i32 [K], kept_score [K], kept_area [K], oks [sum kept x G]).  tab_host: contiguous int64 numpy
+    [n_img + 1, 4]; tab: the same table on the device."""
+    check_device(tab)
+    dev = tab.device
+    n_img = tab_host.shape[0] - 1
+    K, n_oks = int(tab_host[-1, 2]), int(tab_host[-1, 3])
+    kept_src = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)
+    kept_score = torch.empty((max(K, 1),), dtype=torch.float64, device=dev)
+    kept_area = torch.empty((max(K, 1),), dtype=torch.float64, device=dev)
+    oks = torch.empty((max(n_oks, 1),), dtype=torch.float64, device=dev)
+    call("mpn_oks_matrix", ptr(det_kp), ptr(det_score), ptr(gt_kp), ptr(gt_area), ptr(gt_bbox), ctypes.c_void_p(tab_host.ctypes.data),
+         ptr(tab), n_img, int(max_dets), ptr(var), ptr(kept_src), ptr(kept_score), ptr(kept_area), ptr(oks), stream_ptr())
+    return kept_src[:K], kept_score[:K], kept_area[:K], oks[:n_oks]
+
+
+def oks_match(oks, kept_area, gt_area, gt_flags, tab_host, tab, max_dets, area_rng, iou_thrs):
+    """Stage 2: (det_match [A, T, K], det_ig [A, T, K], gt_ig [A, G], gt_match [A, T, G]), int32."""
+    check_device(tab)
+    dev = tab.device
+    n_img = tab_host.shape[0] - 1
+    G, K = int(tab_host[-1, 1]), int(tab_host[-1, 2])
+    A, T = area_rng.shape[0], iou_thrs.numel()
+    det_match = torch.empty((A, T, K), dtype=torch.int32, device=dev)
+    det_ig = torch.empty((A, T, K), dtype=torch.int32, device=dev)
+    gt_ig = torch.empty((A, G), dtype=torch.int32, device=dev)
+    gt_match = torch.empty((A, T, G), dtype=torch.int32, device=dev)
+    one = torch.empty((1,), dtype=torch.int32, device=dev)       # an empty tensor has no address to hand over
+    p = lambda t: ptr(t) if t.numel() else ptr(one)
+    call("mpn_oks_match", p(oks), p(kept_area), ptr(gt_area), ptr(gt_flags), ctypes.c_void_p(tab_host.ctypes.data), ptr(tab), n_img,
+         int(max_dets), ptr(area_rng), A, ptr(iou_thrs), T, p(det_match), p(det_ig), p(gt_ig), p(gt_match), stream_ptr())
+    return det_match, det_ig, gt_ig, gt_match
+
+
+def oks_accumulate(kept_score, det_match, det_ig, gt_ig, rec_thrs, out):
+    """Stage 3: fills out = float64 [T*R*A + T*A] (precision [T, R, A] then recall [T, A]) and returns the order [K] of the stable
+    descending-score sort over all images."""
+    check_device(out)
+    dev = out.device
+    A, T, K = det_match.shape
+    G, R = gt_ig.shape[1], rec_thrs.numel()
+    order = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)
+    ws = workspace(call("mpn_oks_eval_workspace_bytes", K, A, T), dev, slot=9)
+    one = torch.empty((2,), dtype=torch.float64, device=dev)
+    p = lambda t: ptr(t) if t.numel() else ptr(one)
+    call("mpn_oks_accumulate", p(kept_score), p(det_match), p(det_ig), p(gt_ig), K, G, A, T, ptr(rec_thrs), R, ptr(order), ptr(out),
+         ctypes.c_void_p(out.data_ptr() + 8 * T * R * A), ptr(ws), stream_ptr())
+    return order[:K]
