@@ -509,12 +509,11 @@ class Engine(object):
         if want_dy:
             ctx.set_grad(y, dy)
 
-    def dropout(self, ctx, x, p):
-        """nn.Dropout in training mode (posenet.py:139,341-342): counter-based mask, regenerated in backward."""
-        self._drop_calls += 1
-        seed = (torch.initial_seed() * 1000003 + self._drop_calls) & 0xFFFFFFFFFFFFFFFF
+    def _dropout(self, ctx, x, launch):
+        """Body of both dropouts: ``launch(src, dst)`` applies the call's mask — to the activation now, to its gradient in backward
+        (counter-based, so the mask is regenerated, not stored)."""
         y = Act(torch.empty_like(x.t), x.C)
-        call("mpn_dropout", ops.ptr(x.t), ops.ptr(y.t), x.t.numel(), seed, float(p), ops.dtype_code(x.t.dtype), ops.stream_ptr())
+        launch(x.t, y.t)
         if ctx.train and x.needs_grad:
             y.needs_grad = True
 
@@ -523,10 +522,17 @@ class Engine(object):
                 if dy is None:
                     return
                 g = Act(torch.empty_like(dy.t), x.C)
-                call("mpn_dropout", ops.ptr(dy.t), ops.ptr(g.t), dy.t.numel(), seed, float(p), ops.dtype_code(dy.t.dtype), ops.stream_ptr())
+                launch(dy.t, g.t)
                 ctx.set_grad(x, g)
             ctx.tape.append(bwd)
         return y
+
+    def dropout(self, ctx, x, p):
+        """nn.Dropout in training mode (posenet.py:139,341-342): counter-based mask, regenerated in backward."""
+        self._drop_calls += 1
+        seed = (torch.initial_seed() * 1000003 + self._drop_calls) & 0xFFFFFFFFFFFFFFFF
+        return self._dropout(ctx, x, lambda s, d: call("mpn_dropout", ops.ptr(s), ops.ptr(d), s.numel(), seed, float(p),
+                                                       ops.dtype_code(s.dtype), ops.stream_ptr()))
 
     # ---- dropout of a recorded step: the seed comes from a device word, so the launch list draws new masks on every replay
     def begin_drop_step(self, device, d):
@@ -546,20 +552,8 @@ class Engine(object):
     def dropout_dev(self, ctx, x, p, k):
         """``dropout`` with seed = device word + k (mpn_dropout_dev): the k-th dropout of a step begun with begin_drop_step."""
         st = self._drop_state
-        y = Act(torch.empty_like(x.t), x.C)
-        call("mpn_dropout_dev", ops.ptr(x.t), ops.ptr(y.t), x.t.numel(), ops.ptr(st), k, float(p), ops.dtype_code(x.t.dtype), ops.stream_ptr())
-        if ctx.train and x.needs_grad:
-            y.needs_grad = True
-
-            def bwd():
-                dy = ctx.pop_grad(y)
-                if dy is None:
-                    return
-                g = Act(torch.empty_like(dy.t), x.C)
-                call("mpn_dropout_dev", ops.ptr(dy.t), ops.ptr(g.t), dy.t.numel(), ops.ptr(st), k, float(p), ops.dtype_code(dy.t.dtype), ops.stream_ptr())
-                ctx.set_grad(x, g)
-            ctx.tape.append(bwd)
-        return y
+        return self._dropout(ctx, x, lambda s, d: call("mpn_dropout_dev", ops.ptr(s), ops.ptr(d), s.numel(), ops.ptr(st), k, float(p),
+                                                       ops.dtype_code(s.dtype), ops.stream_ptr()))
 
     def end_drop_step(self, d):
         """Last launch of the step (after the update, main stream): the device word moves on by the step's ``d`` dropouts."""

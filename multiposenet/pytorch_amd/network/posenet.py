@@ -349,15 +349,7 @@ class poseNet(nn.Module):
         while the GPU still runs, so a serving loop can post-process the previous batch meanwhile (evaluate/tester.py:
         infer_images_batched).  Returns (heat-maps, decoded boxes [B,A,4], class scores [B,A,K], keep-alive): hold on to the last item
         until this batch's results have been read (it owns tensors that side-stream launches of this forward still use)."""
-        self._prepare(img_batch)
-        eng = self._engine
-        ctx = Ctx(False)
-        c2, c3, c4, c5 = eng.backbone(ctx, img_batch)
-        kp = eng.kp_pyramid(ctx, c2, c3, c4, c5)
-        det = eng.det_pyramid(ctx, c3, c4, c5)
-        predict_keypoint, _ = eng.keypoint_head(ctx, kp, False)
-        classification, regression = eng.detection_head(ctx, det)
-        self._finish_forward(ctx)
+        ctx, _, (predict_keypoint, _, classification, regression) = self._run_net(img_batch, False)
         transformed_anchors = decode_and_clip(self.anchors(img_batch), regression, img_batch)
         return predict_keypoint, transformed_anchors, classification, (ctx, regression)
 
@@ -377,108 +369,104 @@ class poseNet(nn.Module):
         return out if return_class else out[:3]
 
     def _entire_net(self, img_batch, all_images):
-        self._prepare(img_batch)
-        eng = self._engine
-        ctx = Ctx(False)
-        c2, c3, c4, c5 = eng.backbone(ctx, img_batch)
-        kp = eng.kp_pyramid(ctx, c2, c3, c4, c5)
-        det = eng.det_pyramid(ctx, c3, c4, c5)
-        predict_keypoint, _ = eng.keypoint_head(ctx, kp, False)
-        classification, regression = eng.detection_head(ctx, det)
-        self._finish_forward(ctx)
-        anchors = self.anchors(img_batch)
-        transformed_anchors = decode_and_clip(anchors, regression, img_batch)
-        results = []
-        K = classification.shape[2]
+        predict_keypoint, transformed_anchors, classification, _keep = self.forward_padded_begin(img_batch)
+        B, K = classification.shape[0], classification.shape[2]
         if K > 1:
             # posenet.py:267: scores = max over the classes (image 0 alone feeds 'both'); the arg-max (:283) is gathered for the kept
             # anchors only
             score, cls_id = ops.class_max(classification if all_images else classification[:1])
-        if all_images and K > 1:
-            dets = ops.detect_batched(transformed_anchors, score, 0.05, 0.5, cls_id=cls_id)
-            for boxes, nms_scores, nms_class in dets:
-                if boxes is None:
-                    results.append([torch.zeros(0), torch.zeros(0), torch.zeros(0, 4)])      # posenet.py:273-275 (CPU empties)
-                else:
-                    results.append([nms_scores, nms_class, boxes])
-            return predict_keypoint, results
-        if all_images:
-            # every image thresholded (posenet.py:269-271), NMS'd (:281) and gathered (:283-285) by batch-wide launches;
-            # sizes stay on the device between the stages (ops.detect_batched: two host reads per BATCH)
-            cls2 = classification.reshape(classification.shape[0], -1)
-            dets = ops.detect_batched(transformed_anchors, cls2, 0.05, 0.5)
-            # single class: the arg-max class of every detection (posenet.py:283) is 0 — ONE zero vector for the batch, a view per image
-            most = max([b.shape[0] for b, _ in dets if b is not None], default=0)
-            zeros = torch.zeros(most, dtype=torch.int64, device=img_batch.device) if most else None
-            for boxes, nms_scores in dets:
-                if boxes is None:
-                    results.append([torch.zeros(0), torch.zeros(0), torch.zeros(0, 4)])      # posenet.py:273-275 (CPU empties)
-                else:
-                    results.append([nms_scores, zeros[: nms_scores.shape[0]], boxes])
-            return predict_keypoint, results
-        for b in range(1):
-            # posenet.py:269-275: score > 0.05, early-out with the CPU empty triple
-            dets, src = ops.score_filter(transformed_anchors[b], classification[b, :, 0] if K == 1 else score[b], 0.05)
+        else:
+            score, cls_id = classification.reshape(B, -1), None
+        if not all_images:
+            # image 0 with the reference's own sequence.  posenet.py:269-275: score > 0.05, early-out with the CPU empty triple
+            dets, src = ops.score_filter(transformed_anchors[0], score[0], 0.05)
             if dets.shape[0] == 0:
-                results.append([torch.zeros(0), torch.zeros(0), torch.zeros(0, 4)])
-                continue
+                return predict_keypoint, [[torch.zeros(0), torch.zeros(0), torch.zeros(0, 4)]]
             anchors_nms_idx = nms(dets, 0.5)
             boxes, nms_scores = ops.gather_dets(dets, anchors_nms_idx)
             if K == 1:
                 nms_class = torch.zeros(nms_scores.shape[0], dtype=torch.int64, device=nms_scores.device)   # single class
             else:
-                nms_class = ops.gather_class(cls_id[b], src, anchors_nms_idx)
-            results.append([nms_scores, nms_class, boxes])
+                nms_class = ops.gather_class(cls_id[0], src, anchors_nms_idx)
+            return predict_keypoint, [[nms_scores, nms_class, boxes]]
+        # every image thresholded (posenet.py:269-271), NMS'd (:281) and gathered (:283-285) by batch-wide launches;
+        # sizes stay on the device between the stages (ops.detect_batched: two host reads per BATCH)
+        dets = ops.detect_batched(transformed_anchors, score, 0.05, 0.5, cls_id=cls_id)
+        if K == 1:
+            # single class: the arg-max class of every detection (posenet.py:283) is 0 — ONE zero vector for the batch, a view per image
+            most = max([d[0].shape[0] for d in dets if d[0] is not None], default=0)
+            zeros = torch.zeros(most, dtype=torch.int64, device=img_batch.device) if most else None
+        results = []
+        for boxes, nms_scores, *nms_class in dets:
+            if boxes is None:
+                results.append([torch.zeros(0), torch.zeros(0), torch.zeros(0, 4)])      # posenet.py:273-275 (CPU empties)
+            else:
+                results.append([nms_scores, nms_class[0] if K > 1 else zeros[: nms_scores.shape[0]], boxes])
         return predict_keypoint, results
+
+    def _features(self, img_batch, tape, kp=True, det=True):
+        """First step of every network pass: operand refresh, a new Ctx (``tape``: keep the reverse tape), the backbone, then the
+        pyramids asked for — keypoint before detection.  -> (ctx, kp_feats, det_feats), None for a pyramid that did not run."""
+        self._prepare(img_batch)
+        eng = self._engine
+        ctx = Ctx(tape)
+        c2, c3, c4, c5 = eng.backbone(ctx, img_batch)
+        kp_feats = eng.kp_pyramid(ctx, c2, c3, c4, c5) if kp else None
+        det_feats = eng.det_pyramid(ctx, c3, c4, c5) if det else None
+        return ctx, kp_feats, det_feats
+
+    def _heads(self, ctx, kp_feats, det_feats, intermediate=False, internal=False):
+        """Second step: the keypoint head, then the detection head, each over its pyramid (None: not run), then _finish_forward.
+        -> (pred, [k2..k5] when ``intermediate``, classification, regression); ``internal``: Engine.keypoint_head."""
+        eng = self._engine
+        pred, saved = eng.keypoint_head(ctx, kp_feats, intermediate, internal=internal) if kp_feats is not None else (None, [])
+        cls, reg = eng.detection_head(ctx, det_feats) if det_feats is not None else (None, None)
+        self._finish_forward(ctx)
+        return pred, saved, cls, reg
+
+    def _run_net(self, img_batch, tape, kp=True, det=True, heads=True, intermediate=False):
+        """THE forward composition: the only place that fixes the order of the engine's pieces (the reverse tape, the order in which
+        gradients accumulate into the shared feature maps and what runs on the side stream all follow it).  The recorded step
+        (replay.py) calls its two steps itself, because it chooses ``internal`` from the pyramid's geometry in between.
+        -> (ctx, (kp_feats, det_feats), (pred, saved, classification, regression))."""
+        ctx, kp_feats, det_feats = self._features(img_batch, tape, kp, det)
+        outs = self._heads(ctx, kp_feats if heads else None, det_feats if heads else None, intermediate)
+        return ctx, (kp_feats, det_feats), outs
 
     def keypoint_forward(self, img_batch):
         """posenet.py:288-318 -> (pred [B,18,H/4,W/4], [k2,k3,k4,k5 ([B,19,...]), pred])."""
-        self._prepare(img_batch)
-        eng = self._engine
-        ctx = Ctx(self._want_tape())
-        c2, c3, c4, c5 = eng.backbone(ctx, img_batch)
-        kp = eng.kp_pyramid(ctx, c2, c3, c4, c5)       # the unused detection pyramid (fpn.py:107-114) is skipped
-        pred, saved = eng.keypoint_head(ctx, kp, True)
-        self._finish_forward(ctx)
+        # the unused detection pyramid (fpn.py:107-114) is skipped
+        ctx, _, (pred, saved, _, _) = self._run_net(img_batch, self._want_tape(), det=False, intermediate=True)
         outs = self._wrap(ctx, ["k0", "k1", "k2", "k3", "pred"], saved + [pred])
         return outs[4], outs
 
     def detection_forward(self, img_batch):
         """posenet.py:320-335 -> ([], [classification [B,A,K], regression [B,A,4], anchors [1,A,4]])."""
-        self._prepare(img_batch)
-        eng = self._engine
-        ctx = Ctx(self._want_tape())
-        c2, c3, c4, c5 = eng.backbone(ctx, img_batch)
-        det = eng.det_pyramid(ctx, c3, c4, c5)
-        cls, reg = eng.detection_head(ctx, det)
-        self._finish_forward(ctx)
+        ctx, _, (_, _, cls, reg) = self._run_net(img_batch, self._want_tape(), kp=False)
         cls, reg = self._wrap(ctx, ["cls", "reg"], [cls, reg])
         return [], [cls, reg, self.anchors(img_batch)]
 
     def train_both_forward(self, img_batch):
         """SURVEY.md 8d combined step: shared backbone, both pyramids + heads.
         -> (pred, (saved_for_keypoint_loss, saved_for_detection_loss))."""
-        self._prepare(img_batch)
-        eng = self._engine
-        ctx = Ctx(self._want_tape())
-        c2, c3, c4, c5 = eng.backbone(ctx, img_batch)
-        kp = eng.kp_pyramid(ctx, c2, c3, c4, c5)
-        det = eng.det_pyramid(ctx, c3, c4, c5)
-        pred, saved = eng.keypoint_head(ctx, kp, True)
-        cls, reg = eng.detection_head(ctx, det)
-        self._finish_forward(ctx)
+        ctx, _, (pred, saved, cls, reg) = self._run_net(img_batch, self._want_tape(), intermediate=True)
         outs = self._wrap(ctx, ["k0", "k1", "k2", "k3", "pred", "cls", "reg"], saved + [pred, cls, reg])
         return outs[4], (outs[:5], [outs[5], outs[6], self.anchors(img_batch)])
 
     def _fpn_features(self, img_batch):
-        self._prepare(img_batch)
-        eng = self._engine
-        ctx = Ctx(False)
-        c2, c3, c4, c5 = eng.backbone(ctx, img_batch)
-        kp = eng.kp_pyramid(ctx, c2, c3, c4, c5)
-        det = eng.det_pyramid(ctx, c3, c4, c5)
-        self._finish_forward(ctx)
+        _, (kp, det), _ = self._run_net(img_batch, False, heads=False)
         return [[ops.export_f32(a, a.C, a.H, a.W) for a in kp], [ops.export_f32(a, a.C, a.H, a.W) for a in det]]
+
+    def _prn_pack(self, rows, B, n):
+        """Contiguous f32 rows [B, n] -> the PRN's activation layout: [B, 1, 1, npad] in the compute dtype, rows padded with zeros to
+        32 channels (prn_coeff 1 / 3: n % 32 != 0).  One mpn_prn_pack launch; f32 compute with npad == n is a view."""
+        cdt = self.compute_dtype
+        npad = ops.round_up(n, 32)
+        if npad == n and not ops.is16(cdt):
+            return ops.Act(rows.view(B, 1, 1, n), n)
+        y = torch.empty((B, 1, 1, npad), dtype=cdt, device=rows.device)
+        call("mpn_prn_pack", ops.ptr(rows), ops.ptr(y), B, n, npad, ops.dtype_code(cdt), ops.stream_ptr())
+        return ops.Act(y, n)
 
     def _prn_layers(self, ctx, xin, drop):
         """The PRN's layer sequence from the packed input to the f32 pre-activation of dens2 — one implementation for the eager
@@ -510,13 +498,8 @@ class poseNet(nn.Module):
         if x.numel() != B * n or label.numel() != B * n:
             raise ValueError("PRN step: input %s / label %s do not hold %d x %d values" % (tuple(x.shape), tuple(label.shape), B, n))
         npad = ops.round_up(n, 32)
-        if npad != n or ops.is16(cdt):
-            xin = torch.empty((B, 1, 1, npad), dtype=cdt, device=x.device)
-            call("mpn_prn_pack", ops.ptr(x), ops.ptr(xin), B, n, npad, ops.dtype_code(cdt), ops.stream_ptr())
-        else:
-            xin = x.view(B, 1, 1, n)
         ctx = Ctx(True)
-        o = self._prn_layers(ctx, ops.Act(xin, n), lambda c, h, k: eng.dropout_dev(c, h, prn.drop.p, k))
+        o = self._prn_layers(ctx, self._prn_pack(x, B, n), lambda c, h, k: eng.dropout_dev(c, h, prn.drop.p, k))
         if not o.needs_grad:
             raise MpnError("PRN step: no parameter of the PRN is trainable")
         dl = torch.empty((B, 1, 1, npad), dtype=cdt, device=x.device)
@@ -538,18 +521,9 @@ class poseNet(nn.Module):
         B = x.shape[0]
         n = prn.height * prn.width * 17
         res = x.detach().float().reshape(B, n).contiguous()
-        npad = ops.round_up(n, 32)        # activation rows are stored padded to 32 channels (prn_coeff 1 / 3: n % 32 != 0)
-        if npad != n:
-            xin = torch.zeros((B, 1, 1, npad), dtype=self.compute_dtype, device=x.device)
-            xin[:, 0, 0, :n].copy_(res)
-        elif ops.is16(self.compute_dtype):
-            xin = torch.empty((B, 1, 1, n), dtype=self.compute_dtype, device=x.device)
-            ops.cast_lowp(res, xin)
-        else:
-            xin = res.view(B, 1, 1, n)
         train = torch.is_grad_enabled() and any(p.requires_grad for p in prn.parameters())
         ctx = Ctx(train)
-        o = self._prn_layers(ctx, ops.Act(xin, n), lambda c, h, k: eng.dropout(c, h, prn.drop.p))
+        o = self._prn_layers(ctx, self._prn_pack(res, B, n), lambda c, h, k: eng.dropout(c, h, prn.drop.p))
         out = torch.empty((B, n), dtype=torch.float32, device=x.device)
         call("mpn_add_softmax_rows", ops.ptr(o.t), o.Cs, ops.ptr(res), ops.ptr(out), B, n, 1, ops.stream_ptr())
         if ctx.train and o.needs_grad:
@@ -560,15 +534,7 @@ class poseNet(nn.Module):
                 g = g.reshape(B, n).float().contiguous()
                 dl = torch.empty((B, n), dtype=torch.float32, device=x.device)
                 call("mpn_softmax_rows_backward", ops.ptr(out), ops.ptr(g), ops.ptr(o.t), o.Cs, ops.ptr(dl), B, n, ops.stream_ptr())
-                if npad != n:
-                    d = torch.zeros((B, 1, 1, npad), dtype=self.compute_dtype, device=x.device)
-                    d[:, 0, 0, :n].copy_(dl)
-                elif ops.is16(self.compute_dtype):
-                    d = torch.empty((B, 1, 1, n), dtype=self.compute_dtype, device=x.device)
-                    ops.cast_lowp(dl, d)
-                else:
-                    d = dl.view(B, 1, 1, n)
-                ctx.set_grad(o, ops.Act(d, n))
+                ctx.set_grad(o, self._prn_pack(dl, B, n))
             ctx.tape.append(bwd)
         out4 = out.view(B, prn.height, prn.width, 17)
         out4 = self._wrap(ctx, ["prn"], [out4])[0]

@@ -53,7 +53,6 @@ import ctypes
 import torch
 
 from . import _lib, ops
-from .engine import Ctx
 from .network import losses
 
 _epoch = itertools.count(1 << 20)
@@ -117,15 +116,11 @@ class ReplayedTrainStep(object):
         eng = m._engine
         want_kp = subnet in ("keypoint_subnet", "train_both")
         want_det = subnet in ("detection_subnet", "train_both")
-        m._prepare(img)
-        ctx = Ctx(True)
-        c2, c3, c4, c5 = eng.backbone(ctx, img)
         grads = {}
         kp8 = det2 = None
-        # same operation order as poseNet.keypoint_forward / detection_forward / train_both_forward (the reverse tape, hence the
-        # order in which gradients accumulate into shared feature maps, follows it)
-        kp_feats = eng.kp_pyramid(ctx, c2, c3, c4, c5) if want_kp else None
-        det_feats = eng.det_pyramid(ctx, c3, c4, c5) if want_det else None
+        # the two steps of poseNet._run_net, the one forward composition (the reverse tape, hence the order in which gradients
+        # accumulate into shared feature maps, follows it), with the loss form chosen in between
+        ctx, kp_feats, det_feats = m._features(img, True, want_kp, want_det)
         # heat-map loss: one launch over the network's internal tensors where the geometry allows (losses.mse_train_supported),
         # else the API path's export -> loss -> import chain.  Both produce the same gradient bits.
         fused_mse = False
@@ -133,13 +128,10 @@ class ReplayedTrainStep(object):
             hp = kp_feats[0]
             fused_mse = self.fused_mse and tensors[0].shape == (hp.B, 18, hp.H, hp.W) and hp.H % 8 == 0 and hp.W % 8 == 0 \
                 and tensors[0].shape == tensors[1].shape
-            pred, saved = eng.keypoint_head(ctx, kp_feats, True, internal=fused_mse)
-            if fused_mse and not losses.mse_train_supported(saved + [pred], tensors[0], tensors[1]):
-                raise _lib.MpnError("recorded train step: the keypoint head's internal geometry does not fit the one-pass loss kernel; "
-                                    "construct ReplayedTrainStep(..., fused_mse=False)")
-        if want_det:
-            cls, reg = eng.detection_head(ctx, det_feats)
-        m._finish_forward(ctx)
+        pred, saved, cls, reg = m._heads(ctx, kp_feats, det_feats, True, internal=fused_mse)
+        if fused_mse and not losses.mse_train_supported(saved + [pred], tensors[0], tensors[1]):
+            raise _lib.MpnError("recorded train step: the keypoint head's internal geometry does not fit the one-pass loss kernel; "
+                                "construct ReplayedTrainStep(..., fused_mse=False)")
         dev = img.device
         ones = self._ones(dev)
         if want_kp and fused_mse:      # d(total)/d(heat-map total) = 1, known before the loss value is: gradients in the same pass

@@ -48,12 +48,7 @@ def main():
 
     def net_only():
         with torch.no_grad():
-            m._prepare(img)
-            from multiposenet.pytorch_amd.engine import Ctx
-            eng, ctx = m._engine, Ctx(False)
-            c2, c3, c4, c5 = eng.backbone(ctx, img)
-            heat, _ = eng.keypoint_head(ctx, eng.kp_pyramid(ctx, c2, c3, c4, c5), False)
-            return heat, eng.detection_head(ctx, eng.det_pyramid(ctx, c3, c4, c5))
+            return m._run_net(img, False)[2]          # (heat, [], cls, reg): the network without anchors, decode and NMS
 
     def net():
         with torch.no_grad():
