@@ -35,7 +35,7 @@ class Ctx(object):
         self.bn_train_ran = False
         self.side_keep = []      # operands of side-stream launches, kept alive until the streams join
         self.wt_ready = None     # event: the transposed weight copies (made on the side stream) are complete
-        self.bnb = {}            # id(BN output Act) -> per-tile backward statistics produced by the launch that completed its gradient
+        self.bnb = {}            # id(BN output Act) -> BNBackwardResult of the launch that completed its gradient
         self.fwd_side_join = False   # forward work is in flight on the side stream (Engine.det_pyramid): join before it is consumed
         self.cls_ev = None       # event: the class input gradients of conv2 (side stream) are complete (Engine.wait_class_grads)
         self.schedule = None     # bucket schedule of this backward pass: the data-parallel GradReducer, or its process-group-free
@@ -312,7 +312,22 @@ class Engine(object):
         """Arguments of the in-launch forward finalize for BatchNorm layer `bn` (train mode)."""
         if bn is None or not self.fuse_bn_finalize:
             return None
-        return (bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, bn.momentum if bn.momentum is not None else 0.1, bn.eps)
+        return ops.BNFinalize(bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var,
+                              bn.momentum if bn.momentum is not None else 0.1, bn.eps)
+
+    def _bn_backward_ride(self, x, g):
+        """Operands of the BatchNorm-backward statistics that ride in the epilogue of the launch completing ``g``, the gradient of
+        ``x``: a BNBackward when x is a BatchNorm output whose last gradient contribution this is, else None."""
+        src = x.bn_src
+        if x.cons != 0 or src is None or not self.fuse_bn_stats or not src.wants_stats or src.y.t.dtype != g.t.dtype:
+            return None
+        fin = None
+        if self.fuse_bn_finalize:
+            ar, bn = self.m._arena, src.layer
+            fin = ops.BNBackwardFinalize(bn.weight.data, src.train_stats,
+                                         ar.grad_seg(bn.weight) if bn.weight.requires_grad else None,
+                                         ar.grad_seg(bn.bias) if bn.bias.requires_grad else None)
+        return ops.BNBackward(src.y, x if (src.relu and src.has_res) else None, src.state, src.relu, fin)
 
     def conv(self, ctx, x, layer, act=0, res=None, res_mode=0, stats=False, out_f32=False, tag="", bn=None):
         O, I, R, S, stride, pad = _geom(layer)
@@ -320,14 +335,12 @@ class Engine(object):
         y, st = ops.conv_forward(x, self.w_fwd(layer), O, R, S, stride, pad, bias=bias.data if bias is not None else None,
                                  act=act, res=res, res_mode=res_mode, want_stats=stats, out_f32=out_f32, tag=tag,
                                  bn_fin=self._bn_fin(bn) if stats else None)
-        y.relu_out = act == 1
         if ctx.train and self._taped(ctx, layer, (x,), (y,), lambda: self._conv_bwd(ctx, x, layer, y, act, res, res_mode), res=res):
             if x.needs_grad:
                 x.cons += 1
                 x.conv_cons += 1
             if res is not None and res.needs_grad:
                 res.cons += 1
-                res.other_cons += 1
         return y, st
 
     def _conv_bwd(self, ctx, x, layer, y, act, res, res_mode):
@@ -368,18 +381,7 @@ class Engine(object):
             g, existed = ctx.gbuf(x)
             lazy = ctx.lazy_res.pop(id(x), None)      # (dz, bits) of the identity shortcut: added in this launch's epilogue
             wt = self.w_t(ctx, layer)
-            bnb = None
-            if x.cons == 0 and x.bn_src is not None and self.fuse_bn_stats:
-                # this launch completes dz of the BatchNorm that produced x: its backward statistics ride in the epilogue
-                by, st, relu, has_res, wants_stats, bn_layer, train_stats = x.bn_src
-                if wants_stats and by.t.dtype == g.t.dtype:
-                    fin = None
-                    if self.fuse_bn_finalize:
-                        ar = self.m._arena
-                        fin = (bn_layer.weight.data, train_stats,
-                               ar.grad_seg(bn_layer.weight) if bn_layer.weight.requires_grad else None,
-                               ar.grad_seg(bn_layer.bias) if bn_layer.bias.requires_grad else None)
-                    bnb = (by, x if (relu and has_res) else None, st, relu, fin)
+            bnb = self._bn_backward_ride(x, g)
             if lazy is not None:
                 assert not existed
                 _, part = ops.conv_forward(dy, wt, I, R, S, stride, pad, mode=1, out_hw=(x.H, x.W), cin=wt.shape[3], out=g, bnb=bnb,
@@ -396,8 +398,6 @@ class Engine(object):
         O, I, R, S, stride, pad = _geom(layer)
         bias = layer.bias
         ys = ops.conv_forward_seg(xs, self.w_fwd(layer), O, R, S, pad, bias=bias.data if bias is not None else None, act=act, out_f32=out_f32)
-        for y in ys:
-            y.relu_out = act == 1
         if ctx.train:
             self._taped(ctx, layer, xs, ys, lambda: self._conv_seg_bwd(ctx, xs, layer, ys, act))
         return ys
@@ -464,20 +464,10 @@ class Engine(object):
                 self._note_use(ctx, layer.bias)
                 if res is not None and res.needs_grad:
                     res.cons += 1
-                    res.other_cons += 1
                 wants_stats = bool(train_stats or layer.weight.requires_grad or layer.bias.requires_grad)
-                z.bn_src = (y, st, relu, res is not None, wants_stats, layer, train_stats)
+                z.bn_src = ops.BNSource(y, st, relu, res is not None, wants_stats, layer, train_stats)
                 ctx.tape.append(lambda: self._bn_bwd(ctx, y, z, st, layer, relu, res, train_stats))
         return z
-
-    @staticmethod
-    def _bnb_args(fused):
-        """What the launch that completed dz left behind: nothing, per-tile partial statistics, or finished coefficients."""
-        if fused is None:
-            return {}
-        if isinstance(fused, str) or (fused.dim() == 2 and fused.shape[0] == 3):
-            return {"coef": fused}
-        return {"partial": fused}
 
     def _bn_bwd(self, ctx, y, z, st, layer, relu, res, train_stats):
         dz = ctx.pop_grad(z)
@@ -504,7 +494,7 @@ class Engine(object):
                              dgamma=ar.grad_seg(layer.weight) if wg else None,
                              dbeta=ar.grad_seg(layer.bias) if bg else None,
                              want_dy=want_dy, dres=dres, dres_acc=dres_acc, remask=bool(relu and res is None),
-                             **self._bnb_args(ctx.bnb.pop(id(z), None)))
+                             fused=ctx.bnb.pop(id(z), None))
         self._param_grads(ctx, layer, None)          # (dgamma / dbeta were written by the launch above: only the completion report)
         if want_dy:
             ctx.set_grad(y, dy)
@@ -564,7 +554,6 @@ class Engine(object):
         if ctx.train and x.needs_grad:
             z.needs_grad = True
             x.cons += 1
-            x.other_cons += 1
 
             def bwd():
                 x.cons -= 1
@@ -581,7 +570,6 @@ class Engine(object):
         y, idx = ops.maxpool_forward(x, needs_grad=need)
         if need:
             x.cons += 1
-            x.other_cons += 1
 
             def bwd():
                 x.cons -= 1
@@ -626,7 +614,6 @@ class Engine(object):
         O, I, R, S, stride, pad = _geom(layer)
         bias = layer.bias
         y = ops.conv_forward_cat(srcs, H, W, self.w_fwd(layer), O, bias=bias.data if bias is not None else None, act=act)
-        y.relu_out = act == 1
         if ctx.train:
             self._taped(ctx, layer, srcs, (y,), lambda: self._conv_cat_bwd(ctx, srcs, H, W, layer, y, act))
         return y
@@ -711,7 +698,6 @@ class Engine(object):
             ops.upsample_slice(q2, cat2, C)
             y, _ = ops.conv_forward(cat2, wo.wm, O, 3, 3, 1, 1, bias=bias.data if bias is not None else None, act=3 if act == 1 else act,
                                     res=st["e"], res_mode=1)
-        y.relu_out = act == 1
         if ctx.train:        # (wt=False: the transposed operands are wo's)
             self._taped(ctx, layer, srcs, (y,), lambda: self._conv_cat_cls_bwd(ctx, srcs, H, W, layer, y, act, wo, cat2), wt=False)
         ctx.side_keep.append((st, y))

@@ -5,6 +5,7 @@ raw device pointers, sizes and the current ``hipStream_t`` to ``libmpn_hip.so``.
 """
 import ctypes
 import os
+from collections import namedtuple
 
 import torch
 
@@ -85,7 +86,7 @@ class Act(object):
 
     Cs (channel storage) is a multiple of 32; lanes [C, Cs) hold zeros (see include/mpn.h).
     """
-    __slots__ = ("t", "B", "H", "W", "C", "Cs", "needs_grad", "tag", "seg", "cons", "bn_src", "mask", "conv_cons", "relu_out", "other_cons")
+    __slots__ = ("t", "B", "H", "W", "C", "Cs", "needs_grad", "tag", "seg", "cons", "bn_src", "mask", "conv_cons")
 
     def __init__(self, t, C, needs_grad=False, tag=""):
         self.t = t
@@ -95,9 +96,7 @@ class Act(object):
         self.tag = tag
         self.seg = None          # (flat buffer, index) when this activation is one level of a pyramid group (alloc_seg)
         self.cons = 0            # gradient contributions still to come in backward (engine: last-contributor detection)
-        self.bn_src = None       # output of a BatchNorm: (conv output y, BNState, relu, has_residual, wants_stats, the BN layer, train_stats)
-        self.relu_out = False    # forward: this tensor is relu(conv(.)) (conv epilogue act 1)
-        self.other_cons = 0      # consumers other than plain / pyramid convolutions (residual adds, relu, pooling)
+        self.bn_src = None       # output of a BatchNorm: the BNSource that produced it
         self.conv_cons = 0       # how many of the pending contributions are input gradients of plain convolutions (engine.conv)
         self.mask = None         # sign bits of this tensor (uint8 [P, Cs / V]) when bn_act produced them for the backward pass
 
@@ -502,7 +501,12 @@ def conv_forward(x, w, Cout, R, S, stride, pad, bias=None, scale=None, act=0, re
 
     mode 0 = forward gather, mode 1 = dgrad gather (then ``out_hw`` is the input-gradient size and
     ``w`` is the transposed copy).  x_geom=(H, W, sB, sH, sW) overrides the source geometry (stem).
-    y_geom=(ptr_tensor, sB, sP) writes into a slice of a larger buffer.  Returns (Act|None, stats).
+    y_geom=(ptr_tensor, sB, sP) writes into a slice of a larger buffer.
+
+    Returns (Act|None, second).  ``second`` is None unless one of these was asked for:
+    want_stats: the forward statistics table [tiles, Cout, 2] — or, with ``bn_fin`` (a BNFinalize) when the launch finalized in
+    place (fin_in_launch), the finished BNState;
+    bnb (a BNBackward; this launch completes dz of that BatchNorm): a BNBackwardResult.
     """
     dev = x.t.device
     dt = x.t.dtype
@@ -515,7 +519,7 @@ def conv_forward(x, w, Cout, R, S, stride, pad, bias=None, scale=None, act=0, re
             # 1x1 / stride 2 (the ResNet down-sampling shortcut): only the pixels (2 i, 2 j) of dx receive anything — one class, one tap.  Needs an
             # existing dx to add to (the other three quarters keep what they hold) and no epilogue statistics (they would need every pixel).
             conv_forward(x, w, Cout, 1, 1, 1, 0, out=out, accumulate=True, mode=0, out_hw=((out_hw[0] + 1) // 2, (out_hw[1] + 1) // 2), cin=cin,
-                         _cls=(0, 0, None, 0, 1))
+                         _cls=ParityClass(0, 0, None, 0, one_tap=True))
             return out, None
     Cin = cin if cin is not None else round_up(x.C, 32 if is16(dt) else 16)
     if x_geom is None:
@@ -536,11 +540,11 @@ def conv_forward(x, w, Cout, R, S, stride, pad, bias=None, scale=None, act=0, re
             assert out.t.dtype == odt and (out.B, out.H, out.W) == (x.B, Ho, Wo), "conv output geometry mismatch"
             p.y_sB, p.y_sP = Ho * Wo * out.Cs, out.Cs
         else:       # parity class (a, c) of a stride-2 input gradient (mpn.h: y_step): output pixel (i, j) -> (2 i + a, 2 j + c) of `out`
-            ca, cc_, p.y_H, p.y_W = _cls[0], _cls[1], out.H, out.W
+            ca, cc_, p.y_H, p.y_W = _cls.a, _cls.c, out.H, out.W
             assert out.t.dtype == odt and out.B == x.B and out.Cs == round_up(Cout, 32) and cout_store is None, "class launch: output tensor mismatch"
             assert 2 * (Ho - 1) + ca < out.H and 2 * (Wo - 1) + cc_ < out.W, "class launch: class grid exceeds the output"
             p.y_step, p.y_oh, p.y_ow = 2, ca, cc_
-            if len(_cls) > 4 and _cls[4] == 1:          # 1x1 filter: its only tap
+            if _cls.one_tap:                            # 1x1 filter: its only tap
                 p.w_taps, p.wtap0, p.wtap_dr, p.wtap_ds = 1, 0, 0, 0
             else:                                       # 3x3, pad 1: tap (t_r, t_s) of the class is filter tap (a + 1 - 2 t_r, c + 1 - 2 t_s)
                 p.w_taps, p.wtap0, p.wtap_dr, p.wtap_ds = 9, (ca + 1) * 3 + (cc_ + 1), -6, -2
@@ -581,46 +585,47 @@ def conv_forward(x, w, Cout, R, S, stride, pad, bias=None, scale=None, act=0, re
         if bn_fin is not None and fin_in_launch(tiles, Cout):
             # the last workgroup of every channel tile turns the tile partials into the BatchNorm coefficients (no finalize launch):
             # the BNState comes back in the stats slot
-            gamma, beta, rm, rv, momentum, eps = bn_fin
             keep, stats = stats, BNState(Cout, dev)
             p.fin_counters = fin_counters(dev).data_ptr()
-            p.fin_gamma, p.fin_beta = gamma.data_ptr(), beta.data_ptr()
-            p.fin_rm = rm.data_ptr() if rm is not None else None
-            p.fin_rv = rv.data_ptr() if rv is not None else None
+            p.fin_gamma, p.fin_beta = bn_fin.gamma.data_ptr(), bn_fin.beta.data_ptr()
+            p.fin_rm = bn_fin.running_mean.data_ptr() if bn_fin.running_mean is not None else None
+            p.fin_rv = bn_fin.running_var.data_ptr() if bn_fin.running_var is not None else None
             p.fin_out = stats.mean.data_ptr()
-            p.fin_count, p.fin_momentum, p.fin_eps = float(x.B * Ho * Wo), momentum, eps
+            p.fin_count, p.fin_momentum, p.fin_eps = float(x.B * Ho * Wo), bn_fin.momentum, bn_fin.eps
     if bnb is not None:
-        # this launch completes dz of a BatchNorm: its backward statistics ride in the epilogue (returned in the stats slot)
-        by, bz, st, relu = bnb[:4]
+        # this launch completes dz of a BatchNorm: its backward statistics ride in the epilogue (a BNBackwardResult in the stats slot)
+        by, bz, st = bnb.y, bnb.z, bnb.state
         assert y_geom is None and not out_f32 and by.t.shape == out.t.shape and by.t.dtype == out.t.dtype
         tiles = call("mpn_conv_stats_tiles", ctypes.byref(p))
         if _cls is None:
             stats = torch.empty((tiles, Cout, 2), dtype=torch.float32, device=dev)
             p.bnb_partial = stats.data_ptr()
         else:       # rows [tile0, tile0 + tiles) of the table the four class launches share
-            stats, tile0 = _cls[2], _cls[3]
-            assert tile0 + tiles <= stats.shape[0]
-            p.bnb_partial = stats.data_ptr() + tile0 * Cout * 2 * 4
+            stats = _cls.table
+            assert _cls.tile0 + tiles <= stats.shape[0]
+            p.bnb_partial = stats.data_ptr() + _cls.tile0 * Cout * 2 * 4
         p.bnb_y = by.t.data_ptr()
         p.bnb_z = bz.t.data_ptr() if bz is not None else None
         if bz is not None and bz.mask is not None:          # the ReLU mask as bits (bn_act(want_mask=True)): z itself is not read
             p.bnb_mask, p.bnb_z = bz.mask.data_ptr(), None
         p.bnb_mean, p.bnb_invstd = st.mean.data_ptr(), st.invstd.data_ptr()
         p.bnb_scale, p.bnb_shift = st.scale.data_ptr(), st.shift.data_ptr()
-        p.bnb_relu = 1 if relu else 0
-        if _cls is None and len(bnb) > 4 and bnb[4] is not None and fin_in_launch(tiles, Cout):
+        p.bnb_relu = 1 if bnb.relu else 0
+        fin = bnb.fin
+        if _cls is None and fin is not None and fin_in_launch(tiles, Cout):
             # ... and the last workgroup of every channel tile finishes the reduction: dgamma / dbeta and the (k1, k2, k3) of
-            # dy = k1*g + k2*y + k3 (mpn_bn_bwd_finalize's work); the coefficient tensor comes back in the stats slot
-            gamma, train, dgamma, dbeta = bnb[4]
-            keep, stats = stats, (torch.empty((3, Cout), dtype=torch.float32, device=dev) if train else None)
+            # dy = k1*g + k2*y + k3 (mpn_bn_bwd_finalize's work); the partial table dies with this call (keep), the coefficients
+            # (frozen statistics: none, k1 is the forward scale) come back
+            keep, coef = stats, (torch.empty((3, Cout), dtype=torch.float32, device=dev) if fin.train else None)
             p.fin_counters = fin_counters(dev).data_ptr()
-            p.fin_gamma = gamma.data_ptr()
-            p.fin_out = stats.data_ptr() if stats is not None else None
-            p.fin_dgamma = dgamma.data_ptr() if dgamma is not None else None
-            p.fin_dbeta = dbeta.data_ptr() if dbeta is not None else None
-            p.fin_count, p.fin_train = float(x.B * Ho * Wo), 1 if train else 0
-            if stats is None:
-                stats = "frozen"
+            p.fin_gamma = fin.gamma.data_ptr()
+            p.fin_out = coef.data_ptr() if coef is not None else None
+            p.fin_dgamma = fin.dgamma.data_ptr() if fin.dgamma is not None else None
+            p.fin_dbeta = fin.dbeta.data_ptr() if fin.dbeta is not None else None
+            p.fin_count, p.fin_train = float(x.B * Ho * Wo), 1 if fin.train else 0
+            stats = BNBackwardResult(None, coef, coef is None)
+        else:
+            stats = BNBackwardResult(stats, None, False)
 
     def flops():
         # algorithmic FLOPs: 2 * output pixels * Cout * taps * Cin; a stride-s dgrad only has 1/s^2 live taps
@@ -632,7 +637,7 @@ def conv_forward(x, w, Cout, R, S, stride, pad, bias=None, scale=None, act=0, re
         byts = x.B * H * W * Cin * es + x.B * Ho * Wo * p.Cout_store * (4 if out_f32 else es) * (2 if accumulate else 1) \
             + (x.B * Ho * Wo * p.Cout_store * es if res is not None and res_mode == 1 else 0)
         return "%s %dx%d %d->%d @%dx%d s%d%s%s%s%s%s|%d" % (
-            ("dgrad s2 class(%d,%d)" % (_cls[0], _cls[1])) if _cls is not None else ("dgrad" if mode == 1 else "fwd"), R, S, Cin, Cout, Ho, Wo, stride,
+            ("dgrad s2 class(%d,%d)" % (_cls.a, _cls.c)) if _cls is not None else ("dgrad" if mode == 1 else "fwd"), R, S, Cin, Cout, Ho, Wo, stride,
             " stats" if want_stats else "",
             " bias" if bias is not None else "", " act%d" % act if act else "", " res%d" % res_mode if res is not None else "",
             " acc" if accumulate else "", byts)
@@ -659,8 +664,8 @@ def _conv_dgrad_s2_classes(dy, wt, Cout, out_hw, cin, out, accumulate, bnb, need
     for a, c, ho, wo, t, tile0 in plan:
         if t > 0:
             conv_forward(dy, wt, Cout, 1 + a, 1 + c, 1, 0, out=out, accumulate=accumulate, mode=0, out_hw=(ho, wo), cin=cin, bnb=bnb,
-                         _cls=(a, c, part, tile0))
-    return out, part
+                         _cls=ParityClass(a, c, part, tile0))
+    return out, (BNBackwardResult(part, None, False) if bnb is not None else None)
 
 
 def dgrad_s2_class_plan(B, H, W, tile_pixels=128):
@@ -759,6 +764,24 @@ class BNState(object):
         self.mean, self.invstd, self.scale, self.shift = buf[0], buf[1], buf[2], buf[3]
 
 
+# What travels between the engine and conv_forward when BatchNorm work rides in a convolution launch (plain records, read by name).
+# conv_forward(bn_fin=): the in-launch forward finalize of train-mode statistics
+BNFinalize = namedtuple("BNFinalize", "gamma beta running_mean running_var momentum eps")
+# BNBackward.fin: the in-launch backward finalize (train: batch statistics; dgamma / dbeta: the gradient slices to add to, or None)
+BNBackwardFinalize = namedtuple("BNBackwardFinalize", "gamma train dgamma dbeta")
+# conv_forward(bnb=): the BatchNorm whose dz the launch completes — y its input, z its output (only when the ReLU mask must be read
+# from it, else None), state its BNState
+BNBackward = namedtuple("BNBackward", "y z state relu fin", defaults=(None,))
+# Act.bn_src: the BatchNorm that produced the activation
+BNSource = namedtuple("BNSource", "y state relu has_res wants_stats layer train_stats")
+# conv_forward(_cls=): parity class (a, c) of a stride-2 input gradient; its statistics go to rows [tile0, ...) of the shared table
+ParityClass = namedtuple("ParityClass", "a c table tile0 one_tap", defaults=(False,))
+# What a launch given bnb= returns, exactly one of: the per-tile partial table [tiles, C, 2] (reduced, not finalized); coef [3, C]
+# = k1, k2, k3 (finalized in the launch, batch statistics); frozen (finalized in the launch, frozen statistics: k1 is the forward
+# scale, no tensor).  A finalized launch never hands its partial table out: partial is None then.
+BNBackwardResult = namedtuple("BNBackwardResult", "partial coef frozen")
+
+
 def bn_finalize_train(stats, count, gamma, beta, rm, rv, momentum=0.1, eps=1e-5):
     C = stats.shape[1]
     st = BNState(C, stats.device)
@@ -794,23 +817,23 @@ def masked_copy(dz, mask_bits, out):
 
 
 def bn_backward(dz, z, y, st, gamma, relu, train, dgamma=None, dbeta=None, want_dy=True, dres=None, dres_acc=False, remask=False,
-                partial=None, coef=None):
+                fused=None):
     """Returns dy (Act or None).  dres (Act) receives/accumulates g = dz*(z>0).  remask=True (forward without a
     residual input): the ReLU mask is recomputed from y and the forward's scale/shift instead of reading z.
-    partial: per-tile (sum g, sum g*xhat) already produced by the launch that wrote dz (conv_forward(bnb=...)); the
-    reduction pass over dz / y / z is skipped."""
+    fused: the BNBackwardResult of the launch that wrote dz (conv_forward(bnb=...)): with its per-tile (sum g, sum g*xhat)
+    the reduction pass over dz / y / z is skipped, with its coefficients (or frozen) the finalize as well."""
     dev = y.t.device
     P, C, Cs = y.P, y.C, y.Cs
     dc = dtype_code(y.t.dtype)
     k1, k2, k3 = st.scale, None, None        # frozen BN, no parameter gradients: dy = g * gamma * invstd
-    if coef is not None:
-        # reduction AND finalize already happened in the launch that completed dz (conv_forward(bnb=(..., fin))): dgamma / dbeta are
-        # in place, coef = [3][C] k1, k2, k3 (or "frozen": k1 = gamma * invstd = the forward scale)
-        if not isinstance(coef, str):
-            k1, k2, k3 = coef[0], coef[1], coef[2]
+    if fused is not None and fused.partial is None:
+        # reduction AND finalize already happened in the launch that completed dz (BNBackward.fin): dgamma / dbeta are in place,
+        # coef = [3][C] k1, k2, k3 (frozen: none, k1 = gamma * invstd = the forward scale)
+        if not fused.frozen:
+            k1, k2, k3 = fused.coef[0], fused.coef[1], fused.coef[2]
     elif train or dgamma is not None or dbeta is not None:
-        if partial is not None:
-            part, chunks = partial, partial.shape[0]
+        if fused is not None:
+            part, chunks = fused.partial, fused.partial.shape[0]
         else:
             chunks = call("mpn_bn_bwd_chunks", P, Cs, dc)
             part = workspace(chunks * C * 2 * 4, dev, slot=3)

@@ -191,6 +191,7 @@ def test_bnb_partials_accept_the_device_order_and_reject_a_mask_from_y():
 
 
 def test_bnb_finalize_rejects_sum_g_added_to_dgamma():
+    from multiposenet.pytorch_amd.ops import BNBackwardResult
     cid = "f32 dgrad 1x1 256->64 bnb recompute finalize train"
     _, route, _, f = CASES[cid]
     R = st._ref(cid, f)
@@ -201,13 +202,14 @@ def test_bnb_finalize_rejects_sum_g_added_to_dgamma():
     part = _tile_sums(gz, [gz, gz * xh])[0].float()
     count = float(got.numel() // got.shape[1])
     S1, S2, k1, k2, k3, _, _, _ = stream_ref.bwd_coef_ref(part, count, R.gamma, R.mean, R.invstd)
-    coef = torch.stack([k1, k2, k3]).float()
-    st._check_bnb_fin("cpu teeth " + cid, route, f, R, part, (R.dg0.double() + S2).float(), (R.db0.double() + S1).float(), coef, count)
-    _reject(st._check_bnb_fin, "cpu teeth dgamma += sum g", route, f, R, part, (R.dg0.double() + S1).float(), (R.db0.double() + S1).float(), coef, count)
+    fused = BNBackwardResult(None, torch.stack([k1, k2, k3]).float(), False)
+    st._check_bnb_fin("cpu teeth " + cid, route, f, R, part, (R.dg0.double() + S2).float(), (R.db0.double() + S1).float(), fused, count)
+    _reject(st._check_bnb_fin, "cpu teeth dgamma += sum g", route, f, R, part, (R.dg0.double() + S1).float(), (R.db0.double() + S1).float(), fused, count)
     # frozen statistics: no coefficients, dgamma / dbeta still accumulated
     ff = dict(f, bnb_fin="frozen")
-    st._check_bnb_fin("cpu teeth frozen", route, ff, R, part, (R.dg0.double() + S2).float(), (R.db0.double() + S1).float(), "frozen", count)
-    _reject(st._check_bnb_fin, "cpu teeth frozen, dgamma untouched", route, ff, R, part, R.dg0, (R.db0.double() + S1).float(), "frozen", count)
+    frozen = BNBackwardResult(None, None, True)
+    st._check_bnb_fin("cpu teeth frozen", route, ff, R, part, (R.dg0.double() + S2).float(), (R.db0.double() + S1).float(), frozen, count)
+    _reject(st._check_bnb_fin, "cpu teeth frozen, dgamma untouched", route, ff, R, part, R.dg0, (R.db0.double() + S1).float(), frozen, count)
 
 
 def test_class_checks_reject_a_wrong_offset_and_a_wrong_table_row():

@@ -209,16 +209,17 @@ def _check_bnb(cid, route, f, R, got, part):
     _check_partials(cid, route, part, ref_p, mag_p, extra)
 
 
-def _check_bnb_fin(cid, route, f, R, part, dgamma, dbeta, coef, count):
-    """In-launch backward finalize against the device's own partial table: dgamma / dbeta accumulated onto their prefill, and (train) the
-    [3][C] k1 / k2 / k3 of dy = k1 g + k2 y + k3."""
+def _check_bnb_fin(cid, route, f, R, part, dgamma, dbeta, fused, count):
+    """In-launch backward finalize (fused: the launch's ops.BNBackwardResult) against the device's own partial table `part`: dgamma /
+    dbeta accumulated onto their prefill, and (train) the [3][C] k1 / k2 / k3 of dy = k1 g + k2 y + k3."""
     train = f["bnb_fin"] == "train"
+    assert fused.partial is None, (cid, fused)          # a finalized launch keeps its partial table to itself
     if train:
-        assert torch.is_tensor(coef) and tuple(coef.shape) == (3, R.yb.shape[1]), (cid, coef)
+        assert not fused.frozen and torch.is_tensor(fused.coef) and tuple(fused.coef.shape) == (3, R.yb.shape[1]), (cid, fused)
     else:
-        assert isinstance(coef, str) and coef == "frozen", (cid, coef)
+        assert fused.frozen is True and fused.coef is None, (cid, fused)
     stream_ref.check_bwd_finalize(cid + " finalize ", part.cpu(), count, R.gamma, R.mean, R.invstd, R.dg0, R.db0, train, dgamma, dbeta,
-                                  coef if train else None, route)
+                                  fused.coef if train else None, route)
 
 
 def _class_ref(cid, f):
@@ -323,7 +324,7 @@ def _dgrad_weight(wf, dt, k):
 
 
 def _bnb_device(R, f):
-    """(ya, za | None, BNState, relu) as ops.conv_forward takes them."""
+    """The ops.BNBackward (ya, za | None, BNState, relu; no finalize) that ops.conv_forward takes."""
     ops = _ops()
     C = R.yb.shape[1]
     st = ops.BNState(C, "cuda")
@@ -333,7 +334,7 @@ def _bnb_device(R, f):
         za = _act(R.zb, R.odt)
         if how == "mask":
             za.mask = pack_bits(za.t, R.odt)
-    return ya, za, st, how != "norelu"
+    return ops.BNBackward(ya, za, st, how != "norelu")
 
 
 def _conv_case(cid, route, f):
@@ -359,14 +360,14 @@ def _conv_case(cid, route, f):
         gamma, beta = 0.5 + torch.rand(Cout, generator=g), 0.3 * torch.randn(Cout, generator=g)
         rm, rv = 0.1 * torch.randn(Cout, generator=g), 0.5 + torch.rand(Cout, generator=g)
         bn = (gamma, beta, rm, rv, 0.1, 1e-5)
-        kw["bn_fin"] = (gamma.cuda(), beta.cuda(), rm.cuda(), rv.cuda(), 0.1, 1e-5)
+        kw["bn_fin"] = ops.BNFinalize(gamma.cuda(), beta.cuda(), rm.cuda(), rv.cuda(), 0.1, 1e-5)
     tiles = (B * Ho * Wo + TP - 1) // TP
     dgamma = dbeta = None
     if f.get("bnb"):
         kw["bnb"] = _bnb_device(R, f)
         if f.get("bnb_fin"):
             dgamma, dbeta = R.dg0.cuda(), R.db0.cuda()
-            kw["bnb"] += ((R.gamma.cuda(), f["bnb_fin"] == "train", dgamma, dbeta),)
+            kw["bnb"] = kw["bnb"]._replace(fin=ops.BNBackwardFinalize(R.gamma.cuda(), f["bnb_fin"] == "train", dgamma, dbeta))
 
     if f.get("stem"):
         Hp, Wp = H + 6, W + 8
@@ -406,14 +407,15 @@ def _conv_case(cid, route, f):
     if f.get("fin"):
         _check_fin(cid, route, got, stats, bn, kw["bn_fin"])
     if f.get("bnb"):
-        part = stats
+        assert isinstance(stats, ops.BNBackwardResult), (cid, stats)
+        part = stats.partial
         if f.get("bnb_fin") and ops.fin_in_launch(tiles, Cout):
             assert len(seen) == 1, "%s: %d partial tables allocated" % (cid, len(seen))
             part = seen[0]
             _check_bnb_fin(cid, route, f, R, part, dgamma, dbeta, stats, float(B * Ho * Wo))
         elif f.get("bnb_fin"):
             # more pixel tiles than one workgroup finishes: the table comes back, dgamma / dbeta are left to the finalize launch
-            assert torch.is_tensor(stats) and tuple(stats.shape) == (tiles, Cout, 2), (cid, stats)
+            assert torch.is_tensor(part) and tuple(part.shape) == (tiles, Cout, 2) and stats.coef is None and not stats.frozen, (cid, stats)
             assert torch.equal(dgamma.cpu(), R.dg0) and torch.equal(dbeta.cpu(), R.db0), "%s: dgamma / dbeta touched without a finalize" % cid
         _check_bnb(cid, route, f, R, got, part)
         cnt = ops.fin_counters(torch.device("cuda", torch.cuda.current_device()))
@@ -429,11 +431,15 @@ def _class_case(cid, route, f):
     wt, cin = _dgrad_weight(R.wf, dt, 3)
     out = _act(R.prev, dt) if R.prev is not None else _nan_out(B, Hx, Wx, Cx, dt)
     bnb = _bnb_device(R, f) if f.get("bnb") else None
-    (o, part), names = _launch(lambda: ops.conv_forward(_act(R.dy, dt), wt, Cx, 3, 3, 2, 1, mode=1, out_hw=(Hx, Wx), cin=cin, out=out,
-                                                        accumulate=R.prev is not None, bnb=bnb))
+    (o, fused), names = _launch(lambda: ops.conv_forward(_act(R.dy, dt), wt, Cx, 3, 3, 2, 1, mode=1, out_hw=(Hx, Wx), cin=cin, out=out,
+                                                         accumulate=R.prev is not None, bnb=bnb))
     assert len(names) == 4, names
     _assert_route(cid, names, _needs_ext(f), route)
-    assert (part is not None) == bool(f.get("bnb"))
+    assert (fused is not None) == bool(f.get("bnb"))
+    part = None
+    if fused is not None:          # the four classes share one table; class launches never finalize
+        assert fused.partial is not None and fused.coef is None and not fused.frozen, (cid, fused)
+        part = fused.partial
     _check_classes(cid, route, f, R, _nchw(o), part)
     _pad_lanes_zero(cid, o)
 

@@ -169,7 +169,7 @@ def _conv_case(cid, route, f):
         gamma, beta = 0.5 + torch.rand(Cout, generator=g), 0.3 * torch.randn(Cout, generator=g)
         rm, rv = 0.1 * torch.randn(Cout, generator=g), 0.5 + torch.rand(Cout, generator=g)
         bn = (gamma, beta, rm, rv, 0.1, 1e-5)
-        kw["bn_fin"] = (gamma.cuda(), beta.cuda(), rm.cuda(), rv.cuda(), 0.1, 1e-5)
+        kw["bn_fin"] = ops.BNFinalize(gamma.cuda(), beta.cuda(), rm.cuda(), rv.cuda(), 0.1, 1e-5)
     if f.get("bnb"):
         g = torch.Generator().manual_seed(seed + 7)
         st = ops.BNState(Cout, "cuda")
@@ -182,7 +182,7 @@ def _conv_case(cid, route, f):
         if f["bnb"] == "mask":          # the ReLU mask as bits (bn_act(want_mask=True) layout): one byte per 8 channels, bit e = z > 0
             bits = (za.t.float() > 0).view(B * H * W, za.Cs // 8, 8).to(torch.int32)
             za.mask = (bits << torch.arange(8, device="cuda", dtype=torch.int32)).sum(2).to(torch.uint8).contiguous()
-        kw["bnb"] = (ya, za, st, True)
+        kw["bnb"] = ops.BNBackward(ya, za, st, True)
 
     if mode == 0:
         w_dev = w_krsc(wv.float(), dt)
@@ -235,7 +235,8 @@ def _conv_case(cid, route, f):
         xh = (yb - mean.double().view(1, -1, 1, 1)) * invstd.double().view(1, -1, 1, 1)
         gz = got * (zb > 0)
         ref_p, mag_p = _tile_sums(gz, [gz, gz * xh])
-        gp = stats.double().cpu()
+        assert stats.coef is None and not stats.frozen, (cid, stats)          # no finalize asked for: the partial table comes back
+        gp = stats.partial.double().cpu()
         check_elementwise("%s bnb sum g" % cid, gp[..., 0], ref_p[..., 0], mag_p[..., 0], F32, 1, TP, route=route, names="tc")
         check_elementwise("%s bnb sum g*xhat" % cid, gp[..., 1], ref_p[..., 1], mag_p[..., 1], F32, 1, TP, 3, route=route, names="tc")
 
@@ -268,7 +269,8 @@ def _check_fin(cid, route, y, st, bn, bn_dev):
     d_rv = mom * d_var * n / (n - 1) + 3 * U24 * (((1 - mom) * rv0).abs() + (mom * unb).abs())
     z = torch.zeros(C, dtype=torch.float64)
     for tag, gotv, refv, bound in (("mean", st.mean, mu, d_mu), ("invstd", st.invstd, is64, d_is), ("scale", st.scale, sc64, d_sc),
-                                   ("shift", st.shift, sh64, d_sh), ("running mean", bn_dev[2], rm64, d_rm), ("running var", bn_dev[3], rv64, d_rv)):
+                                   ("shift", st.shift, sh64, d_sh), ("running mean", bn_dev.running_mean, rm64, d_rm),
+                                   ("running var", bn_dev.running_var, rv64, d_rv)):
         check_elementwise("%s finalize %s" % (cid, tag), gotv.cpu(), refv, z, F32, 1, 0, extra_abs=bound, route=route, names="c")
     cnt = ops.fin_counters(torch.device("cuda", torch.cuda.current_device()))
     assert int(cnt.abs().sum()) == 0, "%s: fin_counters not back at zero: %s" % (cid, cnt.tolist())

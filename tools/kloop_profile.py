@@ -85,7 +85,7 @@ def main():
             st = ops.BNState(Cin, torch.device(dev))
             st.mean.normal_(); st.invstd.uniform_(0.5, 1.5); st.scale.fill_(1.0); st.shift.zero_()
             runs["dgrad+res+bnb"] = lambda: ops.conv_forward(dy, wt, Cin, k, k, 1, pad, mode=1, out_hw=(H, H), cin=Cout, out=dx,
-                                                              bnb=(by, bz, st, True), res=dz, res_mode=1, res_mask=bz.mask)
+                                                              bnb=ops.BNBackward(by, bz, st, True), res=dz, res_mode=1, res_mask=bz.mask)
         print(name, flush=True)
         for tag, fn in runs.items():
             for _ in range(2):
