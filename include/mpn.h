@@ -704,6 +704,42 @@ int mpn_oks_accumulate(const double* kept_score, const int32_t* det_match, const
                        int64_t n_kept, int64_t n_gt, int n_area, int n_thr, const double* rec_thrs, int n_rec,
                        int32_t* order, double* precision, double* recall, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO box AP / AR on the device (COCOeval(coco, res, 'bbox') evaluate + accumulate: pycocotools cocoeval.py computeIoU /
+ * evaluateImg / accumulate and maskApi.c:bbIou, the published algorithm restated, pycocotools is not linked; the reference scores
+ * its detection subnet by validation loss only, evaluate/tester.py:515-543).  All arithmetic float64 and only + - * / min max, so
+ * every result equals a numpy restatement bit for bit.  Every pointer is a device pointer except tab_host, cat_tab_host and
+ * max_dets_host; doubles and int64 tables 8-byte aligned.
+ *
+ * A row is one (category, image) pair that has at least one detection or ground truth; rows are ordered category-major, then by
+ * ascending image id.  tab [n_row + 1][4] int64, row i = (first detection, first ground truth, first kept detection, first IoU
+ * element), row n_row = the totals (D, G, K, size of iou): the convention of img_tab above, validated on the host the same way.
+ * cat_tab [n_cat + 1][2] int64 = (first kept detection, first ground truth) of every category, last row (K, G).
+ *   det_box [D][4], gt_box [G][4]: (x, y, w, h); det_score [D] (finite); gt_flags [G]: bit 0 = ignored, bit 1 = iscrowd.
+ * mpn_box_iou_matrix (one launch, one workgroup per row): the row's stable descending-score order (ties: lower input index
+ *   first) truncated to max_dets -> kept_src [K] (index into the D detections), kept_score [K], kept_area [K] = w * h of the
+ *   detection's own box, kept_rank [K] = position inside the row; iou [kept x G block per row, row-major, at the table's offsets]
+ *   as maskApi.c:bbIou: w = min(D.x + D.w, G.x + G.w) - max(D.x, G.x), 0 when w <= 0, h likewise, i = w * h,
+ *   u = crowd ? D.w * D.h : D.w * D.h + G.w * G.h - i, iou = i / u.
+ * The matching is mpn_oks_match on (iou, kept_area, the annotations' area fields, gt_flags, tab).
+ * mpn_box_accumulate (two launches): COCOeval.accumulate.  order [K] = every category's kept detections in the stable
+ *   descending-score order over its rows (a segmented rank sort, no scratch); precision [n_thr][n_rec][n_cat][n_area][n_max] and
+ *   recall [n_thr][n_cat][n_area][n_max] over the detections with kept_rank < max_dets_host[m], -1 where the category has no
+ *   non-ignored ground truth in the area range.  det_match / det_ig / gt_ig as mpn_oks_match wrote them.  workspace:
+ *   mpn_box_eval_workspace_bytes(K, n_area, n_max, n_thr) bytes, contents need no initialisation.
+ * MPN_E_BADARG before any HIP call: null pointer, n_row <= 0, max_dets (and every max_dets_host entry) outside 1..128, n_cat
+ * outside 1..65535, n_area outside 1..8, n_max outside 1..4, n_thr outside 1..64, n_rec outside 1..4096, negative totals, a
+ * misaligned double array, a table that fails the checks above.
+ * -------------------------------------------------------------------------------------------*/
+int64_t mpn_box_eval_workspace_bytes(int64_t n_kept, int n_area, int n_max, int n_thr);
+int mpn_box_iou_matrix(const double* det_box, const double* det_score, const double* gt_box, const int32_t* gt_flags,
+                       const int64_t* tab_host, const int64_t* tab, int n_row, int max_dets, int32_t* kept_src,
+                       double* kept_score, double* kept_area, int32_t* kept_rank, double* iou, void* stream);
+int mpn_box_accumulate(const double* kept_score, const int32_t* kept_rank, const int32_t* det_match, const int32_t* det_ig,
+                       const int32_t* gt_ig, const int64_t* cat_tab_host, const int64_t* cat_tab, int n_cat, int64_t n_kept,
+                       int64_t n_gt, int n_area, int n_thr, const int32_t* max_dets_host, int n_max, const double* rec_thrs,
+                       int n_rec, int32_t* order, double* precision, double* recall, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

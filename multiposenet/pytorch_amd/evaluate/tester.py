@@ -54,6 +54,7 @@ class TestParams(object):
     batch_size = 32
     print_freq = 20
     gaussian_filt = False             # NMS(..., bool_gaussian_filt=True): smooth every up-sampled peak patch (sigma 3) before its arg-max
+    category_ids = [1]                # detect_images / coco_eval_bbox: class index of the detection head -> COCO category id
 
 
 def resize(img, out_hw, cubic, inv_scale=None):
@@ -111,6 +112,7 @@ class Tester(object):
         self.batch_processor = batch_processor
         self.model = model
         self.last_eval = None             # coco_eval(..., annotations=...): the KeypointEval result dict
+        self.last_box_eval = None         # coco_eval_bbox(...): the BoxEval result dict
         if self.params.ckpt is not None:
             self._load_ckpt(self.params.ckpt)
             logger.info('Load ckpt from {}'.format(self.params.ckpt))
@@ -366,6 +368,63 @@ class Tester(object):
             ev.summarize()
             if not self.params.testresult_write_json:
                 os.remove(ann_filename)
+        return results
+
+    # ------------------------------------------------------------------ detection head: boxes and box AP / AR (not in the reference)
+    def detect_images(self, images, batch=64, max_per_image=None):
+        """Box results of the detection head for COCO's bbox evaluation: ``images`` yields (image_id, file_name, [H, W, 3] BGR array).
+        Every image takes the square-pad / resize / forward_padded_begin / detect_padded path of ``infer_images_batched``; boxes are
+        multiplied by the image's scale in float32 and turned into [x, y, w, h].  One dict {'image_id', 'file_name', 'category_id',
+        'bbox', 'score'} per kept post-NMS row — every row above the model's 0.05 score threshold, in descending score, not only the
+        persons above 0.5 that feed the PRN — with ``params.category_ids[class index]`` as its category.  ``max_per_image`` keeps the
+        best-scored rows of an image."""
+        from .._lib import MpnError
+        cats = [int(c) for c in self.params.category_ids]
+        K = int(self.model.classificationModel.num_classes)
+        if len(cats) != K:
+            raise MpnError("params.category_ids names %d categories, the detection head has %d classes" % (len(cats), K))
+        images = list(images)
+        S = self.params.inp_size
+        out = []
+        for i0 in range(0, len(images), batch):
+            chunk = images[i0:i0 + batch]
+            xs, scales = [], []
+            for _, _, arr in chunk:
+                img = _to_device_image(arr, self.dev)
+                shape_dst = max(img.shape[0], img.shape[1])
+                scales.append(float(shape_dst) / S)
+                pad = abs(img.shape[1] - img.shape[0])
+                sq = torch.zeros((img.shape[0] + pad, img.shape[1] + pad, 3), dtype=torch.float32, device=self.dev)
+                sq[:img.shape[0], :img.shape[1]] = img
+                xs.append(resnet_preprocess(resize(sq[:shape_dst, :shape_dst], (S, S), cubic=False)))
+            with torch.no_grad():
+                _, anchors, cls, keep = self.model.forward_padded_begin(torch.stack(xs))
+            boxes, scores, kept, classes = self.model.detect_padded(anchors, cls, return_class=True)
+            boxes_h, scores_h, classes_h = boxes.cpu().numpy(), scores.cpu().numpy(), classes.cpu().numpy()
+            del keep
+            for li, (image_id, file_name, _) in enumerate(chunk):
+                n = int(kept[li]) if max_per_image is None else min(int(kept[li]), int(max_per_image))
+                b4 = (boxes_h[li, :n] * np.float32(scales[li])).astype(np.float64)       # boxes * scale in float32, as _finish_batch
+                b4[:, 2:] -= b4[:, :2]
+                for j in range(n):
+                    out.append({'image_id': image_id, 'file_name': file_name, 'category_id': cats[int(classes_h[li, j])],
+                                'bbox': b4[j].tolist(), 'score': float(scores_h[li, j])})
+        return out
+
+    def coco_eval_bbox(self, images, annotations, categories=None):
+        """Box AP / AR of the detection head on the device: ``detect_images`` over ``images``, then box_eval.BoxEval(annotations,
+        categories) over the evaluated image ids.  The twelve COCO lines are logged, the result dict is kept in
+        ``self.last_box_eval``; with ``params.testresult_write_json`` the results also go to ``params.coco_result_filename`` (indent 4,
+        as ``coco_eval``), otherwise no file is written.  Returns the result list."""
+        from .box_eval import BoxEval
+        images = list(images)
+        results = self.detect_images(images)
+        if self.params.testresult_write_json:
+            with open(self.params.coco_result_filename, "w") as f:
+                json.dump(results, f, indent=4)
+        ev = BoxEval(annotations, categories=categories)
+        self.last_box_eval = ev.evaluate(results, img_ids=[image_id for image_id, _, _ in images])
+        ev.summarize()
         return results
 
     # ------------------------------------------------------------------ multi-scale + flip (Tester.coco_eval, :143-175)

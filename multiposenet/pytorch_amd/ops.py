@@ -1142,3 +1142,41 @@ def oks_accumulate(kept_score, det_match, det_ig, gt_ig, rec_thrs, out):
     call("mpn_oks_accumulate", p(kept_score), p(det_match), p(det_ig), p(gt_ig), K, G, A, T, ptr(rec_thrs), R, ptr(order), ptr(out),
          ctypes.c_void_p(out.data_ptr() + 8 * T * R * A), ptr(ws), stream_ptr())
     return order[:K]
+
+
+# ---------------------------------------------------------------- box AP / AR (csrc/box_eval.hip; evaluate/box_eval.py packs the arrays)
+def box_iou_matrix(det_box, det_score, gt_box, gt_flags, tab_host, tab, max_dets):
+    """Stage 1: (kept_src i32 [K], kept_score [K], kept_area [K], kept_rank i32 [K], iou [sum kept x G]).  tab_host: contiguous int64
+    numpy [n_row + 1, 4], one row per (category, image) pair; tab: the same table on the device.  The matching of stage 2 is
+    ``oks_match`` on these IoU blocks."""
+    check_device(tab)
+    dev = tab.device
+    n_row = tab_host.shape[0] - 1
+    K, n_iou = int(tab_host[-1, 2]), int(tab_host[-1, 3])
+    kept_src = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)
+    kept_score = torch.empty((max(K, 1),), dtype=torch.float64, device=dev)
+    kept_area = torch.empty((max(K, 1),), dtype=torch.float64, device=dev)
+    kept_rank = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)
+    iou = torch.empty((max(n_iou, 1),), dtype=torch.float64, device=dev)
+    call("mpn_box_iou_matrix", ptr(det_box), ptr(det_score), ptr(gt_box), ptr(gt_flags), ctypes.c_void_p(tab_host.ctypes.data), ptr(tab),
+         n_row, int(max_dets), ptr(kept_src), ptr(kept_score), ptr(kept_area), ptr(kept_rank), ptr(iou), stream_ptr())
+    return kept_src[:K], kept_score[:K], kept_area[:K], kept_rank[:K], iou[:n_iou]
+
+
+def box_accumulate(kept_score, kept_rank, det_match, det_ig, gt_ig, cat_tab_host, cat_tab, max_dets_host, rec_thrs, out):
+    """Stage 3: fills out = float64 [T*R*C*A*M + T*C*A*M] (precision [T, R, C, A, M] then recall [T, C, A, M]) and returns the order
+    [K] of every category's stable descending-score sort.  cat_tab_host: contiguous int64 numpy [C + 1, 2]; max_dets_host:
+    contiguous int32 numpy [M]."""
+    check_device(out)
+    dev = out.device
+    A, T, K = det_match.shape
+    G, R = gt_ig.shape[1], rec_thrs.numel()
+    C, M = cat_tab_host.shape[0] - 1, max_dets_host.shape[0]
+    order = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)
+    ws = workspace(call("mpn_box_eval_workspace_bytes", K, A, M, T), dev, slot=9)
+    one = torch.empty((2,), dtype=torch.float64, device=dev)
+    p = lambda t: ptr(t) if t.numel() else ptr(one)
+    call("mpn_box_accumulate", p(kept_score), p(kept_rank), p(det_match), p(det_ig), p(gt_ig), ctypes.c_void_p(cat_tab_host.ctypes.data),
+         ptr(cat_tab), C, K, G, A, T, ctypes.c_void_p(max_dets_host.ctypes.data), M, ptr(rec_thrs), R, ptr(order), ptr(out),
+         ctypes.c_void_p(out.data_ptr() + 8 * T * R * C * A * M), ptr(ws), stream_ptr())
+    return order[:K]
