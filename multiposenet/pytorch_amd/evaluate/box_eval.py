@@ -7,25 +7,21 @@
     ev.summarize()                                  # logs the twelve lines in COCO's wording
 
 Stands in for ``COCOeval(coco, coco.loadRes(file), 'bbox')`` + evaluate / accumulate / summarize.  pycocotools is not used: the
-published algorithm is restated.  IoU blocks and the per-category accumulation run in csrc/box_eval.hip, the matching in
-csrc/oks_eval.hip (``ops.oks_match``: it matches on any similarity blocks), five launches in all, and only the two result arrays
-come back to the host, in one read.  The constant tables are built here exactly as COCOeval's Params builds them with numpy.
+published algorithm is restated.  IoU blocks, matching and the per-category accumulation run in csrc/coco_eval.hip, the last two in
+the kernels that score keypoints too (``ops.oks_match`` matches on any similarity blocks), five launches in all, and only the two
+result arrays come back to the host, in one read.  The constant tables are built exactly as COCOeval's Params builds them with numpy.
 
 One row of the table is one (category, image) pair with at least one detection or ground truth — COCOeval's evaluateImg returns
 None for the others — ordered category-major, then by ascending image id, so that every category's kept detections and ground
 truths are contiguous.  ``stats`` follows COCOeval._summarizeDets with the LAST ``max_dets`` entry wherever it names 100 or
 ``maxDets[2]`` (the same thing for COCO's list), and the first two entries for AR@1 / AR@10.
 """
-import logging
-
 import numpy as np
 import torch
 
 from .. import ops
 from .._lib import MpnError
-from .oks_eval import iou_thrs, rec_thrs
-
-logger = logging.getLogger("multiposenet")
+from .coco_eval import CocoEval, iou_thrs, mean_valid, rec_thrs  # noqa: F401  (the tables are part of this module's surface)
 
 AREA_RNG = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]      # all, small, medium, large
 AREA_LBL = ['all', 'small', 'medium', 'large']
@@ -46,21 +42,18 @@ def summarize_stats(precision, recall, thrs):
         if thr is not None:
             s = s[np.where(thr == thrs)[0]]
         s = s[:, :, :, a, m] if ap else s[:, :, a, m]
-        return float(np.mean(s[s > -1])) if len(s[s > -1]) else -1.0
+        return mean_valid(s)
     return np.array([one(*row) for row in _stat_rows(precision.shape[4])], dtype=np.float64)
 
 
 def per_category_ap(precision):
     """Mean over the entries > -1 of precision[:, :, k, all areas, last maxDets], or -1, for every category k."""
-    out = np.full((precision.shape[2],), -1.0, dtype=np.float64)
-    for k in range(precision.shape[2]):
-        s = precision[:, :, k, 0, -1]
-        if len(s[s > -1]):
-            out[k] = np.mean(s[s > -1])
-    return out
+    return np.array([mean_valid(precision[:, :, k, 0, -1]) for k in range(precision.shape[2])], dtype=np.float64)
 
 
-class BoxEval(object):
+class BoxEval(CocoEval):
+    GT, CONST = ('gt_box', 'gt_area', 'gt_flags'), {}
+
     def __init__(self, annotations, categories=None, max_dets=(1, 10, 100)):
         md = [int(m) for m in max_dets]
         if not 1 <= len(md) <= 4 or any(not 1 <= m <= 128 for m in md):
@@ -71,8 +64,7 @@ class BoxEval(object):
         self.categories = sorted(set(int(c) for c in categories))            # COCOeval: catIds = np.unique(catIds)
         if not self.categories:
             raise MpnError("no category to evaluate")
-        self.iou_thrs, self.rec_thrs = iou_thrs(), rec_thrs()
-        self.area_rng = np.asarray(AREA_RNG, dtype=np.float64)
+        CocoEval.__init__(self, AREA_RNG)
         # ground truths grouped by category (ascending id), then image (ascending id), annotation order inside a pair
         cpos = {c: k for k, c in enumerate(self.categories)}
         anns = [a for a in annotations if a['category_id'] in cpos]
@@ -90,26 +82,16 @@ class BoxEval(object):
             crowd = 1 if a.get('iscrowd', 0) else 0
             self.gt_flags[row] = (1 if (crowd or a.get('ignore', 0)) else 0) | (crowd << 1)
         self.gt_img_ids = np.unique(np.asarray([a['image_id'] for a in annotations], dtype=np.int64))
-        self._dev = None
-        self.last = None
-        self.debug = None
 
     # ------------------------------------------------------------------ host packing
     def pack(self, results, img_ids=None):
         """Host arrays of one evaluation: (image ids, rows [n_row, 2] = (category index, image id), ground-truth row index, det_box
         [D, 4], det_score [D], tab [n_row + 1, 4], cat_tab [K + 1, 2])."""
-        known = set(self.gt_img_ids.tolist())
-        if img_ids is None:
-            ids = self.gt_img_ids
-        else:
-            ids = np.unique(np.asarray(list(img_ids), dtype=np.int64))
-            known |= set(ids.tolist())
+        ids = self.image_ids(results, img_ids)
         chosen = set(ids.tolist())
         cpos = {c: k for k, c in enumerate(self.categories)}
         per = {}
         for r in results:
-            if r['image_id'] not in known:
-                raise MpnError("result for image %r, which is neither annotated nor in img_ids" % (r['image_id'],))
             k = cpos.get(r['category_id'])
             if k is None or int(r['image_id']) not in chosen:
                 continue
@@ -143,13 +125,6 @@ class BoxEval(object):
         return ids, np.asarray(rows, dtype=np.int64).reshape(-1, 2), np.asarray(gsel, dtype=np.int64), det_box, det_score, tab, cat_tab
 
     # ------------------------------------------------------------------ device
-    def _device_arrays(self, dev):
-        if self._dev is None or self._dev['dev'] != dev:
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            self._dev = {'dev': dev, 'gt_box': up(self.gt_box), 'gt_area': up(self.gt_area), 'gt_flags': up(self.gt_flags),
-                         'iou': up(self.iou_thrs), 'rec': up(self.rec_thrs), 'area_rng': up(self.area_rng)}
-        return self._dev
-
     def evaluate(self, results, img_ids=None, keep_intermediates=False):
         """Returns {'stats': float64[12], 'precision' [T, R, K, A, M], 'recall' [T, K, A, M], 'names', 'per_category_ap': float64[K]}.
         With keep_intermediates the device results of the three stages stay in ``self.debug`` (tests read them)."""
@@ -160,15 +135,7 @@ class BoxEval(object):
         if len(ids) == 0:
             raise MpnError("no image to evaluate")
         T, R, A, M, C = len(self.iou_thrs), len(self.rec_thrs), len(self.area_rng), len(self.max_dets), len(self.categories)
-        c = self._device_arrays(dev)
-        if len(gsel) == len(self.gt_area):
-            gt_box, gt_area, gt_flags = c['gt_box'], c['gt_area'], c['gt_flags']
-        else:
-            sel = torch.from_numpy(gsel).to(dev)
-            gt_box, gt_area, gt_flags = c['gt_box'][sel], c['gt_area'][sel], c['gt_flags'][sel]
-        pad = lambda t: t if t.shape[0] else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-        gt_box, gt_area, gt_flags = pad(gt_box), pad(gt_area), pad(gt_flags)
-        d_box, d_score = pad(torch.from_numpy(det_box).to(dev)), pad(torch.from_numpy(det_score).to(dev))
+        c, (gt_box, gt_area, gt_flags), (d_box, d_score) = self.device_inputs(dev, gsel, det_box, det_score)
         tab_d, cat_tab_d = torch.from_numpy(tab).to(dev), torch.from_numpy(cat_tab).to(dev)
         md = np.asarray(self.max_dets, dtype=np.int32)
         out = torch.empty((T * R * C * A * M + T * C * A * M,), dtype=torch.float64, device=dev)
@@ -194,21 +161,5 @@ class BoxEval(object):
                           'gt_ig': gt_ig, 'gt_match': gt_match, 'order': order}
         return self.last
 
-    def summary_lines(self, stats):
-        """COCOeval.summarize's twelve lines for ``stats``."""
-        fmt = ' {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}'
-        lines = []
-        for (ap, thr, a, m), v in zip(_stat_rows(len(self.max_dets)), stats):
-            title, typ = ('Average Precision', '(AP)') if ap else ('Average Recall', '(AR)')
-            iou = '{:0.2f}:{:0.2f}'.format(self.iou_thrs[0], self.iou_thrs[-1]) if thr is None else '{:0.2f}'.format(thr)
-            lines.append(fmt.format(title, typ, iou, AREA_LBL[a], self.max_dets[m], v))
-        return lines
-
-    def summarize(self):
-        """COCOeval.summarize for boxes: the twelve lines, logged."""
-        if self.last is None:
-            raise MpnError("summarize() before evaluate()")
-        lines = self.summary_lines(self.last['stats'])
-        for line in lines:
-            logger.info(line)
-        return lines
+    def stat_rows(self):
+        return [(ap, thr, AREA_LBL[a], self.max_dets[m]) for ap, thr, a, m in _stat_rows(len(self.max_dets))]

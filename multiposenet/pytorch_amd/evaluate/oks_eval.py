@@ -7,30 +7,20 @@
 
 Stands in for ``COCOeval(coco, coco.loadRes(file), 'keypoints')`` + evaluate / accumulate / summarize of the reference
 (evaluate/tester.py:179-186).  pycocotools is not used: the published algorithm is restated, OKS, matching and accumulation run in
-csrc/oks_eval.hip (three stages, four launches), and only the two result arrays come back to the host, in one read.  The constant
-tables are built here exactly as COCOeval's Params builds them with numpy and handed to the kernels.
+csrc/coco_eval.hip (three stages, four launches), and only the two result arrays come back to the host, in one read.  The constant
+tables are built here exactly as COCOeval's Params builds them with numpy and handed to the kernels.  What the box metric needs as
+well is CocoEval's (coco_eval.py).
 """
-import logging
-
 import numpy as np
 import torch
 
 from .. import ops
 from .._lib import MpnError
-
-logger = logging.getLogger("multiposenet")
+from .coco_eval import CocoEval, iou_thrs, mean_valid, rec_thrs  # noqa: F401  (the tables are part of this module's surface)
 
 SIGMAS = np.array([.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89]) / 10.0
 AREA_RNG = [[0 ** 2, 1e5 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]            # all, medium, large
 NAMES = ['AP', 'AP50', 'AP75', 'APm', 'APl', 'AR', 'AR50', 'AR75', 'ARm', 'ARl']
-
-
-def iou_thrs():
-    return np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)
-
-
-def rec_thrs():
-    return np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
 
 
 def summarize_stats(precision, recall, thrs):
@@ -40,11 +30,13 @@ def summarize_stats(precision, recall, thrs):
         if thr is not None:
             s = s[np.where(thr == thrs)[0]]
         s = s[:, :, a] if ap else s[:, a]
-        return float(np.mean(s[s > -1])) if len(s[s > -1]) else -1.0
+        return mean_valid(s)
     return np.array([one(ap, thr, a) for ap in (1, 0) for thr, a in ((None, 0), (.5, 0), (.75, 0), (None, 1), (None, 2))], dtype=np.float64)
 
 
-class KeypointEval(object):
+class KeypointEval(CocoEval):
+    GT, CONST = ('gt_kp', 'gt_area', 'gt_bbox', 'gt_flags'), {'var': 'var'}
+
     def __init__(self, annotations, max_dets=20, sigmas=None):
         if not 1 <= int(max_dets) <= 128:
             raise MpnError("max_dets must be in 1..128")
@@ -53,8 +45,7 @@ class KeypointEval(object):
         if sig.shape != (17,):
             raise MpnError("sigmas must hold 17 values")
         self.var = (sig * 2) ** 2
-        self.iou_thrs, self.rec_thrs = iou_thrs(), rec_thrs()
-        self.area_rng = np.asarray(AREA_RNG, dtype=np.float64)
+        CocoEval.__init__(self, AREA_RNG)
         # ground truths of category 1, grouped by image (ascending id), annotation order inside an image
         anns = [a for a in annotations if a.get('category_id', 1) == 1]
         ids = np.asarray([a['image_id'] for a in anns], dtype=np.int64)
@@ -74,24 +65,14 @@ class KeypointEval(object):
             crowd = 1 if a.get('iscrowd', 0) else 0
             nk = a['num_keypoints'] if 'num_keypoints' in a else int((self.gt_kp[row, :, 2] > 0).sum())
             self.gt_flags[row] = (1 if (crowd or nk == 0) else 0) | (crowd << 1)
-        self._dev = None
-        self.last = None
-        self.debug = None
 
     # ------------------------------------------------------------------ host packing
     def pack(self, results, img_ids=None):
         """Host arrays of one evaluation: (image ids, ground-truth row index, det_kp [D, 17, 3], det_score [D], img_tab [I + 1, 4])."""
-        known = set(self.gt_img_ids.tolist())
-        if img_ids is None:
-            ids = self.gt_img_ids
-        else:
-            ids = np.unique(np.asarray(list(img_ids), dtype=np.int64))
-            known |= set(ids.tolist())
+        ids = self.image_ids(results, img_ids)
         pos = {int(v): i for i, v in enumerate(ids)}
         per = [[] for _ in ids]
         for r in results:
-            if r['image_id'] not in known:
-                raise MpnError("result for image %r, which is neither annotated nor in img_ids" % (r['image_id'],))
             if r.get('category_id', 1) != 1:
                 continue
             i = pos.get(int(r['image_id']))
@@ -122,14 +103,6 @@ class KeypointEval(object):
         return ids, gsel, det_kp, det_score, tab
 
     # ------------------------------------------------------------------ device
-    def _device_arrays(self, dev):
-        if self._dev is None or self._dev['dev'] != dev:
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            self._dev = {'dev': dev, 'gt_kp': up(self.gt_kp), 'gt_area': up(self.gt_area), 'gt_bbox': up(self.gt_bbox),
-                         'gt_flags': up(self.gt_flags), 'var': up(self.var), 'iou': up(self.iou_thrs), 'rec': up(self.rec_thrs),
-                         'area_rng': up(self.area_rng)}
-        return self._dev
-
     def evaluate(self, results, img_ids=None, keep_intermediates=False):
         """Returns {'stats': float64[10], 'precision' [T, R, A], 'recall' [T, A], 'names'}.  With keep_intermediates the device
         results of the three stages stay in ``self.debug`` (tests read them)."""
@@ -140,15 +113,7 @@ class KeypointEval(object):
         T, R, A = len(self.iou_thrs), len(self.rec_thrs), len(self.area_rng)
         if len(ids) == 0:
             raise MpnError("no image to evaluate")
-        c = self._device_arrays(dev)
-        if len(gsel) == len(self.gt_area):
-            gt_kp, gt_area, gt_bbox, gt_flags = c['gt_kp'], c['gt_area'], c['gt_bbox'], c['gt_flags']
-        else:
-            sel = torch.from_numpy(gsel).to(dev)
-            gt_kp, gt_area, gt_bbox, gt_flags = c['gt_kp'][sel], c['gt_area'][sel], c['gt_bbox'][sel], c['gt_flags'][sel]
-        pad = lambda t: t if t.shape[0] else torch.zeros((1,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev)
-        gt_kp, gt_area, gt_bbox, gt_flags = pad(gt_kp), pad(gt_area), pad(gt_bbox), pad(gt_flags)
-        d_kp, d_score = pad(torch.from_numpy(det_kp).to(dev)), pad(torch.from_numpy(det_score).to(dev))
+        c, (gt_kp, gt_area, gt_bbox, gt_flags), (d_kp, d_score) = self.device_inputs(dev, gsel, det_kp, det_score)
         tab_d = torch.from_numpy(tab).to(dev)
         out = torch.empty((T * R * A + T * A,), dtype=torch.float64, device=dev)
         kept_src, kept_score, kept_area, oks = ops.oks_matrix(d_kp, d_score, gt_kp, gt_area, gt_bbox, tab, tab_d, self.max_dets, c['var'])
@@ -165,17 +130,6 @@ class KeypointEval(object):
                           'det_match': det_match, 'det_ig': det_ig, 'gt_ig': gt_ig, 'gt_match': gt_match, 'order': order}
         return self.last
 
-    def summarize(self):
-        """COCOeval.summarize for keypoints: the ten lines, logged."""
-        if self.last is None:
-            raise MpnError("summarize() before evaluate()")
-        fmt = ' {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}'
-        rows = [(None, 'all'), (.5, 'all'), (.75, 'all'), (None, 'medium'), (None, 'large')]
-        lines = []
-        for k, v in enumerate(self.last['stats']):
-            thr, area = rows[k % 5]
-            title, typ = ('Average Precision', '(AP)') if k < 5 else ('Average Recall', '(AR)')
-            iou = '{:0.2f}:{:0.2f}'.format(self.iou_thrs[0], self.iou_thrs[-1]) if thr is None else '{:0.2f}'.format(thr)
-            lines.append(fmt.format(title, typ, iou, area, self.max_dets, v))
-            logger.info(lines[-1])
-        return lines
+    def stat_rows(self):
+        return [(ap, thr, area, self.max_dets) for ap in (1, 0)
+                for thr, area in ((None, 'all'), (.5, 'all'), (.75, 'all'), (None, 'medium'), (None, 'large'))]

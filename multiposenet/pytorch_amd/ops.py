@@ -1093,25 +1093,51 @@ def score_filter(boxes0, scores0, thresh):
     return dets[:n], src[:n]
 
 
-# ---------------------------------------------------------------- keypoint AP / AR (csrc/oks_eval.hip; evaluate/oks_eval.py packs the arrays)
+# ---------------------------------------------------------------- keypoint and box AP / AR (csrc/coco_eval.hip; evaluate/oks_eval.py and
+# evaluate/box_eval.py pack the arrays)
+def _stage1_outputs(tab_host, tab, ranked):
+    """Buffers of a stage 1 over the rows of tab_host: kept_src i32, kept_score, kept_area (, kept_rank i32 if ranked) [K] and the
+    similarity blocks [sum kept x G], none of them empty, and their views of the true lengths."""
+    check_device(tab)
+    K, n_sim = int(tab_host[-1, 2]), int(tab_host[-1, 3])
+    kinds = [(K, torch.int32), (K, torch.float64), (K, torch.float64)] + [(K, torch.int32)] * ranked + [(n_sim, torch.float64)]
+    bufs = [torch.empty((max(n, 1),), dtype=dt, device=tab.device) for n, dt in kinds]
+    return bufs, tuple(b[:n] for b, (n, _) in zip(bufs, kinds))
+
+
+def _or_spare(dev):
+    """p(t): the address of t, or of a spare allocation if t is empty and has none to hand over."""
+    one = torch.empty((2,), dtype=torch.float64, device=dev)
+    return lambda t: ptr(t) if t.numel() else ptr(one)
+
+
+def _stage3_buffers(out, K, ws_bytes):
+    """(order buffer i32 [max(K, 1)], workspace, p as _or_spare) of an accumulate into ``out``."""
+    check_device(out)
+    return torch.empty((max(K, 1),), dtype=torch.int32, device=out.device), workspace(ws_bytes, out.device, slot=9), _or_spare(out.device)
+
+
 def oks_matrix(det_kp, det_score, gt_kp, gt_area, gt_bbox, tab_host, tab, max_dets, var):
     """Stage 1: (kept_src i32 [K], kept_score [K], kept_area [K], oks [sum kept x G]).  tab_host: contiguous int64 numpy
     [n_img + 1, 4]; tab: the same table on the device."""
-    check_device(tab)
-    dev = tab.device
-    n_img = tab_host.shape[0] - 1
-    K, n_oks = int(tab_host[-1, 2]), int(tab_host[-1, 3])
-    kept_src = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)
-    kept_score = torch.empty((max(K, 1),), dtype=torch.float64, device=dev)
-    kept_area = torch.empty((max(K, 1),), dtype=torch.float64, device=dev)
-    oks = torch.empty((max(n_oks, 1),), dtype=torch.float64, device=dev)
+    bufs, res = _stage1_outputs(tab_host, tab, ranked=False)
     call("mpn_oks_matrix", ptr(det_kp), ptr(det_score), ptr(gt_kp), ptr(gt_area), ptr(gt_bbox), ctypes.c_void_p(tab_host.ctypes.data),
-         ptr(tab), n_img, int(max_dets), ptr(var), ptr(kept_src), ptr(kept_score), ptr(kept_area), ptr(oks), stream_ptr())
-    return kept_src[:K], kept_score[:K], kept_area[:K], oks[:n_oks]
+         ptr(tab), tab_host.shape[0] - 1, int(max_dets), ptr(var), *[ptr(b) for b in bufs], stream_ptr())
+    return res
+
+
+def box_iou_matrix(det_box, det_score, gt_box, gt_flags, tab_host, tab, max_dets):
+    """Stage 1: (kept_src i32 [K], kept_score [K], kept_area [K], kept_rank i32 [K], iou [sum kept x G]).  tab_host: contiguous int64
+    numpy [n_row + 1, 4], one row per (category, image) pair; tab: the same table on the device.  The matching of stage 2 is
+    ``oks_match`` on these IoU blocks."""
+    bufs, res = _stage1_outputs(tab_host, tab, ranked=True)
+    call("mpn_box_iou_matrix", ptr(det_box), ptr(det_score), ptr(gt_box), ptr(gt_flags), ctypes.c_void_p(tab_host.ctypes.data), ptr(tab),
+         tab_host.shape[0] - 1, int(max_dets), *[ptr(b) for b in bufs], stream_ptr())
+    return res
 
 
 def oks_match(oks, kept_area, gt_area, gt_flags, tab_host, tab, max_dets, area_rng, iou_thrs):
-    """Stage 2: (det_match [A, T, K], det_ig [A, T, K], gt_ig [A, G], gt_match [A, T, G]), int32."""
+    """Stage 2, on OKS or IoU blocks: (det_match [A, T, K], det_ig [A, T, K], gt_ig [A, G], gt_match [A, T, G]), int32."""
     check_device(tab)
     dev = tab.device
     n_img = tab_host.shape[0] - 1
@@ -1121,8 +1147,7 @@ def oks_match(oks, kept_area, gt_area, gt_flags, tab_host, tab, max_dets, area_r
     det_ig = torch.empty((A, T, K), dtype=torch.int32, device=dev)
     gt_ig = torch.empty((A, G), dtype=torch.int32, device=dev)
     gt_match = torch.empty((A, T, G), dtype=torch.int32, device=dev)
-    one = torch.empty((1,), dtype=torch.int32, device=dev)       # an empty tensor has no address to hand over
-    p = lambda t: ptr(t) if t.numel() else ptr(one)
+    p = _or_spare(dev)
     call("mpn_oks_match", p(oks), p(kept_area), ptr(gt_area), ptr(gt_flags), ctypes.c_void_p(tab_host.ctypes.data), ptr(tab), n_img,
          int(max_dets), ptr(area_rng), A, ptr(iou_thrs), T, p(det_match), p(det_ig), p(gt_ig), p(gt_match), stream_ptr())
     return det_match, det_ig, gt_ig, gt_match
@@ -1131,51 +1156,22 @@ def oks_match(oks, kept_area, gt_area, gt_flags, tab_host, tab, max_dets, area_r
 def oks_accumulate(kept_score, det_match, det_ig, gt_ig, rec_thrs, out):
     """Stage 3: fills out = float64 [T*R*A + T*A] (precision [T, R, A] then recall [T, A]) and returns the order [K] of the stable
     descending-score sort over all images."""
-    check_device(out)
-    dev = out.device
     A, T, K = det_match.shape
     G, R = gt_ig.shape[1], rec_thrs.numel()
-    order = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)
-    ws = workspace(call("mpn_oks_eval_workspace_bytes", K, A, T), dev, slot=9)
-    one = torch.empty((2,), dtype=torch.float64, device=dev)
-    p = lambda t: ptr(t) if t.numel() else ptr(one)
+    order, ws, p = _stage3_buffers(out, K, call("mpn_oks_eval_workspace_bytes", K, A, T))
     call("mpn_oks_accumulate", p(kept_score), p(det_match), p(det_ig), p(gt_ig), K, G, A, T, ptr(rec_thrs), R, ptr(order), ptr(out),
          ctypes.c_void_p(out.data_ptr() + 8 * T * R * A), ptr(ws), stream_ptr())
     return order[:K]
-
-
-# ---------------------------------------------------------------- box AP / AR (csrc/box_eval.hip; evaluate/box_eval.py packs the arrays)
-def box_iou_matrix(det_box, det_score, gt_box, gt_flags, tab_host, tab, max_dets):
-    """Stage 1: (kept_src i32 [K], kept_score [K], kept_area [K], kept_rank i32 [K], iou [sum kept x G]).  tab_host: contiguous int64
-    numpy [n_row + 1, 4], one row per (category, image) pair; tab: the same table on the device.  The matching of stage 2 is
-    ``oks_match`` on these IoU blocks."""
-    check_device(tab)
-    dev = tab.device
-    n_row = tab_host.shape[0] - 1
-    K, n_iou = int(tab_host[-1, 2]), int(tab_host[-1, 3])
-    kept_src = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)
-    kept_score = torch.empty((max(K, 1),), dtype=torch.float64, device=dev)
-    kept_area = torch.empty((max(K, 1),), dtype=torch.float64, device=dev)
-    kept_rank = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)
-    iou = torch.empty((max(n_iou, 1),), dtype=torch.float64, device=dev)
-    call("mpn_box_iou_matrix", ptr(det_box), ptr(det_score), ptr(gt_box), ptr(gt_flags), ctypes.c_void_p(tab_host.ctypes.data), ptr(tab),
-         n_row, int(max_dets), ptr(kept_src), ptr(kept_score), ptr(kept_area), ptr(kept_rank), ptr(iou), stream_ptr())
-    return kept_src[:K], kept_score[:K], kept_area[:K], kept_rank[:K], iou[:n_iou]
 
 
 def box_accumulate(kept_score, kept_rank, det_match, det_ig, gt_ig, cat_tab_host, cat_tab, max_dets_host, rec_thrs, out):
     """Stage 3: fills out = float64 [T*R*C*A*M + T*C*A*M] (precision [T, R, C, A, M] then recall [T, C, A, M]) and returns the order
     [K] of every category's stable descending-score sort.  cat_tab_host: contiguous int64 numpy [C + 1, 2]; max_dets_host:
     contiguous int32 numpy [M]."""
-    check_device(out)
-    dev = out.device
     A, T, K = det_match.shape
     G, R = gt_ig.shape[1], rec_thrs.numel()
     C, M = cat_tab_host.shape[0] - 1, max_dets_host.shape[0]
-    order = torch.empty((max(K, 1),), dtype=torch.int32, device=dev)
-    ws = workspace(call("mpn_box_eval_workspace_bytes", K, A, M, T), dev, slot=9)
-    one = torch.empty((2,), dtype=torch.float64, device=dev)
-    p = lambda t: ptr(t) if t.numel() else ptr(one)
+    order, ws, p = _stage3_buffers(out, K, call("mpn_box_eval_workspace_bytes", K, A, M, T))
     call("mpn_box_accumulate", p(kept_score), p(kept_rank), p(det_match), p(det_ig), p(gt_ig), ctypes.c_void_p(cat_tab_host.ctypes.data),
          ptr(cat_tab), C, K, G, A, T, ctypes.c_void_p(max_dets_host.ctypes.data), M, ptr(rec_thrs), R, ptr(order), ptr(out),
          ctypes.c_void_p(out.data_ptr() + 8 * T * R * C * A * M), ptr(ws), stream_ptr())

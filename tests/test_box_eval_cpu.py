@@ -1,6 +1,6 @@
 """Box AP / AR evaluation, CPU tier: the numpy restatement of the published COCOeval(iouType='bbox') algorithm
 (tests/box_eval_ref.py) pinned by hand-derived values, the modelled misreadings it must tell apart, the C-ABI surface of
-csrc/box_eval.hip, the host packing of evaluate/box_eval.py and the summary lines.  pycocotools is not available where this suite
+csrc/coco_eval.hip, the host packing of evaluate/box_eval.py and the summary lines.  pycocotools is not available where this suite
 is built: parity is against the algorithm as published and the hand-derived pins; the live comparison runs where it imports."""
 import ctypes
 import logging
@@ -176,8 +176,25 @@ def test_new_entry_points_are_declared_exported_and_bound():
         assert nargs == len(_lib.SIGNATURES[name][1]), name
     assert "maskApi.c:bbIou" in text and "COCOeval(coco, res, 'bbox')" in text
     mk = open(os.path.join(ROOT, "multiposenet", "pytorch_amd", "csrc", "Makefile")).read()
-    assert re.search(r"^SRCS = .*\bbox_eval\.hip\b", mk, flags=re.M)
-    assert re.search(r"box_eval\.o:.*\n\t.*-ffp-contract=off", mk) and re.search(r"filter \$\*,[^)]*\bbox_eval\b", mk)
+    assert re.search(r"^SRCS = .*\bcoco_eval\.hip\b", mk, flags=re.M) and re.search(r"^FP_STRICT = .*\bcoco_eval\b", mk, flags=re.M)
+    assert re.search(r"\$\(FP_STRICT:=\.o\):.*\n\t.*-ffp-contract=off", mk) and re.search(r"filter \$\*,\$\(FP_STRICT\)\),-ffp-contract=off", mk)
+
+
+def test_the_library_holds_one_rank_and_one_accumulate_kernel():
+    """Keypoints and boxes share stages 2 and 3: the evaluation kernels of the production library are the two similarity front ends,
+    the match, one rank sort and one accumulate."""
+    import sys
+    from multiposenet.pytorch_amd import _lib
+    tools = os.path.join(ROOT, "tools")
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    import codeobj
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    names = [k["name"] for k in codeobj.kernels(_lib.LIB_PATH)]
+    base = [n[m.end():m.end() + int(m.group(1))] for n in names for m in [re.match(r"^_ZN12_GLOBAL__N_1(\d+)", n)] if m]
+    found = sorted(b for b in base if re.match(r"^(oks_|coco_|box_(iou|rank|accum))", b))
+    assert found == ['box_iou_kernel', 'coco_accum_kernel', 'coco_rank_kernel', 'oks_match_kernel', 'oks_matrix_kernel'], found
 
 
 def test_bad_arguments_return_badarg_without_a_gpu():

@@ -1,4 +1,4 @@
-"""Box AP / AR evaluation on the device (csrc/box_eval.hip and the matching of csrc/oks_eval.hip through evaluate/box_eval.py)
+"""Box AP / AR evaluation on the device (csrc/coco_eval.hip through evaluate/box_eval.py)
 against the numpy restatement of the published algorithm (tests/box_eval_ref.py) on the same inputs.  Everything is compared bit
 for bit, no tolerance and no excluded case: the IoU stage is IEEE + - * / and min / max in the order of maskApi.c:bbIou on both
 sides, the matching compares those equal values, precision and recall are IEEE divisions of equal integers, and the twelve stats
@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import box_eval_ref as R
+import oks_eval_ref as K
 from helpers import report
 
 pytestmark = pytest.mark.gpu
@@ -123,6 +124,55 @@ def test_errors_raise():
     _same_result(out, R.evaluate(anns, res))
     empty = BoxEval(anns).evaluate([], img_ids=[3])                                      # no pair has anything: every entry is -1
     assert (empty['stats'] == -1).all() and (empty['precision'] == -1).all()
+
+
+def _kept_1100():
+    anns, res = K.random_set(7, 60, (1, 5), (19, 20))                                    # <= 20 per image: every detection is kept
+    return anns, res[:1100]
+
+
+# name -> (annotations, keypoint results): (a) 1 100 kept detections over 60 images with tied scores, one chunk past 1024;
+# (b) no detection at all beside ground truths; (c) every ground truth below 32^2, so the medium and large ranges have npig == 0
+ONE_CATEGORY = {'kept_1100': _kept_1100, 'no_detection': lambda: (K.random_set(2, 40)[0], []), 'small_only': K.small_only_set}
+
+
+@pytest.mark.parametrize("name", sorted(ONE_CATEGORY))
+def test_keypoint_and_box_accumulate_agree_on_one_category(name):
+    """mpn_oks_accumulate is mpn_box_accumulate with one category, one maxDets entry and nothing sliced off: on the same stage-2
+    results both give the same order, precision and recall, bit for bit."""
+    from multiposenet.pytorch_amd import ops
+    from multiposenet.pytorch_amd.evaluate.oks_eval import KeypointEval
+    anns, res = ONE_CATEGORY[name]()
+    ev = KeypointEval(anns)
+    ev.evaluate(res, keep_intermediates=True)
+    d = ev.debug
+    tab = d['tab']
+    n_kept, G = int(tab[-1, 2]), int(tab[-1, 1])
+    A, T, R_ = len(ev.area_rng), len(ev.iou_thrs), len(ev.rec_thrs)
+    rec = torch.from_numpy(ev.rec_thrs).cuda()
+    out_k, out_b = (torch.full((T * R_ * A + T * A,), 7.0, dtype=torch.float64, device="cuda") for _ in range(2))
+    order_k = ops.oks_accumulate(d['kept_score'], d['det_match'], d['det_ig'], d['gt_ig'], rec, out_k)
+    rank = np.concatenate([np.arange(n) for n in np.diff(tab[:, 2])] + [np.zeros(0)]).astype(np.int32)
+    cat_tab = np.array([[0, 0], [n_kept, G]], dtype=np.int64)
+    order_b = ops.box_accumulate(d['kept_score'], torch.from_numpy(rank).cuda(), d['det_match'], d['det_ig'], d['gt_ig'], cat_tab,
+                                 torch.from_numpy(cat_tab).cuda(), np.array([ev.max_dets], dtype=np.int32), rec, out_b)
+    hk, hb = out_k.cpu().numpy(), out_b.cpu().numpy()
+    pk, rk = hk[:T * R_ * A].reshape(T, R_, A), hk[T * R_ * A:].reshape(T, A)
+    pb, rb = hb[:T * R_ * A].reshape(T, R_, 1, A, 1), hb[T * R_ * A:].reshape(T, 1, A, 1)
+    line = "accumulate, one category, %-12s kept %d gts %d: recall[0] %s" % (name, n_kept, G, np.array2string(rk[0], precision=4))
+    print(line)
+    report(line)
+    assert order_k.shape == order_b.shape == (n_kept,) and torch.equal(order_k, order_b)
+    assert np.array_equal(_bits(pk), _bits(pb.reshape(T, R_, A))) and np.array_equal(_bits(rk), _bits(rb.reshape(T, A)))
+    assert not (hk == 7.0).any()                                                         # every entry was written
+    score = d['kept_score'].cpu().numpy()
+    if name == 'kept_1100':
+        assert n_kept == 1100 and len(ev.gt_img_ids) > 50 and len(set(score.tolist())) < 50 and (rk[:, 0] > 0).all()
+        assert sorted(order_k.cpu().tolist()) == list(range(1100))
+    elif name == 'no_detection':
+        assert n_kept == 0 and G > 0 and (pk[:, :, 0] == 0).all() and (rk[:, 0] == 0).all()
+    else:
+        assert n_kept > 0 and (pk[:, :, 1:] == -1).all() and (rk[:, 1:] == -1).all() and (rk[:, 0] > 0).all()
 
 
 def _lift_scores(model, S, per_image=40.0):

@@ -1,6 +1,6 @@
 """Keypoint AP / AR evaluation, CPU tier: the numpy restatement of the published COCOeval(iouType='keypoints') algorithm
 (tests/oks_eval_ref.py) pinned by hand-derived values, the modelled misreadings it must tell apart, the margin condition the GPU
-comparisons rely on, the C-ABI surface of csrc/oks_eval.hip and the host packing of evaluate/oks_eval.py.  pycocotools is not
+comparisons rely on, the C-ABI surface of csrc/coco_eval.hip and the host packing of evaluate/oks_eval.py.  pycocotools is not
 available here: parity is against the algorithm as published and the hand-derived pins, not against the live library."""
 import ctypes
 import os
@@ -143,7 +143,8 @@ def test_new_entry_points_are_declared_exported_and_bound():
         assert nargs == len(_lib.SIGNATURES[name][1]), name
     assert "evaluate/tester.py:179-186" in open(os.path.join(ROOT, "include", "mpn.h")).read()
     mk = open(os.path.join(ROOT, "multiposenet", "pytorch_amd", "csrc", "Makefile")).read()
-    assert re.search(r"oks_eval\.o:.*\n\t.*-ffp-contract=off", mk) and re.search(r"filter \$\*,[^)]*\boks_eval\b", mk)
+    assert re.search(r"^FP_STRICT = .*\bcoco_eval\b", mk, flags=re.M)
+    assert re.search(r"\$\(FP_STRICT:=\.o\):.*\n\t.*-ffp-contract=off", mk) and re.search(r"filter \$\*,\$\(FP_STRICT\)\),-ffp-contract=off", mk)
 
 
 def test_bad_arguments_return_badarg_without_a_gpu():

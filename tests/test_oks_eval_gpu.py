@@ -1,4 +1,4 @@
-"""Keypoint AP / AR evaluation on the device (csrc/oks_eval.hip through evaluate/oks_eval.py) against the numpy restatement of the
+"""Keypoint AP / AR evaluation on the device (csrc/coco_eval.hip through evaluate/oks_eval.py) against the numpy restatement of the
 published algorithm (tests/oks_eval_ref.py) on the same inputs.  OKS blocks to 1e-12 absolute (both sides: a double exp good to
 about an ulp, <= 0.37 * 3 eps of propagated argument error per term, a mean of <= 17 terms: below 1e-14); orders, truncation,
 areas, every flag and match identical (test_oks_eval_cpu.py asserts the margin condition that makes the comparisons take the same

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Device time of the box-evaluation stages (csrc/box_eval.hip + the matching of csrc/oks_eval.hip) at validation-set scale, next to
+"""Device time of the box-evaluation stages (csrc/coco_eval.hip) at validation-set scale, next to
 the host time of the numpy restatement (tests/box_eval_ref.py) on a subset.
 
     python tools/box_eval_profile.py --out profiles/box_eval_stages.json [--images 5000] [--subset 50] [--reps 20]

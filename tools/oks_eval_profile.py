@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Device time of the three keypoint-evaluation stages (csrc/oks_eval.hip) at validation-set scale, next to the host time of the
+"""Device time of the three keypoint-evaluation stages (csrc/coco_eval.hip) at validation-set scale, next to the host time of the
 numpy restatement (tests/oks_eval_ref.py) on a subset.
 
     python tools/oks_eval_profile.py --out profiles/oks_eval_stages.json [--images 5000] [--subset 200] [--reps 20]
