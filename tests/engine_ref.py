@@ -14,6 +14,16 @@ A SECTION is a piece of R50 that the engine runs through its own composition met
   S6            keypoint head with the intermediate heads on four 256-channel leaves at 16x8, 8x4, 4x2, 2x1
   S7K1 / S7K3   detection head on five 256-channel leaves (8x4, 4x2, 2x1, 1x1, 1x1), K = 1 / K = 3 classes
 
+Every level of those is exactly twice the next.  The ODD sections run the same composition (parameters, units, trainable sets,
+configurations, routes and exact properties are those of their BASE section: ``base``) at the sizes an image that is no multiple of
+32 gives, where the top-down up-sample goes to the lateral's exact size (factor not 2), conv6 / conv7 give ceil-sized levels and the
+max-pool windows hang over the edges.  Detection path only: the reference's keypoint head needs exact x2 / x4 / x8 maps.
+
+  S1o           S1 on an image [2, 3, 19, 13]: stem 10x7, pool 5x4
+  S5o           S5 on the stage sizes of a 75x40 image: leaves [2, 2048, 3, 2], c4 [2, 1024, 5, 3], c3 [2, 512, 10, 5],
+                c2 [2, 256, 19, 10]; up-samples 3->5->10->19 by 2->3->5->10; p6 2x1, p7 1x1
+  S7K1o         S7K1 on the five levels S5o's detection pyramid gives: 10x5, 5x3, 3x2, 2x1, 1x1 (74 cells, 666 anchors per image)
+
 A CONFIGURATION is a trainable set plus a BatchNorm mode (CONFIGS).  S6 / S7 hold no BatchNorm layer, so A (batch statistics) and C
 (BatchNorm affine frozen) are the same run as B there and are not listed twice.
 
@@ -36,8 +46,20 @@ FACTOR = 16.0
 FLOOR = 4.0 * 2.0 ** -24
 BF16_GATES = {"out": 2e-3, "dx": 3e-2, "dx_towers": 8e-2, "dw": 5e-2}       # the gates of the two teacher-forced bf16 tests, unchanged
 
-SECTIONS = ("S1", "S2", "S3", "S4", "S5", "S6", "S7K1", "S7K3")
+SECTIONS = ("S1", "S2", "S3", "S4", "S5", "S6", "S7K1", "S7K3", "S1o", "S5o", "S7K1o")
+_BASE = {"S1o": "S1", "S5o": "S5", "S7K1o": "S7K1"}
 B = 2
+
+
+def base(section):
+    """The section whose composition ``section`` runs: itself, or for an odd-size section the one it re-sizes."""
+    return _BASE.get(section, section)
+
+
+def _with_odd(table):
+    """``table`` (keyed by section) with every odd-size section given its base section's entry."""
+    table.update({o: table[b] for o, b in _BASE.items() if b in table})
+    return table
 
 
 # ------------------------------------------------------------------------------------------------ parameters of a section
@@ -67,6 +89,7 @@ def _tower(p, cout):
 
 def section_shapes(section):
     """Ordered state-dict entries (name, shape) the section reads."""
+    section = base(section)
     if section == "S1":
         return [("fpn.conv1.weight", (64, 3, 7, 7))] + _bn_names("fpn.bn1", 64) + _block("fpn.layer1.0", 64, 64, True) \
             + _block("fpn.layer1.1", 256, 64, False)
@@ -94,7 +117,7 @@ def section_shapes(section):
 
 
 def num_classes(section):
-    return 3 if section == "S7K3" else 1
+    return 3 if base(section) == "S7K3" else 1
 
 
 def is_stat(name):
@@ -110,7 +133,7 @@ def param_names(section):
 
 
 def has_bn(section):
-    return section in ("S1", "S2", "S3", "S4", "S5")
+    return base(section) in ("S1", "S2", "S3", "S4", "S5")
 
 
 def gen_state(section, dtype=F64):
@@ -130,7 +153,7 @@ CONFIGS = {
     "F": ("none", "frozen", True),
     "G": ("all", "frozen", True),          # ... and some outputs get no gradient (G_VARIANTS)
 }
-G_VARIANTS = {"S5": ("kp", "det"), "S6": ("pred",), "S7K1": ("reg", "cls"), "S7K3": ("reg", "cls")}
+G_VARIANTS = _with_odd({"S5": ("kp", "det"), "S6": ("pred",), "S7K1": ("reg", "cls"), "S7K3": ("reg", "cls")})
 
 _UNITS = {
     "S1": (("fpn.conv1.", "fpn.bn1."), ("fpn.layer1.1.",)),
@@ -143,6 +166,7 @@ _UNITS = {
     "S7K1": (("regressionModel.conv1.", "classificationModel.conv1."), ("regressionModel.output.", "classificationModel.output.")),
 }
 _UNITS["S7K3"] = _UNITS["S7K1"]
+_with_odd(_UNITS)
 
 
 def trainable_set(section, cfg):
@@ -189,6 +213,9 @@ SEEDS = {
     ("S5", "batch"): 3, ("S5", "frozen"): 0,
     ("S6", "frozen"): 0,
     ("S7K1", "frozen"): 36, ("S7K3", "frozen"): 11,
+    ("S1o", "batch"): 8, ("S1o", "frozen"): 0,
+    ("S5o", "batch"): 2, ("S5o", "frozen"): 1,
+    ("S7K1o", "frozen"): 216,
 }
 
 
@@ -226,29 +253,44 @@ _LEAVES = {
     "S5": ((2048, 2, 1), (1024, 4, 2), (512, 8, 4), (256, 16, 8)),          # input of layer4.2, c4, c3, c2
     "S6": ((256, 16, 8), (256, 8, 4), (256, 4, 2), (256, 2, 1)),
     "S7K1": ((256, 8, 4), (256, 4, 2), (256, 2, 1), (256, 1, 1), (256, 1, 1)),
+    "S1o": ((3, 19, 13),),
+    "S5o": ((2048, 3, 2), (1024, 5, 3), (512, 10, 5), (256, 19, 10)),
+    "S7K1o": ((256, 10, 5), (256, 5, 3), (256, 3, 2), (256, 2, 1), (256, 1, 1)),
 }
 _LEAVES["S7K3"] = _LEAVES["S7K1"]
 
 
+def _half(n):
+    """Extent after a stride-2 layer whose padding is half its kernel (7x7 / 3, 3x3 / 1, the max-pool): ceil(n / 2)."""
+    return (n + 1) // 2
+
+
 def out_shapes(section):
-    if section == "S1":
-        return [(256, 4, 3)]
-    if section in ("S2", "S3", "S4"):
-        c, h, w = _LEAVES[section][0]
-        return [(2 * c, (h + 1) // 2, (w + 1) // 2)]
-    if section == "S5":          # fp2s, fp3s, fp4s, fp5, p3s, p4s, p5s, p6, p7
-        return [(256, 16, 8), (256, 8, 4), (256, 4, 2), (256, 2, 1), (256, 8, 4), (256, 4, 2), (256, 2, 1), (256, 1, 1), (256, 1, 1)]
-    if section == "S6":          # k2, k3, k4, k5 (API tensors at the output resolution), pred
-        return [(19, 16, 8)] * 4 + [(18, 16, 8)]
-    cells = sum(h * w for _, h, w in _LEAVES[section])
+    """Output shapes, from the section's leaves (the sizes the layers of its base section give at any extent)."""
+    leaves, kind = _LEAVES[section], base(section)
+    if kind == "S1":          # stem (stride 2), max-pool (stride 2), layer1
+        _, h, w = leaves[0]
+        return [(256, _half(_half(h)), _half(_half(w)))]
+    if kind in ("S2", "S3", "S4"):
+        c, h, w = leaves[0]
+        return [(2 * c, _half(h), _half(w))]
+    if kind == "S5":          # fp2s, fp3s, fp4s, fp5, p3s, p4s, p5s, p6, p7: each level has its lateral's size, p6 / p7 halve c5 (ceil)
+        (_, h5, w5), (_, h4, w4), (_, h3, w3), (_, h2, w2) = leaves
+        h6, w6 = _half(h5), _half(w5)
+        return [(256, h2, w2), (256, h3, w3), (256, h4, w4), (256, h5, w5), (256, h3, w3), (256, h4, w4), (256, h5, w5), (256, h6, w6),
+                (256, _half(h6), _half(w6))]
+    if kind == "S6":          # k2, k3, k4, k5 (API tensors at the output resolution), pred
+        _, h, w = leaves[0]
+        return [(19, h, w)] * 4 + [(18, h, w)]
+    cells = sum(h * w for _, h, w in leaves)
     return [("A", 9 * cells, num_classes(section)), ("A", 9 * cells, 4)]          # cls [B, A, K], reg [B, A, 4]
 
 
-OUT_NAMES = {
+OUT_NAMES = _with_odd({
     "S1": ("c2",), "S2": ("out",), "S3": ("out",), "S4": ("out",),
     "S5": ("fp2s", "fp3s", "fp4s", "fp5", "p3s", "p4s", "p5s", "p6", "p7"),
     "S6": ("k2", "k3", "k4", "k5", "pred"), "S7K1": ("cls", "reg"), "S7K3": ("cls", "reg"),
-}
+})
 
 
 def outputs_with_gradient(section, variant):
@@ -266,14 +308,14 @@ def gen_inputs(section, seed, dtype=F32):
     leaves = []
     for shp in _LEAVES[section]:
         x = torch.randn(B, *shp, generator=g)
-        if section in ("S2", "S3", "S4", "S5"):
+        if base(section) in ("S2", "S3", "S4", "S5"):
             x = torch.relu(x)
         leaves.append(x.to(dtype).float())
     grads = []
     for shp in out_shapes(section):
         full = (B,) + tuple(shp[1:]) if shp[0] == "A" else (B,) + tuple(shp)
         d = torch.randn(*full, generator=g) * 0.05
-        grads.append(d if section in ("S6", "S7K1", "S7K3") else d.to(dtype).float())
+        grads.append(d if base(section) in ("S6", "S7K1", "S7K3") else d.to(dtype).float())
     return leaves, grads
 
 
@@ -358,6 +400,7 @@ def oracle_forward(section, sd, xs, bn_train):
     """The section through the oracle's own functions -> list of outputs in OUT_NAMES order (NCHW; S7: [B, A, K] / [B, A, 4])."""
     from oracle import posenet_oracle as po
     xs = [po._q(x) for x in xs]
+    section = base(section)
     if section == "S1":
         c1 = po._q(F.relu(po._bn(sd, "fpn.bn1", po._conv(sd, "fpn.conv1", xs[0], stride=2, padding=3), bn_train)))
         c1 = F.max_pool2d(c1, kernel_size=3, stride=2, padding=1)
@@ -403,7 +446,7 @@ def run_oracle(section, seed, dtype, bn_train, variant=None, fault=None, state=N
     for n in names:
         sd[n].requires_grad_(True)
     xs0, gs0 = gen_inputs(section, seed, quant if quant is not None else F32)
-    image = section == "S1"
+    image = base(section) == "S1"
     xs = [x.to(dtype).requires_grad_(not image) for x in xs0]
     shim = Shim(fault, sd)
     saved_cls = po.CONV2_CLASSES
@@ -525,7 +568,7 @@ def rel_l2(a, b):
 def compare_bf16(case, got, ref):
     """rel-L2 of outputs / leaf gradients / parameter gradients against the rounding oracle under BF16_GATES.  One report line."""
     _, section, cfg, _ = case
-    lim = {"out": BF16_GATES["out"], "dx": BF16_GATES["dx_towers" if section.startswith("S7") else "dx"], "dw": BF16_GATES["dw"]}
+    lim = {"out": BF16_GATES["out"], "dx": BF16_GATES["dx_towers" if base(section).startswith("S7") else "dx"], "dw": BF16_GATES["dw"]}
     worst, fails = {"out": (0.0, ""), "dx": (0.0, ""), "dw": (0.0, "")}, []
     for (kind, name, t), (_, _, r) in zip(_tensors(got, False), _tensors(ref, False)):
         if r is None or t is None:
@@ -569,9 +612,10 @@ def expected_routes(section, cfg):
     (the identity shortcut's share of its gradient was deferred into conv1's input-gradient launch, the BatchNorm-backward statistics
     of the bn3 behind z rode in that launch) — what the two-block chains exist to reach.  The share is deferred whenever z needs a
     gradient at all; the statistics ride when that bn3 has any to form (batch statistics, or a trainable affine pair)."""
-    if section not in ("S1", "S2", "S3", "S4"):
+    if base(section) not in ("S1", "S2", "S3", "S4"):
         return None
     tr = trainable_set(section, cfg)
+    section = base(section)
     first = {n for n in param_names(section) if n.startswith(_UNITS[section][0])} if section != "S1" else \
         {n for n in param_names(section) if not n.startswith("fpn.layer1.1.")}
     z_needs = (leaf_grad(cfg) and section != "S1") or bool(tr & first)

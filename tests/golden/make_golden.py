@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Generate the committed golden vectors by importing the REAL reference (build container only).
 
-Run:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+Run:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [g0 g1 g2 g2odd g3 ...]
+Without names every file is rewritten; with names only theirs (``g2odd`` writes g2_forward_odd_r50.npz alone).
 Needs /root/reference (read-only mount).  Never runs on the GPU box; only the .npz files travel.
 
 Import recipe: the reference targets torch 0.4 / CUDA, so
@@ -162,6 +163,58 @@ def g2_forward():
                         out["both_boxes_" + tag] = det[2].numpy()
         save("g2_forward_r%d.npz" % layers, **out)
         del model
+
+
+# ---- G2 at sizes that are no multiple of 32 (R50, detection path) --------------------------
+def g2_forward_odd():
+    """tests/golden/g2_forward_odd_r50.npz: 100x70 and 75x40, where the top-down up-sample goes to the lateral's exact size and
+    conv6 / conv7 give ceil-sized levels.  Detection only: the keypoint head's torch.cat needs exact x2 / x4 / x8 maps and raises
+    at these sizes.  Forward in G2's layout; the detection loss and its gradients at 2x100x70 in G3's ('det': frozen BatchNorm as
+    the trainer runs this subnet, G3's annotations scaled from 128x128 into 100x70)."""
+    model = poseNet(50)
+    out = {}
+    for mode, b, h, w in (("eval", 2, 100, 70), ("eval", 1, 75, 40), ("train", 2, 100, 70)):
+        tag = "%s_%dx%dx%d" % (mode, b, h, w)
+        img = t(weightgen.gen_images(1, b, h, w))
+        load_weights(model, seed=0, flavour="he")       # reset running stats
+        model.train() if mode == "train" else model.eval()
+        with torch.no_grad():
+            feats = model.fpn(img)
+            for n, f in zip(("fp2", "fp3", "fp4", "fp5"), feats[0]):
+                out["stat_%s_%s" % (n, tag)] = stats(f)
+                out["shape_%s_%s" % (n, tag)] = np.array(f.shape)
+            for n, f in zip(("p3", "p4", "p5", "p6", "p7"), feats[1]):
+                out["stat_%s_%s" % (n, tag)] = stats(f)
+                out["shape_%s_%s" % (n, tag)] = np.array(f.shape)
+            if mode == "train":
+                out["bn1_rm_" + tag] = model.fpn.bn1.running_mean.numpy().copy()
+                out["bn1_rv_" + tag] = model.fpn.bn1.running_var.numpy().copy()
+                out["l4bn3_rv_" + tag] = model.fpn.layer4[2].bn3.running_var.numpy().copy()
+                load_weights(model, seed=0, flavour="he")
+                model.train()
+            _, dsaved = model([img, "detection_subnet"])
+            out["det_cls_" + tag] = dsaved[0].numpy()
+            out["det_reg_" + tag] = dsaved[1].numpy()
+    # detection loss + gradients at 2x100x70, as g3_losses does at 2x128x128
+    b, h, w = 2, 100, 70
+    img = t(weightgen.gen_images(2, b, h, w))
+    anno = weightgen.gen_boxes_gt(2, b, 128, max_n=6)
+    anno[1, 3:] = -1
+    valid = anno[:, :, 4] != -1
+    anno[:, :, 0:4:2] = np.where(valid[:, :, None], anno[:, :, 0:4:2] * np.float32(w / 128.0), -1)
+    anno[:, :, 1:4:2] = np.where(valid[:, :, None], anno[:, :, 1:4:2] * np.float32(h / 128.0), -1)
+    out["anno"] = anno
+    load_weights(model, 0, "he")
+    model.train()
+    model.freeze_bn()
+    _, dsaved = model([img, "detection_subnet"])
+    dloss, dlog = build_detection_loss(dsaved, t(anno))
+    model.zero_grad()
+    dloss.backward()
+    out["det_loss"] = np.array([dlog["total_loss"], dlog["classification_loss"], dlog["regression_loss"]])
+    _grad_pack(model, out, "det", FULL_GRADS_DET)
+    save("g2_forward_odd_r50.npz", **out)
+    print("  det loss", out["det_loss"], " anchors", dsaved[0].shape[1])
 
 
 # ---- G3: keypoint / detection / combined loss + grads (R50) --------------------------------
@@ -343,8 +396,8 @@ def g8_steps():
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["g0", "g1", "g2", "g3", "g4", "g5", "g6", "g7", "g8"]
-    fns = dict(g0=g0_keys, g1=g1_anchors, g2=g2_forward, g3=g3_losses, g4=g4_focal, g5=g5_nms,
+    which = sys.argv[1:] or ["g0", "g1", "g2", "g2odd", "g3", "g4", "g5", "g6", "g7", "g8"]
+    fns = dict(g0=g0_keys, g1=g1_anchors, g2=g2_forward, g2odd=g2_forward_odd, g3=g3_losses, g4=g4_focal, g5=g5_nms,
                g6=g6_decode, g7=g7_prn, g8=g8_steps)
     for w in which:
         print("==", w)

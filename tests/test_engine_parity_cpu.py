@@ -44,7 +44,7 @@ def test_case_table_lists_every_section_configuration_and_dtype():
     for s, vs in er.G_VARIANTS.items():
         assert {c[3] for c in er.CASES if c[1] == s and c[2] == "G"} == set(vs)
     assert all(er.case_seed(c) is not None for c in er.CASES)
-    assert len([c for c in er.CASES if c[0] == "fp32"]) == 49 and len([c for c in er.CASES if c[0] == "bf16"]) == 44
+    assert len([c for c in er.CASES if c[0] == "fp32"]) == 69 and len([c for c in er.CASES if c[0] == "bf16"]) == 62
 
 
 @pytest.mark.parametrize("key", sorted(er.SEEDS), ids=lambda k: "%s-%s" % k)
@@ -55,8 +55,8 @@ def test_stored_seed_satisfies_the_margin_condition_and_is_the_first(key):
     r64, r32 = runs(section, stats)
     ok, worst = er.margins(r64, r32)
     assert ok, "%s / %s seed %d: margin / (16 x deviation) = %.3f" % (section, stats, er.SEEDS[key], worst)
-    n_relu = {"S1": 7, "S2": 6, "S3": 6, "S4": 6, "S5": 4, "S6": 1, "S7K1": 40, "S7K3": 40}[section]
-    assert len(r64["relu"]) == n_relu and len(r64["pool"]) == (1 if section == "S1" else 0)
+    n_relu = {"S1": 7, "S2": 6, "S3": 6, "S4": 6, "S5": 4, "S6": 1, "S7K1": 40, "S7K3": 40}[er.base(section)]
+    assert len(r64["relu"]) == n_relu and len(r64["pool"]) == (1 if er.base(section) == "S1" else 0)
     if er.SEEDS[key] <= 12:
         assert er.find_seed(section, stats, limit=er.SEEDS[key] + 1) == er.SEEDS[key]
 
@@ -432,3 +432,157 @@ def test_teeth_11_an_unused_heads_gradient_zero_filled():
         er.compare_fp32(case, r32, r64, r32, log=False)
     r64 = runs("S5", "frozen", "det")[0]
     assert r64["leaf_grads"][3] is None and r64["leaf_grads"][0] is not None          # c2 feeds the keypoint pyramid only
+
+
+# ------------------------------------------------------------------------------------------------ the odd-size sections
+def test_odd_sections_have_the_shapes_of_an_image_that_is_no_multiple_of_32():
+    """S1o: image 19x13 -> stem 10x7 -> pool 5x4.  S5o: the stage sizes of a 75x40 image, every pyramid level at its lateral's size,
+    p6 / p7 ceil-sized.  S7K1o: those five levels, 74 cells, 666 anchors per image, 100 / 30 / 12 / 4 / 2 pixels per level for B = 2.
+    The even sections keep the shapes they had."""
+    assert er.out_shapes("S1o") == [(256, 5, 4)] and er.out_shapes("S1") == [(256, 4, 3)]
+    assert er.out_shapes("S5o") == [(256, 19, 10), (256, 10, 5), (256, 5, 3), (256, 3, 2), (256, 10, 5), (256, 5, 3), (256, 3, 2), (256, 2, 1), (256, 1, 1)]
+    assert er.out_shapes("S5") == [(256, 16, 8), (256, 8, 4), (256, 4, 2), (256, 2, 1), (256, 8, 4), (256, 4, 2), (256, 2, 1), (256, 1, 1), (256, 1, 1)]
+    assert er.out_shapes("S6") == [(19, 16, 8)] * 4 + [(18, 16, 8)]
+    assert er.out_shapes("S7K1o") == [("A", 666, 1), ("A", 666, 4)] and er.out_shapes("S7K1") == [("A", 396, 1), ("A", 396, 4)]
+    assert [er.B * h * w for _, h, w in er._LEAVES["S7K1o"]] == [100, 30, 12, 4, 2]
+    assert [tuple(s[1:]) for s in er._LEAVES["S7K1o"]] == [tuple(s[1:]) for s in er.out_shapes("S5o")[4:]]      # what S5o's detection pyramid gives
+    h, w = 75, 40
+    sizes = []
+    for _ in range(5):
+        h, w = (h + 1) // 2, (w + 1) // 2
+        sizes.append((h, w))
+    assert [tuple(s[1:]) for s in er._LEAVES["S5o"]] == sizes[:0:-1]
+    for o, b in (("S1o", "S1"), ("S5o", "S5"), ("S7K1o", "S7K1")):
+        assert er.base(o) == b and er.section_shapes(o) == er.section_shapes(b) and er.G_VARIANTS.get(o) == er.G_VARIANTS.get(b)
+        assert [er.trainable_set(o, c) for c in "ABCDEFG"] == [er.trainable_set(b, c) for c in "ABCDEFG"]
+        assert [er.expected_routes(o, c) for c in "ABCDEFG"] == [er.expected_routes(b, c) for c in "ABCDEFG"]
+        assert er.gen_inputs(o, 0)[0][0].shape[2:] != er.gen_inputs(b, 0)[0][0].shape[2:]
+    r64 = runs("S5o", "frozen")[0]
+    assert [tuple(o.shape[1:]) for o in r64["outs"]] == er.out_shapes("S5o")          # the oracle sizes by the lateral, conv6 / conv7 by ceil
+    assert [tuple(o.shape[1:]) for o in runs("S1o", "frozen")[0]["outs"]] == er.out_shapes("S1o")
+    assert tuple(r64["pool"]) == () and tuple(runs("S1o", "frozen")[0]["pool"][0][0].shape[2:]) == (10, 7)
+
+
+def _halving(n_out, n_in):
+    """The 2x-only rule: source index i // 2, clamped to the last row / column."""
+    return (torch.arange(n_out) // 2).clamp(max=n_in - 1)
+
+
+def _pixel_centres(n_out, n_in):
+    """The other nearest convention: the source pixel under the CENTRE of the destination pixel, floor((i + 1/2) * n_in / n_out)."""
+    return (((2 * torch.arange(n_out) + 1) * n_in) // (2 * n_out)).clamp(max=n_in - 1)
+
+
+class NearestBy(er.Fault):
+    """12. / 13. Every nearest up-sample-to-size of the run replaced by a gather under another index rule (forward, and through the
+    gather's own backward the enumeration of each coarse pixel's children)."""
+
+    def __init__(self, rule):
+        self.rule, self.hits = rule, 0
+
+    def interpolate(self, i, args, kwargs, orig):
+        x, (H, W) = args[0], kwargs["size"]
+        assert kwargs["mode"] == "nearest"
+        self.hits += 1
+        return x[:, :, self.rule(H, x.shape[2])][:, :, :, self.rule(W, x.shape[3])]
+
+
+def _failed_names(case, got, r64, r32):
+    """The tensors compare_fp32 rejects (names as in its report: out<i>, leaf<i>, parameter names)."""
+    with pytest.raises(AssertionError) as e:
+        er.compare_fp32(case, got, r64, r32, log=False)
+    return {line.strip().split(":")[0] for line in str(e.value).splitlines()[1:]}
+
+
+def _nearest(n_out, n_in):
+    x = torch.arange(n_in, dtype=F64).view(1, 1, n_in, 1)
+    return torch.nn.functional.interpolate(x, size=(n_out, 1), mode="nearest").view(-1).long()
+
+
+def test_teeth_12_upsample_by_the_halving_rule():
+    """Source index i // 2 (clamped) in place of nearest-to-size.  On S5 every level is exactly twice the next and the rule IS the
+    nearest rule, so the faulty run is accepted: S5 cannot see it.  It is accepted on S5o as well, and on every size the network can
+    produce: a lateral of extent L sits over a coarse level of extent n = ceil(L / 2), so L is 2n or 2n - 1, and for L = 2n - 1
+    floor(i * n / (2n - 1)) = floor(i / 2 + i / (2 (2n - 1))) = i // 2 because the second term stays below 1/2 (checked below for
+    every n up to 64).  What S5o can see of an index rule that S5 cannot is the next test's."""
+    for n in range(1, 65):
+        for L in (2 * n - 1, 2 * n):
+            assert torch.equal(_nearest(L, n), _halving(L, n)), (L, n)
+    for section in ("S5", "S5o"):
+        r64, r32 = runs(section, "frozen")
+        f = NearestBy(_halving)
+        got = faulty(section, "frozen", f)
+        assert f.hits == 5
+        er.compare_fp32(("fp32", section, "B", None), got, r64, r32, log=False)
+        assert all(torch.equal(a, b) for a, b in zip(got["outs"], r32["outs"]))          # not merely accepted: the same forward, bit for bit
+
+
+def test_teeth_13_upsample_by_pixel_centres():
+    """The source pixel under the destination pixel's centre (the "nearest-exact" convention) in place of nearest-to-size's
+    floor(i * n_in / n_out).  At an exact factor 2 the two agree — floor((2i + 1) / 4) = i // 2 — so S5 accepts the run: the reason
+    S5o exists.  At 3 -> 5 they part (sources 0 0 1 2 2 against 0 0 1 1 2), as at every odd extent above 1, and S5o rejects the run:
+    every output below the first non-2x level, the gradient of layer4.2's input, and the parameter gradients of the two 1x1
+    convolutions whose outputs are up-sampled first; what lies above that level (fp5, p5s, p6, p7 and their parameters) is untouched."""
+    for n in range(1, 65):
+        assert torch.equal(_nearest(2 * n, n), _pixel_centres(2 * n, n))
+        assert n == 1 or not torch.equal(_nearest(2 * n - 1, n), _pixel_centres(2 * n - 1, n))
+    r64, r32 = runs("S5", "frozen")
+    got = faulty("S5", "frozen", NearestBy(_pixel_centres))
+    er.compare_fp32(("fp32", "S5", "B", None), got, r64, r32, log=False)
+    assert all(torch.equal(a, b) for a, b in zip(got["outs"], r32["outs"]))
+    r64, r32 = runs("S5o", "frozen")
+    f = NearestBy(_pixel_centres)
+    got = faulty("S5o", "frozen", f)
+    assert f.hits == 5
+    names = er.OUT_NAMES["S5o"]
+    bad = _failed_names(("fp32", "S5o", "B", None), got, r64, r32)
+    for n in ("fp4s", "fp3s", "fp2s", "p4s", "p3s"):
+        assert "out%d" % names.index(n) in bad, (n, sorted(bad))
+    for n in ("fp5", "p5s", "p6", "p7"):
+        assert "out%d" % names.index(n) not in bad, (n, sorted(bad))
+    assert "leaf0" in bad          # the input of layer4.2
+    for n in ("fpn.toplayer.weight", "fpn.latlayer1.weight"):
+        assert n in bad, (n, sorted(bad))
+    # (their bias gradients are sums over every pixel, and under either rule every fine pixel has exactly one parent: unchanged)
+    assert not bad & {"fpn.toplayer.bias", "fpn.latlayer1.bias"}
+    assert not bad & {"fpn.conv6.weight", "fpn.conv7.weight", "fpn.toplayer0.weight"}
+    # ... with nothing trainable (F) the outputs and the leaf gradient still show it
+    rejected(("fp32", "S5o", "F", None), got, r64, r32)
+
+
+class FloorSizedP6(er.Fault):
+    """14. conv6 sized by floor(H / 2) x floor(W / 2): the stride-2 convolution loses its last output row / column where the extent is
+    odd.  ``refill``: the level keeps its ceil-sized buffer and the lost row / column is never written (zeros)."""
+
+    def __init__(self, refill):
+        self.refill, self.hits = refill, 0
+
+    def conv2d(self, i, args, kwargs, orig, sd):
+        if args[1] is not sd["fpn.conv6.weight"]:
+            return None
+        self.hits += 1
+        x = args[0]
+        y = orig(*args, **kwargs)
+        h, w = max(x.shape[2] // 2, 1), max(x.shape[3] // 2, 1)
+        cut = y[:, :, :h, :w]
+        if self.refill:
+            cut = torch.nn.functional.pad(cut, (0, y.shape[3] - w, 0, y.shape[2] - h))
+        return cut
+
+
+def test_teeth_14_p6_sized_by_floor():
+    """S5o: c5 is 3x2, p6 must be 2x1 (ceil).  Sized by floor it is 1x1: rejected by the shape check (the unused-detection G case, so
+    that the run needs no gradient of that shape); kept at 2x1 with the second row never written: rejected element by element in p6,
+    p7 and conv6's gradients.  S5's c5 is 2x1, where floor and ceil agree: the same fault is accepted there."""
+    r64, r32 = runs("S5o", "frozen", "kp")
+    f = FloorSizedP6(False)
+    got = faulty("S5o", "frozen", f, "kp")
+    assert f.hits == 1 and tuple(got["outs"][7].shape[2:]) == (1, 1) and tuple(r64["outs"][7].shape[2:]) == (2, 1)
+    with pytest.raises(AssertionError) as e:
+        er.compare_fp32(("fp32", "S5o", "G", "kp"), got, r64, r32, log=False)
+    assert "(2, 256, 1, 1)" in str(e.value) and "(2, 256, 2, 1)" in str(e.value)          # measure's shape check, not an element
+    r64, r32 = runs("S5o", "frozen")
+    bad = _failed_names(("fp32", "S5o", "B", None), faulty("S5o", "frozen", FloorSizedP6(True)), r64, r32)
+    assert {"out7", "out8", "fpn.conv6.weight", "fpn.conv6.bias", "leaf0"} <= bad and "out6" not in bad, sorted(bad)
+    r64, r32 = runs("S5", "frozen")
+    assert er.compare_fp32(("fp32", "S5", "B", None), faulty("S5", "frozen", FloorSizedP6(True)), r64, r32, log=False) <= 1.0 + 1e-12

@@ -1,7 +1,11 @@
 """Engine tier on the MI355X (tests/engine_ref.py): every section of R50 through the engine's own composition method and
 Engine.run_backward — side stream, joins and completion reports included — under every configuration of the case table, against
 the oracle: in fp32 element by element against its float64 run under 16 x its float32 run's deviation, in bf16 against its
-storage-rounding model under the gates of the two teacher-forced tests; and the exact properties of the bookkeeping in both."""
+storage-rounding model under the gates of the two teacher-forced tests; and the exact properties of the bookkeeping in both.
+
+The odd-size sections (S1o, S5o, S7K1o) run the stem, the two pyramids and the detection head at the extents of an image that is no
+multiple of 32.  The keypoint head and 'both' have no such section: the reference's keypoint head concatenates exact x2 / x4 / x8
+maps and raises at any other size, so there is nothing to compare with."""
 import pytest
 import torch
 
@@ -118,6 +122,7 @@ def compose(m, ctx, section, xs, cdt, need):
     from multiposenet.pytorch_amd import ops
     eng, f = m._engine, m.fpn
     dev = torch.device("cuda", torch.cuda.current_device())
+    section = er.base(section)          # an odd-size section is its base section's composition on other extents
     if section == "S1":
         c = eng.stem(ctx, xs[0].cuda())
         c = eng.bottleneck(ctx, c, f.layer1[0])

@@ -245,6 +245,68 @@ def test_bf16_tracks_fp32():
     assert rl2 <= 3e-2
 
 
+def test_detection_path_matches_reference_golden_at_sizes_no_multiple_of_32():
+    """g2_forward_odd_r50.npz (the real reference at 100x70 and 75x40): the top-down up-sample goes to the lateral's exact size
+    (7 -> 13, 4 -> 7, 3 -> 5 ...), conv6 / conv7 give ceil-sized levels, the stem and the max-pool see odd extents, and five ragged
+    levels go through the pyramid-tower launch and the output packing.  fp32 forward in eval and train mode (running statistics
+    too), the detection loss and its gradients (frozen BatchNorm, as G3's 'det'), and bf16 against the fp32 golden — all under the
+    limits the 64 / 128 cases above use.  Detection path only: the reference's keypoint head concatenates exact x2 / x4 / x8 maps
+    and raises at these sizes, so 'keypoint_subnet' and 'both' have nothing to be compared with."""
+    from multiposenet.pytorch_amd.network.posenet import poseNet
+    from multiposenet.pytorch_amd import synthetic as weightgen
+    g = gold("g2_forward_odd_r50.npz")
+    n_anchors = {(100, 70): 1521, (75, 40): 666}
+    assert tuple(gold("g1_anchors.npz")["shape_100x70"]) == (1, 1521, 4)
+    model = get_model(50, torch.float32)
+    for mode, b, h, w in (("eval", 2, 100, 70), ("eval", 1, 75, 40), ("train", 2, 100, 70)):
+        tag = "%s_%dx%dx%d" % (mode, b, h, w)
+        img = t(weightgen.gen_images(1, b, h, w)).cuda()
+        load_he(model)
+        model.train() if mode == "train" else model.eval()
+        with torch.no_grad():
+            empty, dsaved = model([img, "detection_subnet"])
+        A = n_anchors[(h, w)]
+        assert empty == [] and len(dsaved) == 3
+        assert dsaved[0].shape == (b, A, 1) and dsaved[1].shape == (b, A, 4) and dsaved[2].shape == (1, A, 4)
+        if (h, w) == (100, 70):
+            assert dsaved[0].shape[1] == int(gold("g1_anchors.npz")["shape_100x70"][1])
+            assert np.array_equal(dsaved[2].cpu().numpy(), gold("g1_anchors.npz")["full_100x70"])
+        close("R50 det cls %s" % tag, dsaved[0], t(g["det_cls_" + tag]), 1e-3, 1e-4)
+        close("R50 det reg %s" % tag, dsaved[1], t(g["det_reg_" + tag]), 1e-3, 1e-4)
+        if mode == "train":
+            close("bn1 running_mean " + tag, model.fpn.bn1.running_mean, t(g["bn1_rm_" + tag]), 1e-5, 1e-5)
+            close("bn1 running_var " + tag, model.fpn.bn1.running_var, t(g["bn1_rv_" + tag]), 1e-5, 1e-5)
+            close("layer4.2.bn3 running_var " + tag, model.fpn.layer4[2].bn3.running_var, t(g["l4bn3_rv_" + tag]), 1e-5, 1e-4)
+            assert int(model.fpn.bn1.num_batches_tracked.item()) == 1
+    # --- detection loss and gradients at 2x100x70, frozen BN (trainer.py:173-174)
+    img = t(weightgen.gen_images(2, 2, 100, 70)).cuda()
+    load_he(model)
+    model.train()
+    model.freeze_bn()
+    model.zero_grad()
+    _, dsaved = model([img, "detection_subnet"])
+    dloss, dlog = poseNet.build_loss(dsaved, "detection_subnet", t(g["anno"]).cuda())
+    dloss.backward()
+    ref = g["det_loss"]
+    report("det loss 2x100x70: got %s ref %s" % ([dlog["total_loss"], dlog["classification_loss"], dlog["regression_loss"]], list(ref)))
+    for got, r in zip((dlog["total_loss"], dlog["classification_loss"], dlog["regression_loss"]), ref):
+        assert abs(got - r) <= 2e-4 * max(abs(r), 1.0), (got, r)
+    assert ref[2] > 0          # the scaled boxes do give positive anchors: the regression branch is exercised
+    _grad_check(model, g, "det")
+    # --- bf16 against the fp32 golden
+    m = get_model(50, torch.bfloat16)
+    m.eval()
+    img = t(weightgen.gen_images(1, 2, 100, 70)).cuda()
+    with torch.no_grad():
+        _, ds = m([img, "detection_subnet"])
+    assert ds[0].shape == (2, 1521, 1) and ds[1].shape == (2, 1521, 4)
+    for name, got, key in (("det cls", ds[0], "det_cls_eval_2x100x70"), ("det reg", ds[1], "det_reg_eval_2x100x70")):
+        ref = t(g[key])
+        rl2 = ((got.float().cpu() - ref).norm() / ref.norm()).item()
+        report("bf16 vs reference fp32 at 100x70: %s rel-L2 %.3e (lim 3.0e-02)" % (name, rl2))
+        assert rl2 <= 3e-2, (name, rl2)
+
+
 def test_full_size_batch_independence_and_determinism():
     """BASELINE full size (R101, 480x480): size-independent properties — in eval mode an image's
     outputs do not depend on its batch neighbours (bit-exact), and two runs are bit-identical."""
