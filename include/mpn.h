@@ -424,6 +424,47 @@ int mpn_nms_batched_topk(const float* dets, int64_t dets_stride, const int32_t* 
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Class-wise candidates and NMS for a head with K classes.  NOT in the reference, whose post-processing takes the maximum over
+ * the classes ahead of the threshold (posenet.py:267-271: one candidate per anchor, suppression across classes) — this is the
+ * form a RetinaNet is scored with, and opt-in (ops.detect_batched_classwise).  boxes [B,A,4] f32 (16-byte aligned), cls [B,A,K]
+ * f32 (any 4-byte aligned address: an image's base is not 16-byte aligned when A*K % 4 != 0), A*K < 2^31.
+ *   candidates   every flat index f = a*K + c with cls[b,a,c] > thresh (strict: a NaN or a score equal to thresh does not pass),
+ *                in ascending f; row (boxes[b,a], cls[b,a,c]), class c = f % K, anchor a = f / K
+ *   suppression  in descending score, ties lower f first; a kept candidate suppresses a later one iff both have the SAME class
+ *                and devIoU (nms_kernel.cu:16-24) > thresh (mode 0) / >= thresh (mode 1); top_k as mpn_nms_batched_topk: the
+ *                top_k best-scored candidates of the IMAGE (not of each class), ties lower f first, 0 = all of them
+ *   output       keep_out: rows of the candidate list in descending score across classes, ties lower f first
+ * With K == 1 every list equals mpn_score_filter_batched + mpn_nms_batched(_topk) byte for byte.
+ * Two passes over cls (the outputs are sized from the counted totals, never A*K rows), grid = (chunks, B) with
+ * mpn_class_filter_chunk() flat indices per chunk; positions come from bit counts, wave scans and the chunk table, never from
+ * atomics: the same bytes on every launch and at every position in the batch.
+ *   mpn_class_filter_count  chunk_cnt [B][chunks] i32 (mpn_class_filter_workspace_bytes(B, A, K) bytes; chunks =
+ *                           ceil(A*K / mpn_class_filter_chunk())) and counts [B] i32 = candidates per image
+ *   mpn_class_filter_fill   from the SAME cls, thresh and chunk_cnt: dets [B][dets_stride] f32 (rows of 5; dets_stride >= nmax*5),
+ *                           cand_cls / cand_anchor [B][idx_stride] i32 (idx_stride >= nmax), counts [B] = min(candidates, nmax);
+ *                           nmax >= max counts[b] of the count pass (rows at and beyond nmax are never written)
+ *   mpn_nms_batched_classes mpn_nms_batched(_topk) with cand_cls[b*cls_stride + i] the class of row i (cls_stride >= nmax);
+ *                           workspace mpn_nms_batched_classes_workspace_bytes(B, top_k > 0 ? min(nmax, top_k) : nmax): the layout
+ *                           of mpn_nms_batched plus the sorted classes; keep_stride >= that row count
+ *   mpn_gather_cand_class   classes[b*out_stride + i] = cand_cls[b*idx_stride + keep[b*keep_stride + i]] as int64 for i < num[b],
+ *                           0 for num[b] <= i < kmax (mpn_gather_class's padding); anchors (optional, with cand_anchor) the same.
+ *                           Boxes and scores: mpn_gather_dets_batched.
+ * -------------------------------------------------------------------------------------------*/
+int mpn_class_filter_chunk(void);
+int64_t mpn_class_filter_workspace_bytes(int B, int A, int K);   /* MPN_E_BADARG for B, A, K <= 0 or A*K >= 2^31 */
+int mpn_class_filter_count(const float* cls, int B, int A, int K, float thresh, int32_t* chunk_cnt, int32_t* counts, void* stream);
+int mpn_class_filter_fill(const float* boxes, const float* cls, int B, int A, int K, float thresh, const int32_t* chunk_cnt,
+                          int64_t nmax, float* dets, int64_t dets_stride, int32_t* cand_cls, int32_t* cand_anchor,
+                          int64_t idx_stride, int32_t* counts, void* stream);
+int64_t mpn_nms_batched_classes_workspace_bytes(int B, int64_t nmax);
+int mpn_nms_batched_classes(const float* dets, int64_t dets_stride, const int32_t* cand_cls, int64_t cls_stride,
+                            const int32_t* counts, int B, int64_t nmax, int64_t top_k, float thresh, int mode, int64_t* keep_out,
+                            int64_t keep_stride, int64_t* num_out, void* workspace, void* stream);
+int mpn_gather_cand_class(const int32_t* cand_cls, const int32_t* cand_anchor, int64_t idx_stride, const int64_t* keep,
+                          int64_t keep_stride, const int64_t* num, int B, int kmax, int64_t* classes, int64_t* anchors,
+                          int64_t out_stride, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Optimizer: torch.optim.Adam semantics (training/multipose_keypoint_train.py:106-110), fused over
  * a flat f32 arena.  step_size/bias corrections are computed on the host and passed in.
  * -------------------------------------------------------------------------------------------*/

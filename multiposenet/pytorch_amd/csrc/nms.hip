@@ -271,6 +271,237 @@ __global__ void gather_class_kernel(const int64_t* __restrict__ cls_id, const in
     out[(long)b * out_stride + i] = c;
 }
 
+// ---------------------------------------------------------------------------------- class-wise candidates and NMS (K-class heads)
+// Not in the reference (posenet.py:267 reduces the classes to their maximum before the threshold): every (anchor, class) pair of
+// cls [B,A,K] above the threshold is a candidate, flat index f = a*K + c, listed in ascending f.  Two passes over cls, because the
+// outputs are sized from the counted totals and never A*K rows: grid = (chunks of kClsChunk flat indices, B), the count pass leaves one
+// int32 per (image, chunk), the fill pass recomputes the predicate and starts at the sum of the chunks ahead of its own.  Positions
+// come from bit counts, wave scans and that table only (no atomics), so the output is the same bytes on every launch.
+constexpr int kClsChunk = 16384;          // flat indices per workgroup: 375 chunks per image at A = 76 725, K = 80
+constexpr int kClsThreads = 256;
+constexpr int kClsTile = kClsThreads * 4; // flat indices per step of a workgroup, four consecutive ones per lane
+
+// Four consecutive scores p[g .. g + 3], the valid ones being lo <= g + j < hi; p is 16-byte aligned and g a multiple of four (the
+// chunk's start address rounded down: an image's base b*A*K floats is not aligned when A*K % 4 != 0), so a quad that lies inside
+// [lo, hi) is one vector load and only the head / tail quads of a chunk read scalars.  Bit j of the result: element j passes
+// (strict >, false for NaN); v receives the scores.
+__device__ __forceinline__ unsigned cls_pass4(const float* __restrict__ p, int g, int lo, int hi, float thresh, float4& v) {
+    v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g >= lo && g + 4 <= hi) {
+        v = *reinterpret_cast<const float4*>(p + g);
+        return (unsigned)(v.x > thresh) | ((unsigned)(v.y > thresh) << 1) | ((unsigned)(v.z > thresh) << 2) | ((unsigned)(v.w > thresh) << 3);
+    }
+    unsigned m = 0u;
+    if (g + 0 >= lo && g + 0 < hi) { v.x = p[g + 0]; m |= (unsigned)(v.x > thresh); }
+    if (g + 1 >= lo && g + 1 < hi) { v.y = p[g + 1]; m |= (unsigned)(v.y > thresh) << 1; }
+    if (g + 2 >= lo && g + 2 < hi) { v.z = p[g + 2]; m |= (unsigned)(v.z > thresh) << 2; }
+    if (g + 3 >= lo && g + 3 < hi) { v.w = p[g + 3]; m |= (unsigned)(v.w > thresh) << 3; }
+    return m;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__global__ void __launch_bounds__(kClsThreads) class_filter_count_kernel(const float* __restrict__ cls, long AK, float thresh,
+                                                                         int* __restrict__ chunk_cnt, int nchunks) {
+    __shared__ int wave_cnt[kClsThreads / 64];
+    const int b = blockIdx.y, c = blockIdx.x;
+    const long f0 = (long)c * kClsChunk;
+    const int len = (int)((AK - f0) < (long)kClsChunk ? (AK - f0) : (long)kClsChunk);
+    const float* __restrict__ src = cls + (long)b * AK + f0;
+    const int s = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3);      // floats past the 16-byte boundary below src
+    const float* __restrict__ p = src - s;
+    int cnt = 0;
+    for (int g = threadIdx.x * 4; g < s + len; g += kClsTile) {
+        float4 v;
+        cnt += __popc(cls_pass4(p, g, s, s + len, thresh, v));
+    }
+    cnt = wave_sum(cnt);
+    if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int w = 0; w < kClsThreads / 64; ++w) t += wave_cnt[w];
+        chunk_cnt[(long)b * nchunks + c] = t;
+    }
+}
+
+// counts[b] = sum of image b's chunk table; one wave per image
+__global__ void __launch_bounds__(64) class_filter_sum_kernel(const int* __restrict__ chunk_cnt, int nchunks, int* __restrict__ counts) {
+    const int b = blockIdx.x;
+    int t = 0;
+    for (int j = threadIdx.x; j < nchunks; j += 64) t += chunk_cnt[(long)b * nchunks + j];
+    t = wave_sum(t);
+    if (threadIdx.x == 0) counts[b] = t;
+}
+
+__global__ void __launch_bounds__(kClsThreads) class_filter_fill_kernel(const float* __restrict__ boxes_all, const float* __restrict__ cls,
+                                                                        int A, int K, long AK, float thresh, const int* __restrict__ chunk_cnt,
+                                                                        int nchunks, int nmax, float* __restrict__ dets_all, long dets_stride,
+                                                                        int* __restrict__ cand_cls, int* __restrict__ cand_anchor,
+                                                                        long idx_stride, int* __restrict__ counts) {
+    __shared__ int wave_cnt[kClsThreads / 64];
+    __shared__ int base_s;
+    const int b = blockIdx.y, c = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (wave == 0) {                               // candidates of the chunks ahead of this one
+        int t = 0;
+        for (int j = lane; j < c; j += 64) t += chunk_cnt[(long)b * nchunks + j];
+        t = wave_sum(t);
+        if (lane == 0) base_s = t;
+    }
+    __syncthreads();
+    int base = base_s;
+    const long f0 = (long)c * kClsChunk;
+    const int len = (int)((AK - f0) < (long)kClsChunk ? (AK - f0) : (long)kClsChunk);
+    const float* __restrict__ src = cls + (long)b * AK + f0;
+    const int s = (int)((reinterpret_cast<uintptr_t>(src) >> 2) & 3);
+    const float* __restrict__ p = src - s;
+    const float* __restrict__ boxes = boxes_all + (long)b * A * 4;
+    float* __restrict__ dets = dets_all + (long)b * dets_stride;
+    int* __restrict__ ocls = cand_cls + (long)b * idx_stride;
+    int* __restrict__ oanc = cand_anchor + (long)b * idx_stride;
+    const int ntiles = (s + len + kClsTile - 1) / kClsTile;
+    for (int tile = 0; tile < ntiles; ++tile) {
+        const int g = tile * kClsTile + threadIdx.x * 4;
+        float4 v;
+        const unsigned m = cls_pass4(p, g, s, s + len, thresh, v);
+        const int n = __popc(m);
+        int inc = n;                               // inclusive scan over the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += t;
+        }
+        if (lane == 63) wave_cnt[wave] = inc;
+        __syncthreads();
+        int off = base, tot = 0;
+        for (int w = 0; w < kClsThreads / 64; ++w) {
+            if (w < wave) off += wave_cnt[w];
+            tot += wave_cnt[w];
+        }
+        if (m) {
+            int pos = off + inc - n;
+            const float sc[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (!((m >> j) & 1u)) continue;
+                const int f = (int)(f0 + (g - s + j));
+                const int a = f / K;
+                if (pos < nmax) {
+                    const float4 bx = *reinterpret_cast<const float4*>(boxes + (long)a * 4);
+                    float* o = dets + (long)pos * 5;
+                    o[0] = bx.x; o[1] = bx.y; o[2] = bx.z; o[3] = bx.w; o[4] = sc[j];
+                    ocls[pos] = f - a * K;
+                    oanc[pos] = a;
+                }
+                ++pos;
+            }
+        }
+        base += tot;
+        __syncthreads();
+    }
+    if (c == nchunks - 1 && threadIdx.x == 0) counts[b] = base < nmax ? base : nmax;
+}
+
+// NmsBatch with the class of every candidate: cls[b*cls_stride + i] for row i of image b; the sorted classes take an extra
+// [rows] int32 region at off_cls of the image's workspace (mpn_nms_batched_classes only)
+struct NmsClassBatch {
+    NmsBatch q;
+    const int* cls; long cls_stride;
+    long off_cls;
+};
+
+// nms_rank_kernel that also carries each candidate's class to its sorted position
+__global__ void nms_rank_class_kernel(const NmsClassBatch qc) {
+    __shared__ float ssc[1024];
+    const NmsBatch& q = qc.q;
+    const int b = blockIdx.z;
+    const int n = nb_all(q, b);
+    const int live = nb_count(q, b);
+    if ((int)(blockIdx.x * blockDim.x) >= n) return;
+    const float* __restrict__ dets = q.dets + (long)b * q.dets_stride;
+    const int* __restrict__ cls = qc.cls + (long)b * qc.cls_stride;
+    float* __restrict__ sorted = reinterpret_cast<float*>(q.ws + (long)b * q.ws_stride);
+    int* __restrict__ order = reinterpret_cast<int*>(q.ws + (long)b * q.ws_stride + q.off_order);
+    int* __restrict__ scls = reinterpret_cast<int*>(q.ws + (long)b * q.ws_stride + qc.off_cls);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const float si = (i < n) ? dets[(long)i * 5 + 4] : 0.f;
+    int rank = 0;
+    for (int j0 = 0; j0 < n; j0 += 1024) {
+        for (int t = threadIdx.x; t < 1024; t += blockDim.x) ssc[t] = (j0 + t < n) ? dets[(long)(j0 + t) * 5 + 4] : 0.f;
+        __syncthreads();
+        const int lim = (n - j0) < 1024 ? (n - j0) : 1024;
+        for (int t = 0; t < lim; ++t) {
+            const float sj = ssc[t];
+            rank += (sj > si) || (sj == si && (j0 + t) < i);
+        }
+        __syncthreads();
+    }
+    if (i < n && rank < live) {
+        order[rank] = i;
+        scls[rank] = cls[i];
+        const float* s = dets + (long)i * 5;
+        float* d = sorted + (long)rank * 5;
+        d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3]; d[4] = s[4];
+    }
+}
+
+// nms_mask_kernel whose bit (row, column) also needs both boxes to be of the same class: the row's class stays in a register, the
+// column's travels lane to lane with its box
+__global__ void __launch_bounds__(64) nms_mask_class_kernel(const NmsClassBatch qc, float thresh, int mode) {
+    const NmsBatch& q = qc.q;
+    const int b = blockIdx.z;
+    const int n = nb_count(q, b);
+    const int cbn = (n + 63) / 64;
+    const int cb = q.cb;
+    int row_blk = (int)((2.0 * cb + 1.0 - sqrt((2.0 * cb + 1.0) * (2.0 * cb + 1.0) - 8.0 * (double)blockIdx.x)) * 0.5);
+    while (row_blk > 0 && (long)row_blk * cb - (long)row_blk * (row_blk - 1) / 2 > (long)blockIdx.x) --row_blk;
+    while ((long)(row_blk + 1) * cb - (long)(row_blk + 1) * row_blk / 2 <= (long)blockIdx.x) ++row_blk;
+    const int col_blk = row_blk + (int)((long)blockIdx.x - ((long)row_blk * cb - (long)row_blk * (row_blk - 1) / 2));
+    if (row_blk >= cbn || col_blk >= cbn) return;
+    const float* __restrict__ sorted = reinterpret_cast<const float*>(q.ws + (long)b * q.ws_stride);
+    const int* __restrict__ scls = reinterpret_cast<const int*>(q.ws + (long)b * q.ws_stride + qc.off_cls);
+    unsigned long long* __restrict__ mask = reinterpret_cast<unsigned long long*>(q.ws + (long)b * q.ws_stride + q.off_mask);
+    const int t = threadIdx.x;
+    const int row = row_blk * 64 + t, col = col_blk * 64 + t;
+    float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
+    int ck = -1, rk = -2;
+    if (col < n) { const float* p = sorted + (long)col * 5; c0 = p[0]; c1 = p[1]; c2 = p[2]; c3 = p[3]; ck = scls[col]; }
+    if (row < n) { const float* p = sorted + (long)row * 5; r0 = p[0]; r1 = p[1]; r2 = p[2]; r3 = p[3]; rk = scls[row]; }
+    const int col_size = (n - col_blk * 64) < 64 ? (n - col_blk * 64) : 64;
+    unsigned long long bits = 0ull;
+    const int start = (row_blk == col_blk) ? t + 1 : 0;
+    for (int i = 0; i < col_size; ++i) {
+        const float b0 = __shfl(c0, i, 64), b1 = __shfl(c1, i, 64), b2 = __shfl(c2, i, 64), b3 = __shfl(c3, i, 64);
+        const int bk = __shfl(ck, i, 64);
+        const float iou = dev_iou(r0, r1, r2, r3, b0, b1, b2, b3);
+        const bool hit = ((mode == 0) ? (iou > thresh) : (iou >= thresh)) && (bk == rk);
+        if (hit && i >= start) bits |= 1ull << i;
+    }
+    if (row < n) mask[nms_tri_row(row, cb) + (col_blk - row_blk)] = bits;
+}
+
+// classes[b, i] = cand_cls[b][keep[b, i]] (and anchors[b, i] = cand_anchor[b][keep[b, i]] when asked for) as int64 for i < num[b],
+// 0 for num[b] <= i < kmax: gather_class_kernel's padding rule
+__global__ void gather_cand_class_kernel(const int* __restrict__ cand_cls, const int* __restrict__ cand_anchor, long idx_stride,
+                                         const int64_t* __restrict__ keep, long keep_stride, const int64_t* __restrict__ num, int kmax,
+                                         int64_t* __restrict__ classes, int64_t* __restrict__ anchors, long out_stride) {
+    const int b = blockIdx.y;
+    const int k = (int)num[b];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= kmax) return;
+    int64_t c = 0, a = 0;
+    if (i < k) {
+        const long r = (long)b * idx_stride + keep[(long)b * keep_stride + i];
+        c = cand_cls[r];
+        if (anchors) a = cand_anchor[r];
+    }
+    classes[(long)b * out_stride + i] = c;
+    if (anchors) anchors[(long)b * out_stride + i] = a;
+}
+
 inline long align_up(long v, long a) { return (v + a - 1) / a * a; }
 
 }  // namespace
@@ -406,4 +637,83 @@ extern "C" int mpn_nms_batched_topk(const float* dets, int64_t dets_stride, cons
     MPN_CHECK_ARG(nmax > 0 && nmax < (1 << 30) && keep_stride >= nlive && dets_stride >= nmax * 5);
     return launch_nms(dets, (long)dets_stride, counts, 0, B, (long)nmax, thresh, mode, keep_out, (long)keep_stride, num_out, workspace,
                       (hipStream_t)stream, (long)top_k);
+}
+
+// ---------------------------------------------------------------------------------- class-wise candidates and NMS: entry points
+// (semantics in include/mpn.h; not in the reference, which thresholds the maximum over the classes, posenet.py:267-271)
+extern "C" int mpn_class_filter_chunk(void) { return kClsChunk; }
+
+namespace {
+inline bool class_filter_dims_ok(int B, int A, int K) { return B > 0 && A > 0 && K > 0 && (int64_t)A * K < (1LL << 31); }
+inline int class_filter_chunks(int A, int K) { return (int)(((int64_t)A * K + kClsChunk - 1) / kClsChunk); }
+}  // namespace
+
+extern "C" int64_t mpn_class_filter_workspace_bytes(int B, int A, int K) {
+    if (!class_filter_dims_ok(B, A, K)) return MPN_E_BADARG;
+    return (int64_t)B * class_filter_chunks(A, K) * 4;
+}
+
+extern "C" int mpn_class_filter_count(const float* cls, int B, int A, int K, float thresh, int32_t* chunk_cnt, int32_t* counts,
+                                      void* stream) {
+    MPN_CHECK_ARG(cls && chunk_cnt && counts && class_filter_dims_ok(B, A, K) && (reinterpret_cast<uintptr_t>(cls) & 3) == 0);
+    const int nchunks = class_filter_chunks(A, K);
+    hipLaunchKernelGGL(class_filter_count_kernel, dim3(nchunks, B), dim3(kClsThreads), 0, (hipStream_t)stream, cls, (long)A * K, thresh,
+                       chunk_cnt, nchunks);
+    hipLaunchKernelGGL(class_filter_sum_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, chunk_cnt, nchunks, counts);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_class_filter_fill(const float* boxes, const float* cls, int B, int A, int K, float thresh, const int32_t* chunk_cnt,
+                                     int64_t nmax, float* dets, int64_t dets_stride, int32_t* cand_cls, int32_t* cand_anchor,
+                                     int64_t idx_stride, int32_t* counts, void* stream) {
+    MPN_CHECK_ARG(boxes && cls && chunk_cnt && dets && cand_cls && cand_anchor && counts && class_filter_dims_ok(B, A, K));
+    MPN_CHECK_ARG((reinterpret_cast<uintptr_t>(cls) & 3) == 0 && (reinterpret_cast<uintptr_t>(boxes) & 15) == 0);
+    MPN_CHECK_ARG(nmax > 0 && nmax < (1 << 30) && dets_stride >= nmax * 5 && idx_stride >= nmax);
+    const int nchunks = class_filter_chunks(A, K);
+    hipLaunchKernelGGL(class_filter_fill_kernel, dim3(nchunks, B), dim3(kClsThreads), 0, (hipStream_t)stream, boxes, cls, A, K, (long)A * K,
+                       thresh, chunk_cnt, nchunks, (int)nmax, dets, (long)dets_stride, cand_cls, cand_anchor, (long)idx_stride, counts);
+    return mpn_launch_status();
+}
+
+namespace {
+// an image's workspace: mpn_nms_batched's layout for `rows` rows, then the sorted classes [rows] i32
+inline long nms_class_ws(long rows) { return nms_layout(rows).total + align_up(rows * 4, 256); }
+}  // namespace
+
+extern "C" int64_t mpn_nms_batched_classes_workspace_bytes(int B, int64_t nmax) {
+    if (B <= 0 || nmax <= 0) return 256;
+    return (int64_t)B * nms_class_ws((long)nmax);
+}
+
+extern "C" int mpn_nms_batched_classes(const float* dets, int64_t dets_stride, const int32_t* cand_cls, int64_t cls_stride,
+                                       const int32_t* counts, int B, int64_t nmax, int64_t top_k, float thresh, int mode, int64_t* keep_out,
+                                       int64_t keep_stride, int64_t* num_out, void* workspace, void* stream) {
+    MPN_CHECK_ARG(dets && cand_cls && counts && keep_out && num_out && workspace && B > 0 && (mode == 0 || mode == 1) && top_k >= 0);
+    const int64_t nlive = (top_k > 0 && top_k < nmax) ? top_k : nmax;
+    MPN_CHECK_ARG(nmax > 0 && nmax < (1 << 30) && keep_stride >= nlive && dets_stride >= nmax * 5 && cls_stride >= nmax);
+    const NmsLayout l = nms_layout((long)nlive);
+    NmsClassBatch qc;
+    NmsBatch& q = qc.q;
+    q.dets = dets; q.dets_stride = (long)dets_stride; q.counts = counts; q.n_host = 0;
+    q.ws = (char*)workspace; q.ws_stride = nms_class_ws((long)nlive);
+    q.off_order = l.off_order; q.off_remv = l.off_remv; q.off_mask = l.off_mask; q.cb = l.cb;
+    q.cap = top_k > 0 ? (int)nlive : 0;
+    qc.cls = cand_cls; qc.cls_stride = (long)cls_stride; qc.off_cls = l.total;
+    const long tri = (long)l.cb * (l.cb + 1) / 2;
+    if (tri > 0x7fffffffL) return MPN_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(nms_rank_class_kernel, dim3((unsigned)((nmax + 255) / 256), 1, B), dim3(256), 0, st, qc);
+    hipLaunchKernelGGL(nms_mask_class_kernel, dim3((unsigned)tri, 1, B), dim3(64), 0, st, qc, thresh, mode);
+    hipLaunchKernelGGL(nms_scan_kernel, dim3(B), dim3(1024), 0, st, q, keep_out, (long)keep_stride, num_out);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_gather_cand_class(const int32_t* cand_cls, const int32_t* cand_anchor, int64_t idx_stride, const int64_t* keep,
+                                     int64_t keep_stride, const int64_t* num, int B, int kmax, int64_t* classes, int64_t* anchors,
+                                     int64_t out_stride, void* stream) {
+    MPN_CHECK_ARG(cand_cls && keep && num && classes && B > 0 && kmax > 0 && out_stride >= kmax && idx_stride > 0);
+    MPN_CHECK_ARG(!anchors || cand_anchor);
+    hipLaunchKernelGGL(gather_cand_class_kernel, dim3((kmax + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, cand_cls, cand_anchor,
+                       (long)idx_stride, keep, (long)keep_stride, num, kmax, classes, anchors, (long)out_stride);
+    return mpn_launch_status();
 }

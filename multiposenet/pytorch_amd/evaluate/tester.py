@@ -55,6 +55,7 @@ class TestParams(object):
     print_freq = 20
     gaussian_filt = False             # NMS(..., bool_gaussian_filt=True): smooth every up-sampled peak patch (sigma 3) before its arg-max
     category_ids = [1]                # detect_images / coco_eval_bbox: class index of the detection head -> COCO category id
+    nms_per_class = False             # detect_images / coco_eval_bbox: every (anchor, class) score is a candidate, NMS per class (not in the reference)
 
 
 def resize(img, out_hw, cubic, inv_scale=None):
@@ -377,7 +378,9 @@ class Tester(object):
         multiplied by the image's scale in float32 and turned into [x, y, w, h].  One dict {'image_id', 'file_name', 'category_id',
         'bbox', 'score'} per kept post-NMS row — every row above the model's 0.05 score threshold, in descending score, not only the
         persons above 0.5 that feed the PRN — with ``params.category_ids[class index]`` as its category.  ``max_per_image`` keeps the
-        best-scored rows of an image."""
+        best-scored rows of an image.  ``params.nms_per_class`` takes the class-wise post-processing (poseNet.detect_padded(class_wise=True):
+        an anchor yields a candidate for every class above 0.05, boxes of different classes never suppress each other); the rows
+        stay in descending score across classes, so ``max_per_image`` is the top N across classes."""
         from .._lib import MpnError
         cats = [int(c) for c in self.params.category_ids]
         K = int(self.model.classificationModel.num_classes)
@@ -399,7 +402,8 @@ class Tester(object):
                 xs.append(resnet_preprocess(resize(sq[:shape_dst, :shape_dst], (S, S), cubic=False)))
             with torch.no_grad():
                 _, anchors, cls, keep = self.model.forward_padded_begin(torch.stack(xs))
-            boxes, scores, kept, classes = self.model.detect_padded(anchors, cls, return_class=True)
+            boxes, scores, kept, classes = self.model.detect_padded(anchors, cls, return_class=True,
+                                                                    class_wise=bool(getattr(self.params, "nms_per_class", False)))
             boxes_h, scores_h, classes_h = boxes.cpu().numpy(), scores.cpu().numpy(), classes.cpu().numpy()
             del keep
             for li, (image_id, file_name, _) in enumerate(chunk):

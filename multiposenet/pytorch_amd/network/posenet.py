@@ -329,19 +329,22 @@ class poseNet(nn.Module):
         predict_keypoint, dets = self._entire_net(img_batch, all_images=False)
         return predict_keypoint, dets[0]
 
-    def forward_all_images(self, img_batch):
+    def forward_all_images(self, img_batch, class_wise=False):
         """Entire-net inference with detections for EVERY image of the batch (the reference thresholds and
         NMSes image 0 only, posenet.py:271,281).  Returns (heat-maps [B,18,H/4,W/4], [per-image
-        [nms_scores, nms_class, boxes]]); entry b equals what the reference returns for image b run alone."""
-        return self._entire_net(img_batch, all_images=True)
+        [nms_scores, nms_class, boxes]]); entry b equals what the reference returns for image b run alone.
+        class_wise=True (not in the reference): every (anchor, class) score above 0.05 is a candidate and the suppression runs per
+        class (ops.detect_batched_classwise)."""
+        return self._entire_net(img_batch, all_images=True, class_wise=class_wise)
 
-    def forward_all_images_padded(self, img_batch, pre_nms_top_n=None, return_class=False):
+    def forward_all_images_padded(self, img_batch, pre_nms_top_n=None, return_class=False, class_wise=False):
         """forward_all_images for batched post-processing: (heat-maps [B,18,H/4,W/4], boxes [B,nmax,4], scores [B,nmax], kept) with
         image b's detections in rows [:kept[b]] (descending score) — no per-image tensors or Python lists.  return_class: also the
         arg-max class of every row, classes [B,nmax] int64 (posenet.py:283; zeros for a single-class head and past kept[b]).
-        pre_nms_top_n: optional cap on the candidates that enter the suppression (ops.detect_batched; not in the reference)."""
+        pre_nms_top_n: optional cap on the candidates that enter the suppression (ops.detect_batched; not in the reference).
+        class_wise: detect_padded's."""
         predict_keypoint, transformed_anchors, classification, _keep = self.forward_padded_begin(img_batch)
-        out = self.detect_padded(transformed_anchors, classification, pre_nms_top_n, return_class)
+        out = self.detect_padded(transformed_anchors, classification, pre_nms_top_n, return_class, class_wise)
         return (predict_keypoint,) + tuple(out)
 
     def forward_padded_begin(self, img_batch):
@@ -354,11 +357,17 @@ class poseNet(nn.Module):
         return predict_keypoint, transformed_anchors, classification, (ctx, regression)
 
     @staticmethod
-    def detect_padded(transformed_anchors, classification, pre_nms_top_n=None, return_class=False):
+    def detect_padded(transformed_anchors, classification, pre_nms_top_n=None, return_class=False, class_wise=False):
         """Second half: score filter + per-image NMS + gather on the CURRENT stream (two host reads) -> (boxes, scores, kept[, classes]).
         Several classes: the score is the maximum over the classes and the class its arg-max (posenet.py:267,283); the suppression
-        runs across classes, as the reference's."""
+        runs across classes, as the reference's.  class_wise=True (not in the reference, any K): every (anchor, class) score above
+        0.05 is a candidate, the suppression runs among candidates of one class only and the rows are in descending score across
+        classes (ops.detect_batched_classwise); with K == 1 the result is the same."""
         B, K = classification.shape[0], classification.shape[-1]
+        if class_wise:
+            out = ops.detect_batched_classwise(transformed_anchors.contiguous(), classification.contiguous(), 0.05, 0.5, padded=True,
+                                               pre_nms_top_n=pre_nms_top_n)
+            return out if return_class else out[:3]
         if K == 1:
             out = ops.detect_batched(transformed_anchors, classification.reshape(B, -1), 0.05, 0.5, padded=True, pre_nms_top_n=pre_nms_top_n)
             if return_class:
@@ -368,9 +377,13 @@ class poseNet(nn.Module):
         out = ops.detect_batched(transformed_anchors, score, 0.05, 0.5, padded=True, pre_nms_top_n=pre_nms_top_n, cls_id=cls_id)
         return out if return_class else out[:3]
 
-    def _entire_net(self, img_batch, all_images):
+    def _entire_net(self, img_batch, all_images, class_wise=False):
         predict_keypoint, transformed_anchors, classification, _keep = self.forward_padded_begin(img_batch)
         B, K = classification.shape[0], classification.shape[2]
+        if class_wise:
+            dets = ops.detect_batched_classwise(transformed_anchors.contiguous(), classification.contiguous(), 0.05, 0.5)
+            return predict_keypoint, [[torch.zeros(0), torch.zeros(0), torch.zeros(0, 4)] if boxes is None else [nms_scores, nms_class, boxes]
+                                      for boxes, nms_scores, nms_class in dets]
         if K > 1:
             # posenet.py:267: scores = max over the classes (image 0 alone feeds 'both'); the arg-max (:283) is gathered for the kept
             # anchors only

@@ -1081,6 +1081,69 @@ def detect_batched(boxes, scores, score_thresh, iou_thresh, mode=0, ws_limit=4 <
     return [(out_boxes[b, :k], out_scores[b, :k]) if cnt[b] > 0 else (None, None) for b, k in enumerate(kept)]
 
 
+def detect_batched_classwise(boxes, cls, score_thresh, iou_thresh, mode=0, ws_limit=4 << 30, padded=False, pre_nms_top_n=None):
+    """Class-wise post-processing of a K-class head (NOT the reference's, which thresholds the maximum over the classes and suppresses
+    across them, posenet.py:267-281): every (anchor, class) score of cls [B,A,K] above score_thresh is a candidate, the suppression runs
+    among candidates of the same class only, and the kept rows come out in descending score across classes (ties: lower a*K + c first)
+    — include/mpn.h, "Class-wise candidates and NMS".  boxes [B,A,4], cls [B,A,K] (f32, contiguous).
+    Returns what detect_batched(..., cls_id=...) returns: per image (boxes[k,4], scores[k], classes[k] int64) device tensors (views), or
+    with padded=True (boxes [B,nmax,4], scores [B,nmax], kept counts list, classes [B,nmax] int64).  Two host reads per batch: the
+    candidate counts after the count pass, the kept counts at the end.  pre_nms_top_n / MPN_NMS_PRE_TOPN, the warning above 32 768
+    candidates and ws_limit are detect_batched's; the cap counts the candidates of an image, not of a class.  With K == 1 every result
+    equals detect_batched's byte for byte."""
+    B, A, K = cls.shape
+    dev = cls.device
+    if not (boxes.is_contiguous() and cls.is_contiguous()):
+        raise _lib.MpnError("detect_batched_classwise needs contiguous boxes [B,A,4] and cls [B,A,K]")
+    chunk_bytes = call("mpn_class_filter_workspace_bytes", B, A, K)
+    if chunk_bytes < 0:
+        raise _lib.MpnError("detect_batched_classwise: B=%d A=%d K=%d is out of range (A*K must stay below 2^31)" % (B, A, K))
+    chunk_cnt = torch.empty((chunk_bytes // 4,), dtype=torch.int32, device=dev)
+    counts = torch.empty((B,), dtype=torch.int32, device=dev)
+    call("mpn_class_filter_count", ptr(cls), B, A, K, float(score_thresh), ptr(chunk_cnt), ptr(counts), stream_ptr())
+    cnt = counts.tolist()                              # host round trip 1
+    ncand = max(cnt)
+    if ncand == 0:
+        if padded:
+            return (torch.zeros((B, 0, 4), dtype=torch.float32, device=dev), torch.zeros((B, 0), dtype=torch.float32, device=dev), [0] * B,
+                    torch.zeros((B, 0), dtype=torch.int64, device=dev))
+        return [(None, None, None)] * B
+    dets = torch.empty((B, ncand, 5), dtype=torch.float32, device=dev)
+    cand_cls = torch.empty((B, ncand), dtype=torch.int32, device=dev)
+    cand_anchor = torch.empty((B, ncand), dtype=torch.int32, device=dev)
+    call("mpn_class_filter_fill", ptr(boxes), ptr(cls), B, A, K, float(score_thresh), ptr(chunk_cnt), ncand, ptr(dets), ncand * 5, ptr(cand_cls),
+         ptr(cand_anchor), ncand, ptr(counts), stream_ptr())
+    if pre_nms_top_n is None and nms_pre_topn_env() > 0:
+        pre_nms_top_n = nms_pre_topn_env()
+    top = int(pre_nms_top_n) if pre_nms_top_n else 0
+    if top == 0 and ncand > 32768 and not _NMS_WARNED:
+        import warnings
+        _NMS_WARNED.append(True)
+        warnings.warn("NMS over %d candidates in one image (upper-triangle N x N / 128 mask = %.0f MB per image); pass pre_nms_top_n or set "
+                      "MPN_NMS_PRE_TOPN to bound it (not in the reference)" % (ncand, ncand * float(ncand) / 128 * 8 / 1e6))
+    nmax = min(ncand, top) if top > 0 else ncand       # rows of the sort / mask scratch and of the outputs
+    keep = torch.empty((B, nmax), dtype=torch.int64, device=dev)
+    num = torch.empty((B,), dtype=torch.int64, device=dev)
+    per_img = call("mpn_nms_batched_classes_workspace_bytes", 1, nmax)
+    group = max(1, min(B, int(ws_limit // per_img)))
+    for b0 in range(0, B, group):
+        nb = min(group, B - b0)
+        ws = workspace(per_img * nb, dev, slot=4)
+        call("mpn_nms_batched_classes", ctypes.c_void_p(dets.data_ptr() + b0 * ncand * 5 * 4), ncand * 5,
+             ctypes.c_void_p(cand_cls.data_ptr() + b0 * ncand * 4), ncand, ctypes.c_void_p(counts.data_ptr() + b0 * 4), nb, ncand, top,
+             float(iou_thresh), mode, ctypes.c_void_p(keep.data_ptr() + b0 * nmax * 8), nmax, ctypes.c_void_p(num.data_ptr() + b0 * 8), ptr(ws),
+             stream_ptr())
+    out_boxes = torch.empty((B, nmax, 4), dtype=torch.float32, device=dev)
+    out_scores = torch.empty((B, nmax), dtype=torch.float32, device=dev)
+    out_cls = torch.empty((B, nmax), dtype=torch.int64, device=dev)
+    call("mpn_gather_dets_batched", ptr(dets), ncand * 5, ptr(keep), nmax, ptr(num), B, nmax, ptr(out_boxes), ptr(out_scores), nmax, stream_ptr())
+    call("mpn_gather_cand_class", ptr(cand_cls), None, ncand, ptr(keep), nmax, ptr(num), B, nmax, ptr(out_cls), None, nmax, stream_ptr())
+    kept = num.tolist()                                # host round trip 2
+    if padded:
+        return out_boxes, out_scores, [k if cnt[b] > 0 else 0 for b, k in enumerate(kept)], out_cls
+    return [(out_boxes[b, :k], out_scores[b, :k], out_cls[b, :k]) if cnt[b] > 0 else (None, None, None) for b, k in enumerate(kept)]
+
+
 def score_filter(boxes0, scores0, thresh):
     """Image-0 candidates with score > thresh: returns (dets[n,5], src_idx[n]) (one D2H of n)."""
     A = scores0.numel()
