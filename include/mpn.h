@@ -443,7 +443,8 @@ int mpn_nms_batched_topk(const float* dets, int64_t dets_stride, const int32_t* 
  *   mpn_class_filter_fill   from the SAME cls, thresh and chunk_cnt: dets [B][dets_stride] f32 (rows of 5; dets_stride >= nmax*5),
  *                           cand_cls / cand_anchor [B][idx_stride] i32 (idx_stride >= nmax), counts [B] = min(candidates, nmax);
  *                           nmax >= max counts[b] of the count pass (rows at and beyond nmax are never written)
- *   mpn_nms_batched_classes mpn_nms_batched(_topk) with cand_cls[b*cls_stride + i] the class of row i (cls_stride >= nmax);
+ *   mpn_nms_batched_classes mpn_nms_batched(_topk) with cand_cls[b*cls_stride + i] the class of row i (cls_stride >= nmax): the
+ *                           same kernels, nms_rank_kernel<true> / nms_mask_kernel<true> in place of the <false> instantiations;
  *                           workspace mpn_nms_batched_classes_workspace_bytes(B, top_k > 0 ? min(nmax, top_k) : nmax): the layout
  *                           of mpn_nms_batched plus the sorted classes; keep_stride >= that row count
  *   mpn_gather_cand_class   classes[b*out_stride + i] = cand_cls[b*idx_stride + keep[b*keep_stride + i]] as int64 for i < num[b],

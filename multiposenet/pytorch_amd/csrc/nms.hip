@@ -89,14 +89,30 @@ __global__ void __launch_bounds__(1024) score_filter_kernel(const float* __restr
 
 // ---------------------------------------------------------------------------------- NMS
 // Every kernel below serves one image per blockIdx.z (or .x for the scan): image b has n = counts[b] candidates (counts ==
-// NULL: n_host for the single image), its rows start at dets + b*dets_stride, its scratch at b*ws_stride bytes.
+// NULL: n_host for the single image), its rows start at dets + b*dets_stride, its scratch at ws + b*l.total bytes.
+// That scratch, for `rows` rows and every region 256-byte aligned: sorted [rows*5 f32] | order [rows i32] at off_order | remv [cb u64] at
+// off_remv | mask (upper triangle, packed: nms_tri_row) at off_mask [| the sorted classes [rows] i32 at off_cls: class-wise NMS only]
+// (cb: mask words per row = ceil(rows / 64).  The class fields come last here and in NmsBatch: what the plain kernels read keeps the
+// kernel-argument offsets it had without them, and with the offsets their scalar prologues.)
+struct NmsLayout { long total, off_order, off_remv, off_mask; int cb; long off_cls; };
+inline long align_up(long v, long a) { return (v + a - 1) / a * a; }
+inline NmsLayout nms_layout(long rows, bool with_classes) {
+    NmsLayout l;
+    l.cb = (int)((rows + 63) / 64);
+    l.off_order = align_up(rows * 5 * 4, 256);
+    l.off_remv = l.off_order + align_up(rows * 4, 256);
+    l.off_mask = l.off_remv + align_up((long)l.cb * 8, 256);
+    l.off_cls = l.off_mask + align_up(64L * ((long)l.cb * (l.cb + 1) / 2) * 8, 256);
+    l.total = l.off_cls + (with_classes ? align_up(rows * 4, 256) : 0);
+    return l;
+}
+
 struct NmsBatch {
     const float* dets; long dets_stride;         // candidate rows [n][5] per image (floats between images)
     const int* counts; int n_host;
-    char* ws; long ws_stride;                    // per image: sorted [nmax*5 f32] | order [nmax i32] | remv [cb u64] | mask (upper triangle, packed)
-    long off_order, off_remv, off_mask;
-    int cb;                                      // mask words per row = ceil(nmax / 64)
     int cap;                                     // 0, or: only the `cap` best-scored candidates of an image enter the suppression
+    char* ws; NmsLayout l;                       // image b's scratch starts l.total bytes after image b - 1's
+    const int* cls; long cls_stride;             // NULL / 0, or the class of every candidate: cls[b*cls_stride + i] for row i of image b
 };
 // candidates of image b / the ones that take part in the suppression (the best `cap` of them after the sort)
 __device__ __forceinline__ int nb_all(const NmsBatch& q, int b) { return q.counts ? q.counts[b] : q.n_host; }
@@ -113,6 +129,8 @@ __device__ __forceinline__ long nms_tri_row(int r, int cb) {
     return 64 * (rb * cb - rb * (rb - 1) / 2) + (long)(r & 63) * (cb - rb);
 }
 
+// kClass: each candidate's class travels to its sorted position too (the plain instantiation never reads q.cls / off_cls)
+template <bool kClass>
 __global__ void nms_rank_kernel(const NmsBatch q) {
     __shared__ float ssc[1024];
     const int b = blockIdx.z;
@@ -120,8 +138,8 @@ __global__ void nms_rank_kernel(const NmsBatch q) {
     const int live = nb_count(q, b);
     if ((int)(blockIdx.x * blockDim.x) >= n) return;
     const float* __restrict__ dets = q.dets + (long)b * q.dets_stride;
-    float* __restrict__ sorted = reinterpret_cast<float*>(q.ws + (long)b * q.ws_stride);
-    int* __restrict__ order = reinterpret_cast<int*>(q.ws + (long)b * q.ws_stride + q.off_order);
+    float* __restrict__ sorted = reinterpret_cast<float*>(q.ws + (long)b * q.l.total);
+    int* __restrict__ order = reinterpret_cast<int*>(q.ws + (long)b * q.l.total + q.l.off_order);
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const float si = (i < n) ? dets[(long)i * 5 + 4] : 0.f;
     int rank = 0;
@@ -137,6 +155,7 @@ __global__ void nms_rank_kernel(const NmsBatch q) {
     }
     if (i < n && rank < live) {
         order[rank] = i;
+        if constexpr (kClass) reinterpret_cast<int*>(q.ws + (long)b * q.l.total + q.l.off_cls)[rank] = q.cls[(long)b * q.cls_stride + i];
         const float* s = dets + (long)i * 5;
         float* d = sorted + (long)rank * 5;
         d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3]; d[4] = s[4];
@@ -155,33 +174,45 @@ __device__ __forceinline__ float dev_iou(const float a0, const float a1, const f
     return interS / (Sa + Sb - interS);
 }
 
-// One wave per 64x64 tile of the UPPER triangle (tile pairs are enumerated so that no workgroup is launched for the
-// lower half): blockIdx.x = row_blk * cb - row_blk*(row_blk-1)/2 + (col_blk - row_blk).
+// Tiles of the UPPER triangle are enumerated so that no workgroup is launched for the lower half: blockIdx.x = row_blk * cb -
+// row_blk*(row_blk-1)/2 + (col_blk - row_blk), cb the launch-wide tiles per side.  Returns (row_blk, col_blk).
+__device__ __forceinline__ int2 nms_tile(int cb) {
+    int row_blk = (int)((2.0 * cb + 1.0 - sqrt((2.0 * cb + 1.0) * (2.0 * cb + 1.0) - 8.0 * (double)blockIdx.x)) * 0.5);
+    while (row_blk > 0 && (long)row_blk * cb - (long)row_blk * (row_blk - 1) / 2 > (long)blockIdx.x) --row_blk;
+    while ((long)(row_blk + 1) * cb - (long)(row_blk + 1) * row_blk / 2 <= (long)blockIdx.x) ++row_blk;
+    return make_int2(row_blk, row_blk + (int)((long)blockIdx.x - ((long)row_blk * cb - (long)row_blk * (row_blk - 1) / 2)));
+}
+
+// One wave per 64x64 tile.  kClass: bit (row, column) also needs both boxes to be of the same class — the row's class stays in a register,
+// the column's travels lane to lane with its box; the plain instantiation carries neither the loads, the shuffle nor the compare.
+template <bool kClass>
 __global__ void __launch_bounds__(64) nms_mask_kernel(const NmsBatch q, float thresh, int mode) {
     const int b = blockIdx.z;
     const int n = nb_count(q, b);
     const int cbn = (n + 63) / 64;               // live tiles per side for this image
-    // invert the triangular index with the launch-wide cb
-    const int cb = q.cb;
-    int row_blk = (int)((2.0 * cb + 1.0 - sqrt((2.0 * cb + 1.0) * (2.0 * cb + 1.0) - 8.0 * (double)blockIdx.x)) * 0.5);
-    while (row_blk > 0 && (long)row_blk * cb - (long)row_blk * (row_blk - 1) / 2 > (long)blockIdx.x) --row_blk;
-    while ((long)(row_blk + 1) * cb - (long)(row_blk + 1) * row_blk / 2 <= (long)blockIdx.x) ++row_blk;
-    const int col_blk = row_blk + (int)((long)blockIdx.x - ((long)row_blk * cb - (long)row_blk * (row_blk - 1) / 2));
+    const int cb = q.l.cb;
+    const int2 tile = nms_tile(cb);
+    const int row_blk = tile.x, col_blk = tile.y;
     if (row_blk >= cbn || col_blk >= cbn) return;
-    const float* __restrict__ sorted = reinterpret_cast<const float*>(q.ws + (long)b * q.ws_stride);
-    unsigned long long* __restrict__ mask = reinterpret_cast<unsigned long long*>(q.ws + (long)b * q.ws_stride + q.off_mask);
+    const float* __restrict__ sorted = reinterpret_cast<const float*>(q.ws + (long)b * q.l.total);
+    const int* __restrict__ scls = kClass ? reinterpret_cast<const int*>(q.ws + (long)b * q.l.total + q.l.off_cls) : nullptr;
+    unsigned long long* __restrict__ mask = reinterpret_cast<unsigned long long*>(q.ws + (long)b * q.l.total + q.l.off_mask);
     const int t = threadIdx.x;
     const int row = row_blk * 64 + t, col = col_blk * 64 + t;
     float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
-    if (col < n) { const float* p = sorted + (long)col * 5; c0 = p[0]; c1 = p[1]; c2 = p[2]; c3 = p[3]; }
-    if (row < n) { const float* p = sorted + (long)row * 5; r0 = p[0]; r1 = p[1]; r2 = p[2]; r3 = p[3]; }
+    int ck = -1, rk = -2;                        // kClass: class of the column / row box, never equal where one of them is missing
+    if (col < n) { const float* p = sorted + (long)col * 5; c0 = p[0]; c1 = p[1]; c2 = p[2]; c3 = p[3]; if constexpr (kClass) ck = scls[col]; }
+    if (row < n) { const float* p = sorted + (long)row * 5; r0 = p[0]; r1 = p[1]; r2 = p[2]; r3 = p[3]; if constexpr (kClass) rk = scls[row]; }
     const int col_size = (n - col_blk * 64) < 64 ? (n - col_blk * 64) : 64;
     unsigned long long bits = 0ull;
     const int start = (row_blk == col_blk) ? t + 1 : 0;       // nms_kernel.cu:58-61
     for (int i = 0; i < col_size; ++i) {
         const float b0 = __shfl(c0, i, 64), b1 = __shfl(c1, i, 64), b2 = __shfl(c2, i, 64), b3 = __shfl(c3, i, 64);
+        const int bk = kClass ? __shfl(ck, i, 64) : 0;
         const float iou = dev_iou(r0, r1, r2, r3, b0, b1, b2, b3);
-        const bool hit = (mode == 0) ? (iou > thresh) : (iou >= thresh);
+        bool hit;                                 // spelled out per instantiation: each compiles to its loop of before the kernels were merged
+        if constexpr (kClass) hit = ((mode == 0) ? (iou > thresh) : (iou >= thresh)) && (bk == rk);
+        else hit = (mode == 0) ? (iou > thresh) : (iou >= thresh);
         if (hit && i >= start) bits |= 1ull << i;
     }
     if (row < n) mask[nms_tri_row(row, cb) + (col_blk - row_blk)] = bits;
@@ -194,11 +225,11 @@ __global__ void __launch_bounds__(1024) nms_scan_kernel(const NmsBatch q, int64_
     __shared__ int base_cnt;
     const int b = blockIdx.x;
     const int n = nb_count(q, b);
-    const int cb = q.cb;
+    const int cb = q.l.cb;
     const int cbn = (n + 63) / 64;
-    const int* __restrict__ order = reinterpret_cast<const int*>(q.ws + (long)b * q.ws_stride + q.off_order);
-    unsigned long long* __restrict__ remv = reinterpret_cast<unsigned long long*>(q.ws + (long)b * q.ws_stride + q.off_remv);
-    const unsigned long long* __restrict__ mask = reinterpret_cast<const unsigned long long*>(q.ws + (long)b * q.ws_stride + q.off_mask);
+    const int* __restrict__ order = reinterpret_cast<const int*>(q.ws + (long)b * q.l.total + q.l.off_order);
+    unsigned long long* __restrict__ remv = reinterpret_cast<unsigned long long*>(q.ws + (long)b * q.l.total + q.l.off_remv);
+    const unsigned long long* __restrict__ mask = reinterpret_cast<const unsigned long long*>(q.ws + (long)b * q.l.total + q.l.off_mask);
     int64_t* __restrict__ keep_out = keep_all + (long)b * keep_stride;
     const int tid = threadIdx.x;
     for (int j = tid; j < cbn; j += 1024) remv[j] = 0ull;
@@ -405,84 +436,6 @@ __global__ void __launch_bounds__(kClsThreads) class_filter_fill_kernel(const fl
     if (c == nchunks - 1 && threadIdx.x == 0) counts[b] = base < nmax ? base : nmax;
 }
 
-// NmsBatch with the class of every candidate: cls[b*cls_stride + i] for row i of image b; the sorted classes take an extra
-// [rows] int32 region at off_cls of the image's workspace (mpn_nms_batched_classes only)
-struct NmsClassBatch {
-    NmsBatch q;
-    const int* cls; long cls_stride;
-    long off_cls;
-};
-
-// nms_rank_kernel that also carries each candidate's class to its sorted position
-__global__ void nms_rank_class_kernel(const NmsClassBatch qc) {
-    __shared__ float ssc[1024];
-    const NmsBatch& q = qc.q;
-    const int b = blockIdx.z;
-    const int n = nb_all(q, b);
-    const int live = nb_count(q, b);
-    if ((int)(blockIdx.x * blockDim.x) >= n) return;
-    const float* __restrict__ dets = q.dets + (long)b * q.dets_stride;
-    const int* __restrict__ cls = qc.cls + (long)b * qc.cls_stride;
-    float* __restrict__ sorted = reinterpret_cast<float*>(q.ws + (long)b * q.ws_stride);
-    int* __restrict__ order = reinterpret_cast<int*>(q.ws + (long)b * q.ws_stride + q.off_order);
-    int* __restrict__ scls = reinterpret_cast<int*>(q.ws + (long)b * q.ws_stride + qc.off_cls);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const float si = (i < n) ? dets[(long)i * 5 + 4] : 0.f;
-    int rank = 0;
-    for (int j0 = 0; j0 < n; j0 += 1024) {
-        for (int t = threadIdx.x; t < 1024; t += blockDim.x) ssc[t] = (j0 + t < n) ? dets[(long)(j0 + t) * 5 + 4] : 0.f;
-        __syncthreads();
-        const int lim = (n - j0) < 1024 ? (n - j0) : 1024;
-        for (int t = 0; t < lim; ++t) {
-            const float sj = ssc[t];
-            rank += (sj > si) || (sj == si && (j0 + t) < i);
-        }
-        __syncthreads();
-    }
-    if (i < n && rank < live) {
-        order[rank] = i;
-        scls[rank] = cls[i];
-        const float* s = dets + (long)i * 5;
-        float* d = sorted + (long)rank * 5;
-        d[0] = s[0]; d[1] = s[1]; d[2] = s[2]; d[3] = s[3]; d[4] = s[4];
-    }
-}
-
-// nms_mask_kernel whose bit (row, column) also needs both boxes to be of the same class: the row's class stays in a register, the
-// column's travels lane to lane with its box
-__global__ void __launch_bounds__(64) nms_mask_class_kernel(const NmsClassBatch qc, float thresh, int mode) {
-    const NmsBatch& q = qc.q;
-    const int b = blockIdx.z;
-    const int n = nb_count(q, b);
-    const int cbn = (n + 63) / 64;
-    const int cb = q.cb;
-    int row_blk = (int)((2.0 * cb + 1.0 - sqrt((2.0 * cb + 1.0) * (2.0 * cb + 1.0) - 8.0 * (double)blockIdx.x)) * 0.5);
-    while (row_blk > 0 && (long)row_blk * cb - (long)row_blk * (row_blk - 1) / 2 > (long)blockIdx.x) --row_blk;
-    while ((long)(row_blk + 1) * cb - (long)(row_blk + 1) * row_blk / 2 <= (long)blockIdx.x) ++row_blk;
-    const int col_blk = row_blk + (int)((long)blockIdx.x - ((long)row_blk * cb - (long)row_blk * (row_blk - 1) / 2));
-    if (row_blk >= cbn || col_blk >= cbn) return;
-    const float* __restrict__ sorted = reinterpret_cast<const float*>(q.ws + (long)b * q.ws_stride);
-    const int* __restrict__ scls = reinterpret_cast<const int*>(q.ws + (long)b * q.ws_stride + qc.off_cls);
-    unsigned long long* __restrict__ mask = reinterpret_cast<unsigned long long*>(q.ws + (long)b * q.ws_stride + q.off_mask);
-    const int t = threadIdx.x;
-    const int row = row_blk * 64 + t, col = col_blk * 64 + t;
-    float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
-    int ck = -1, rk = -2;
-    if (col < n) { const float* p = sorted + (long)col * 5; c0 = p[0]; c1 = p[1]; c2 = p[2]; c3 = p[3]; ck = scls[col]; }
-    if (row < n) { const float* p = sorted + (long)row * 5; r0 = p[0]; r1 = p[1]; r2 = p[2]; r3 = p[3]; rk = scls[row]; }
-    const int col_size = (n - col_blk * 64) < 64 ? (n - col_blk * 64) : 64;
-    unsigned long long bits = 0ull;
-    const int start = (row_blk == col_blk) ? t + 1 : 0;
-    for (int i = 0; i < col_size; ++i) {
-        const float b0 = __shfl(c0, i, 64), b1 = __shfl(c1, i, 64), b2 = __shfl(c2, i, 64), b3 = __shfl(c3, i, 64);
-        const int bk = __shfl(ck, i, 64);
-        const float iou = dev_iou(r0, r1, r2, r3, b0, b1, b2, b3);
-        const bool hit = ((mode == 0) ? (iou > thresh) : (iou >= thresh)) && (bk == rk);
-        if (hit && i >= start) bits |= 1ull << i;
-    }
-    if (row < n) mask[nms_tri_row(row, cb) + (col_blk - row_blk)] = bits;
-}
-
 // classes[b, i] = cand_cls[b][keep[b, i]] (and anchors[b, i] = cand_anchor[b][keep[b, i]] when asked for) as int64 for i < num[b],
 // 0 for num[b] <= i < kmax: gather_class_kernel's padding rule
 __global__ void gather_cand_class_kernel(const int* __restrict__ cand_cls, const int* __restrict__ cand_anchor, long idx_stride,
@@ -502,20 +455,9 @@ __global__ void gather_cand_class_kernel(const int* __restrict__ cand_cls, const
     if (anchors) anchors[(long)b * out_stride + i] = a;
 }
 
-inline long align_up(long v, long a) { return (v + a - 1) / a * a; }
-
 }  // namespace
 
-extern "C" int mpn_box_decode_clip(const float* anchors, const float* deltas, float* boxes, int B, int A, float img_w,
-                                   float img_h, void* stream) {
-    MPN_CHECK_ARG(anchors && deltas && boxes && B > 0 && A > 0);
-    const long n = (long)B * A;
-    hipLaunchKernelGGL(box_decode_clip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, anchors, deltas,
-                       boxes, B, A, img_w, img_h, make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.1f, 0.1f, 0.2f, 0.2f));
-    return mpn_launch_status();
-}
-
-// BBoxTransform(mean, std) with non-default coefficients (utils.py:8-17): mean_std = {mean[0..3], std[0..3]} on the HOST
+// BBoxTransform(mean, std) (utils.py:8-17): mean_std = {mean[0..3], std[0..3]} on the HOST
 extern "C" int mpn_box_decode_clip_ms(const float* anchors, const float* deltas, float* boxes, int B, int A, float img_w,
                                       float img_h, const float* mean_std, void* stream) {
     MPN_CHECK_ARG(anchors && deltas && boxes && mean_std && B > 0 && A > 0);
@@ -524,6 +466,13 @@ extern "C" int mpn_box_decode_clip_ms(const float* anchors, const float* deltas,
                        boxes, B, A, img_w, img_h, make_float4(mean_std[0], mean_std[1], mean_std[2], mean_std[3]),
                        make_float4(mean_std[4], mean_std[5], mean_std[6], mean_std[7]));
     return mpn_launch_status();
+}
+
+// the reference's default coefficients (utils.py:10-17)
+extern "C" int mpn_box_decode_clip(const float* anchors, const float* deltas, float* boxes, int B, int A, float img_w,
+                                   float img_h, void* stream) {
+    static const float kDefaultMeanStd[8] = {0.f, 0.f, 0.f, 0.f, 0.1f, 0.1f, 0.2f, 0.2f};
+    return mpn_box_decode_clip_ms(anchors, deltas, boxes, B, A, img_w, img_h, kDefaultMeanStd, stream);
 }
 
 extern "C" int mpn_clip_boxes(float* boxes, int64_t n, float img_w, float img_h, void* stream) {
@@ -570,29 +519,26 @@ extern "C" int mpn_gather_class(const int64_t* cls_id, const int32_t* src, int A
 }
 
 namespace {
-struct NmsLayout { long off_order, off_remv, off_mask, total; int cb; };
-inline NmsLayout nms_layout(long nmax) {
-    NmsLayout l;
-    l.cb = (int)((nmax + 63) / 64);
-    l.off_order = align_up(nmax * 5 * 4, 256);
-    l.off_remv = l.off_order + align_up(nmax * 4, 256);
-    l.off_mask = l.off_remv + align_up((long)l.cb * 8, 256);
-    l.total = l.off_mask + align_up(64L * ((long)l.cb * (l.cb + 1) / 2) * 8, 256);      // upper triangle only (nms_tri_row)
-    return l;
-}
+// rank, mask and scan for B images; top_k 0 = no cap; cls NULL = suppression across classes, else among candidates of one class only
 inline int launch_nms(const float* dets, long dets_stride, const int* counts, int n_host, int B, long nmax, float thresh, int mode,
-                      int64_t* keep_out, long keep_stride, int64_t* num_out, void* workspace, hipStream_t st, long top_k = 0) {
+                      int64_t* keep_out, long keep_stride, int64_t* num_out, void* workspace, hipStream_t st, long top_k = 0,
+                      const int* cls = nullptr, long cls_stride = 0) {
     const long nlive = (top_k > 0 && top_k < nmax) ? top_k : nmax;      // rows of the sorted / mask scratch
-    const NmsLayout l = nms_layout(nlive);
     NmsBatch q;
     q.dets = dets; q.dets_stride = dets_stride; q.counts = counts; q.n_host = n_host;
-    q.ws = (char*)workspace; q.ws_stride = l.total;
-    q.off_order = l.off_order; q.off_remv = l.off_remv; q.off_mask = l.off_mask; q.cb = l.cb;
+    q.ws = (char*)workspace; q.l = nms_layout(nlive, cls != nullptr);
     q.cap = top_k > 0 ? (int)nlive : 0;
-    const long tri = (long)l.cb * (l.cb + 1) / 2;
+    q.cls = cls; q.cls_stride = cls_stride;
+    const long tri = (long)q.l.cb * (q.l.cb + 1) / 2;
     if (tri > 0x7fffffffL) return MPN_E_UNSUPPORTED;
-    hipLaunchKernelGGL(nms_rank_kernel, dim3((unsigned)((nmax + 255) / 256), 1, B), dim3(256), 0, st, q);
-    hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)tri, 1, B), dim3(64), 0, st, q, thresh, mode);
+    const dim3 rank_grid((unsigned)((nmax + 255) / 256), 1, B), mask_grid((unsigned)tri, 1, B);
+    if (cls) {
+        hipLaunchKernelGGL(nms_rank_kernel<true>, rank_grid, dim3(256), 0, st, q);
+        hipLaunchKernelGGL(nms_mask_kernel<true>, mask_grid, dim3(64), 0, st, q, thresh, mode);
+    } else {
+        hipLaunchKernelGGL(nms_rank_kernel<false>, rank_grid, dim3(256), 0, st, q);
+        hipLaunchKernelGGL(nms_mask_kernel<false>, mask_grid, dim3(64), 0, st, q, thresh, mode);
+    }
     hipLaunchKernelGGL(nms_scan_kernel, dim3(B), dim3(1024), 0, st, q, keep_out, keep_stride, num_out);
     return mpn_launch_status();
 }
@@ -600,7 +546,7 @@ inline int launch_nms(const float* dets, long dets_stride, const int* counts, in
 
 extern "C" int64_t mpn_nms_workspace_bytes(int64_t n) {
     if (n <= 0) return 256;
-    return nms_layout(n).total;
+    return nms_layout(n, false).total;
 }
 
 extern "C" int mpn_nms(const float* dets, int64_t n, float thresh, int mode, int64_t* keep_out, int64_t* num_out,
@@ -614,7 +560,7 @@ extern "C" int mpn_nms(const float* dets, int64_t n, float thresh, int mode, int
 
 extern "C" int64_t mpn_nms_batched_workspace_bytes(int B, int64_t nmax) {
     if (B <= 0 || nmax <= 0) return 256;
-    return (int64_t)B * nms_layout(nmax).total;
+    return (int64_t)B * nms_layout(nmax, false).total;
 }
 
 extern "C" int mpn_nms_batched(const float* dets, int64_t dets_stride, const int32_t* counts, int B, int64_t nmax, float thresh, int mode,
@@ -675,14 +621,9 @@ extern "C" int mpn_class_filter_fill(const float* boxes, const float* cls, int B
     return mpn_launch_status();
 }
 
-namespace {
-// an image's workspace: mpn_nms_batched's layout for `rows` rows, then the sorted classes [rows] i32
-inline long nms_class_ws(long rows) { return nms_layout(rows).total + align_up(rows * 4, 256); }
-}  // namespace
-
 extern "C" int64_t mpn_nms_batched_classes_workspace_bytes(int B, int64_t nmax) {
     if (B <= 0 || nmax <= 0) return 256;
-    return (int64_t)B * nms_class_ws((long)nmax);
+    return (int64_t)B * nms_layout(nmax, true).total;
 }
 
 extern "C" int mpn_nms_batched_classes(const float* dets, int64_t dets_stride, const int32_t* cand_cls, int64_t cls_stride,
@@ -691,21 +632,8 @@ extern "C" int mpn_nms_batched_classes(const float* dets, int64_t dets_stride, c
     MPN_CHECK_ARG(dets && cand_cls && counts && keep_out && num_out && workspace && B > 0 && (mode == 0 || mode == 1) && top_k >= 0);
     const int64_t nlive = (top_k > 0 && top_k < nmax) ? top_k : nmax;
     MPN_CHECK_ARG(nmax > 0 && nmax < (1 << 30) && keep_stride >= nlive && dets_stride >= nmax * 5 && cls_stride >= nmax);
-    const NmsLayout l = nms_layout((long)nlive);
-    NmsClassBatch qc;
-    NmsBatch& q = qc.q;
-    q.dets = dets; q.dets_stride = (long)dets_stride; q.counts = counts; q.n_host = 0;
-    q.ws = (char*)workspace; q.ws_stride = nms_class_ws((long)nlive);
-    q.off_order = l.off_order; q.off_remv = l.off_remv; q.off_mask = l.off_mask; q.cb = l.cb;
-    q.cap = top_k > 0 ? (int)nlive : 0;
-    qc.cls = cand_cls; qc.cls_stride = (long)cls_stride; qc.off_cls = l.total;
-    const long tri = (long)l.cb * (l.cb + 1) / 2;
-    if (tri > 0x7fffffffL) return MPN_E_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(nms_rank_class_kernel, dim3((unsigned)((nmax + 255) / 256), 1, B), dim3(256), 0, st, qc);
-    hipLaunchKernelGGL(nms_mask_class_kernel, dim3((unsigned)tri, 1, B), dim3(64), 0, st, qc, thresh, mode);
-    hipLaunchKernelGGL(nms_scan_kernel, dim3(B), dim3(1024), 0, st, q, keep_out, (long)keep_stride, num_out);
-    return mpn_launch_status();
+    return launch_nms(dets, (long)dets_stride, counts, 0, B, (long)nmax, thresh, mode, keep_out, (long)keep_stride, num_out, workspace,
+                      (hipStream_t)stream, (long)top_k, cand_cls, (long)cls_stride);
 }
 
 extern "C" int mpn_gather_cand_class(const int32_t* cand_cls, const int32_t* cand_anchor, int64_t idx_stride, const int64_t* keep,

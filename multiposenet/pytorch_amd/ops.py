@@ -1015,6 +1015,65 @@ def gather_class(cls_id0, src, keep):
     return out
 
 
+def _pre_nms_top_n(pre_nms_top_n, ncand):
+    """Cap of candidates per image entering NMS: the caller's pre_nms_top_n, else MPN_NMS_PRE_TOPN (nms_pre_topn_env), else 0 = none.
+    ncand: the most candidates of one image; above 32 768 of them and with no cap, warns once per process."""
+    if pre_nms_top_n is None and nms_pre_topn_env() > 0:
+        pre_nms_top_n = nms_pre_topn_env()
+    top = int(pre_nms_top_n) if pre_nms_top_n else 0
+    if top == 0 and ncand > 32768 and not _NMS_WARNED:
+        # the reference's behaviour (every candidate above the score threshold enters the suppression) costs the upper triangle of an
+        # N x N / 64 mask per image: 67 MB at 32 768 candidates, 0.6 GB at 100 000 — say so once instead of silently taking seconds
+        import warnings
+        _NMS_WARNED.append(True)
+        warnings.warn("NMS over %d candidates in one image (upper-triangle N x N / 128 mask = %.0f MB per image); pass pre_nms_top_n or set "
+                      "MPN_NMS_PRE_TOPN to bound it (not in the reference)" % (ncand, ncand * float(ncand) / 128 * 8 / 1e6))
+    return top
+
+
+def _no_detections(B, dev, padded, with_cls):
+    """What detect_batched / detect_batched_classwise return when no image of the batch has a candidate."""
+    if not padded:
+        return [(None, None, None) if with_cls else (None, None)] * B
+    out = (torch.zeros((B, 0, 4), dtype=torch.float32, device=dev), torch.zeros((B, 0), dtype=torch.float32, device=dev), [0] * B)
+    return out + (torch.zeros((B, 0), dtype=torch.int64, device=dev),) if with_cls else out
+
+
+def _suppress_and_gather(dets, dets_stride, counts, cnt, ncand, cand_cls, cls_stride, top, iou_thresh, mode, ws_limit, padded, gather_cls):
+    """The tail of detect_batched / detect_batched_classwise: per-image NMS over the candidate rows dets (dets_stride floats between
+    images, counts [B] int32 on the device = cnt on the host, ncand = max(cnt) > 0), class-wise when cand_cls (int32, cls_stride between
+    images) is given; then the gathers and host round trip 2, and the results in the shape the two functions document.
+    gather_cls: None, or a callable (keep, num, nmax, out) that enqueues the class gather into out [B,nmax] int64."""
+    B, dev = len(cnt), dets.device
+    nmax = min(ncand, top) if top > 0 else ncand       # rows of the sort / mask scratch and of the outputs
+    keep = torch.empty((B, nmax), dtype=torch.int64, device=dev)
+    num = torch.empty((B,), dtype=torch.int64, device=dev)
+    per_img = call("mpn_nms_batched_classes_workspace_bytes" if cand_cls is not None else "mpn_nms_batched_workspace_bytes", 1, nmax)
+    group = max(1, min(B, int(ws_limit // per_img)))   # bound the N x N/64 mask scratch; groups of images per launch set
+    for b0 in range(0, B, group):
+        nb = min(group, B - b0)
+        ws = workspace(per_img * nb, dev, slot=4)
+        rows = (ctypes.c_void_p(dets.data_ptr() + b0 * dets_stride * 4), dets_stride)
+        head = (ctypes.c_void_p(counts.data_ptr() + b0 * 4), nb, ncand)
+        tail = (float(iou_thresh), mode, ctypes.c_void_p(keep.data_ptr() + b0 * nmax * 8), nmax, ctypes.c_void_p(num.data_ptr() + b0 * 8),
+                ptr(ws), stream_ptr())
+        if cand_cls is not None:
+            call("mpn_nms_batched_classes", *(rows + (ctypes.c_void_p(cand_cls.data_ptr() + b0 * cls_stride * 4), cls_stride) + head + (top,) + tail))
+        elif top > 0:
+            call("mpn_nms_batched_topk", *(rows + head + (top,) + tail))
+        else:
+            call("mpn_nms_batched", *(rows + head + tail))
+    outs = (torch.empty((B, nmax, 4), dtype=torch.float32, device=dev), torch.empty((B, nmax), dtype=torch.float32, device=dev))
+    call("mpn_gather_dets_batched", ptr(dets), dets_stride, ptr(keep), nmax, ptr(num), B, nmax, ptr(outs[0]), ptr(outs[1]), nmax, stream_ptr())
+    if gather_cls is not None:
+        outs += (torch.empty((B, nmax), dtype=torch.int64, device=dev),)
+        gather_cls(keep, num, nmax, outs[2])
+    kept = num.tolist()                                # host round trip 2
+    if padded:
+        return outs[:2] + ([k if cnt[b] > 0 else 0 for b, k in enumerate(kept)],) + outs[2:]
+    return [tuple(o[b, :k] for o in outs) if cnt[b] > 0 else (None,) * len(outs) for b, k in enumerate(kept)]
+
+
 def detect_batched(boxes, scores, score_thresh, iou_thresh, mode=0, ws_limit=4 << 30, padded=False, pre_nms_top_n=None, cls_id=None):
     """Score filter + per-image NMS + gather for EVERY image of a batch with two host round trips per batch (the candidate
     counts size the NMS launches, the kept counts size the returned tensors) instead of two per image.
@@ -1032,53 +1091,15 @@ def detect_batched(boxes, scores, score_thresh, iou_thresh, mode=0, ws_limit=4 <
     call("mpn_score_filter_batched", ptr(boxes), ptr(scores), B, A, float(score_thresh), ptr(dets), ptr(src) if src is not None else None,
          ptr(counts), stream_ptr())
     cnt = counts.tolist()                              # host round trip 1
-    nmax = max(cnt)
-    if nmax == 0:
-        if padded:
-            out = (torch.zeros((B, 0, 4), dtype=torch.float32, device=dev), torch.zeros((B, 0), dtype=torch.float32, device=dev), [0] * B)
-            return out + (torch.zeros((B, 0), dtype=torch.int64, device=dev),) if cls_id is not None else out
-        return [(None, None, None) if cls_id is not None else (None, None)] * B
-    ncand = nmax
-    if pre_nms_top_n is None and nms_pre_topn_env() > 0:
-        pre_nms_top_n = nms_pre_topn_env()
-    top = int(pre_nms_top_n) if pre_nms_top_n else 0
-    if top == 0 and nmax > 32768 and not _NMS_WARNED:
-        # the reference's behaviour (every candidate above the score threshold enters the suppression) costs the upper triangle of an
-        # N x N / 64 mask per image: 67 MB at 32 768 candidates, 0.6 GB at 100 000 — say so once instead of silently taking seconds
-        import warnings
-        _NMS_WARNED.append(True)
-        warnings.warn("NMS over %d candidates in one image (upper-triangle N x N / 128 mask = %.0f MB per image); pass pre_nms_top_n or set "
-                      "MPN_NMS_PRE_TOPN to bound it (not in the reference)" % (nmax, nmax * float(nmax) / 128 * 8 / 1e6))
-    if top > 0:
-        nmax = min(nmax, top)                          # rows of the sort / mask scratch and of the outputs
-    keep = torch.empty((B, nmax), dtype=torch.int64, device=dev)
-    num = torch.empty((B,), dtype=torch.int64, device=dev)
-    per_img = call("mpn_nms_batched_workspace_bytes", 1, nmax)
-    group = max(1, min(B, int(ws_limit // per_img)))   # bound the N x N/64 mask scratch; groups of images per launch set
-    for b0 in range(0, B, group):
-        nb = min(group, B - b0)
-        ws = workspace(per_img * nb, dev, slot=4)
-        head = (ctypes.c_void_p(dets.data_ptr() + b0 * A * 5 * 4), A * 5, ctypes.c_void_p(counts.data_ptr() + b0 * 4), nb, ncand)
-        tail = (float(iou_thresh), mode, ctypes.c_void_p(keep.data_ptr() + b0 * nmax * 8), nmax, ctypes.c_void_p(num.data_ptr() + b0 * 8),
-                ptr(ws), stream_ptr())
-        if top > 0:
-            call("mpn_nms_batched_topk", *(head + (top,) + tail))
-        else:
-            call("mpn_nms_batched", *(head + tail))
-    out_boxes = torch.empty((B, nmax, 4), dtype=torch.float32, device=dev)
-    out_scores = torch.empty((B, nmax), dtype=torch.float32, device=dev)
-    call("mpn_gather_dets_batched", ptr(dets), A * 5, ptr(keep), nmax, ptr(num), B, nmax, ptr(out_boxes), ptr(out_scores), nmax, stream_ptr())
-    out_cls = None
+    ncand = max(cnt)
+    if ncand == 0:
+        return _no_detections(B, dev, padded, cls_id is not None)
+    gather_cls = None
     if cls_id is not None:
-        out_cls = torch.empty((B, nmax), dtype=torch.int64, device=dev)
-        call("mpn_gather_class", ptr(cls_id), ptr(src), A, ptr(keep), nmax, ptr(num), B, nmax, ptr(out_cls), nmax, stream_ptr())
-    kept = num.tolist()                                # host round trip 2
-    if padded:
-        out = (out_boxes, out_scores, [k if cnt[b] > 0 else 0 for b, k in enumerate(kept)])
-        return out + (out_cls,) if out_cls is not None else out
-    if out_cls is not None:
-        return [(out_boxes[b, :k], out_scores[b, :k], out_cls[b, :k]) if cnt[b] > 0 else (None, None, None) for b, k in enumerate(kept)]
-    return [(out_boxes[b, :k], out_scores[b, :k]) if cnt[b] > 0 else (None, None) for b, k in enumerate(kept)]
+        def gather_cls(keep, num, nmax, out):
+            call("mpn_gather_class", ptr(cls_id), ptr(src), A, ptr(keep), nmax, ptr(num), B, nmax, ptr(out), nmax, stream_ptr())
+    return _suppress_and_gather(dets, A * 5, counts, cnt, ncand, None, 0, _pre_nms_top_n(pre_nms_top_n, ncand), iou_thresh, mode, ws_limit,
+                                padded, gather_cls)
 
 
 def detect_batched_classwise(boxes, cls, score_thresh, iou_thresh, mode=0, ws_limit=4 << 30, padded=False, pre_nms_top_n=None):
@@ -1104,44 +1125,17 @@ def detect_batched_classwise(boxes, cls, score_thresh, iou_thresh, mode=0, ws_li
     cnt = counts.tolist()                              # host round trip 1
     ncand = max(cnt)
     if ncand == 0:
-        if padded:
-            return (torch.zeros((B, 0, 4), dtype=torch.float32, device=dev), torch.zeros((B, 0), dtype=torch.float32, device=dev), [0] * B,
-                    torch.zeros((B, 0), dtype=torch.int64, device=dev))
-        return [(None, None, None)] * B
+        return _no_detections(B, dev, padded, True)
     dets = torch.empty((B, ncand, 5), dtype=torch.float32, device=dev)
     cand_cls = torch.empty((B, ncand), dtype=torch.int32, device=dev)
     cand_anchor = torch.empty((B, ncand), dtype=torch.int32, device=dev)
     call("mpn_class_filter_fill", ptr(boxes), ptr(cls), B, A, K, float(score_thresh), ptr(chunk_cnt), ncand, ptr(dets), ncand * 5, ptr(cand_cls),
          ptr(cand_anchor), ncand, ptr(counts), stream_ptr())
-    if pre_nms_top_n is None and nms_pre_topn_env() > 0:
-        pre_nms_top_n = nms_pre_topn_env()
-    top = int(pre_nms_top_n) if pre_nms_top_n else 0
-    if top == 0 and ncand > 32768 and not _NMS_WARNED:
-        import warnings
-        _NMS_WARNED.append(True)
-        warnings.warn("NMS over %d candidates in one image (upper-triangle N x N / 128 mask = %.0f MB per image); pass pre_nms_top_n or set "
-                      "MPN_NMS_PRE_TOPN to bound it (not in the reference)" % (ncand, ncand * float(ncand) / 128 * 8 / 1e6))
-    nmax = min(ncand, top) if top > 0 else ncand       # rows of the sort / mask scratch and of the outputs
-    keep = torch.empty((B, nmax), dtype=torch.int64, device=dev)
-    num = torch.empty((B,), dtype=torch.int64, device=dev)
-    per_img = call("mpn_nms_batched_classes_workspace_bytes", 1, nmax)
-    group = max(1, min(B, int(ws_limit // per_img)))
-    for b0 in range(0, B, group):
-        nb = min(group, B - b0)
-        ws = workspace(per_img * nb, dev, slot=4)
-        call("mpn_nms_batched_classes", ctypes.c_void_p(dets.data_ptr() + b0 * ncand * 5 * 4), ncand * 5,
-             ctypes.c_void_p(cand_cls.data_ptr() + b0 * ncand * 4), ncand, ctypes.c_void_p(counts.data_ptr() + b0 * 4), nb, ncand, top,
-             float(iou_thresh), mode, ctypes.c_void_p(keep.data_ptr() + b0 * nmax * 8), nmax, ctypes.c_void_p(num.data_ptr() + b0 * 8), ptr(ws),
-             stream_ptr())
-    out_boxes = torch.empty((B, nmax, 4), dtype=torch.float32, device=dev)
-    out_scores = torch.empty((B, nmax), dtype=torch.float32, device=dev)
-    out_cls = torch.empty((B, nmax), dtype=torch.int64, device=dev)
-    call("mpn_gather_dets_batched", ptr(dets), ncand * 5, ptr(keep), nmax, ptr(num), B, nmax, ptr(out_boxes), ptr(out_scores), nmax, stream_ptr())
-    call("mpn_gather_cand_class", ptr(cand_cls), None, ncand, ptr(keep), nmax, ptr(num), B, nmax, ptr(out_cls), None, nmax, stream_ptr())
-    kept = num.tolist()                                # host round trip 2
-    if padded:
-        return out_boxes, out_scores, [k if cnt[b] > 0 else 0 for b, k in enumerate(kept)], out_cls
-    return [(out_boxes[b, :k], out_scores[b, :k], out_cls[b, :k]) if cnt[b] > 0 else (None, None, None) for b, k in enumerate(kept)]
+
+    def gather_cls(keep, num, nmax, out):
+        call("mpn_gather_cand_class", ptr(cand_cls), None, ncand, ptr(keep), nmax, ptr(num), B, nmax, ptr(out), None, nmax, stream_ptr())
+    return _suppress_and_gather(dets, ncand * 5, counts, cnt, ncand, cand_cls, ncand, _pre_nms_top_n(pre_nms_top_n, ncand), iou_thresh, mode,
+                                ws_limit, padded, gather_cls)
 
 
 def score_filter(boxes0, scores0, thresh):

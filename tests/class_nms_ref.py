@@ -1,5 +1,5 @@
 """Inputs and two independent numpy formulations of the class-wise post-processing of a K-class detection head (csrc/nms.hip:
-class_filter_count_kernel / class_filter_fill_kernel, nms_rank_class_kernel / nms_mask_class_kernel, gather_cand_class_kernel;
+class_filter_count_kernel / class_filter_fill_kernel, nms_rank_kernel<true> / nms_mask_kernel<true>, gather_cand_class_kernel;
 ops.detect_batched_classwise).  The contract (include/mpn.h, "Class-wise candidates and NMS"):
 
   1. every flat index f = a*K + c with cls[b,a,c] > thr (strict; NaN fails) is a candidate, listed in ascending f;

@@ -149,6 +149,33 @@ def test_class_nms_entry_points_size_their_buffers_and_reject_bad_arguments_with
         assert L.mpn_gather_cand_class(*args) == BAD, (pos, val)
 
 
+def test_pre_nms_cap_is_the_argument_then_the_environment_at_call_time_and_only_an_uncapped_dense_image_warns_once(monkeypatch):
+    import warnings
+    from multiposenet.pytorch_amd import ops
+    monkeypatch.setattr(ops, "_NMS_WARNED", [])          # the once-per-process latch, fresh for this test
+    monkeypatch.delenv("MPN_NMS_PRE_TOPN", raising=False)
+    assert ops._pre_nms_top_n(None, 100) == 0 and ops._pre_nms_top_n(70, 100) == 70
+    monkeypatch.setenv("MPN_NMS_PRE_TOPN", "300")
+    assert ops._pre_nms_top_n(None, 100) == 300
+    assert ops._pre_nms_top_n(50, 100) == 50 and ops._pre_nms_top_n(0, 100) == 0          # an explicit value, 0 = no cap included, wins
+    monkeypatch.delenv("MPN_NMS_PRE_TOPN")
+    assert ops._pre_nms_top_n(None, 100) == 0                                             # read at call time, not at import
+    for junk in ("", "many", "1.5", "-5"):
+        monkeypatch.setenv("MPN_NMS_PRE_TOPN", junk)
+        assert ops._pre_nms_top_n(None, 100) == 0, junk
+    with warnings.catch_warnings(record=True) as seen:
+        warnings.simplefilter("always")
+        monkeypatch.setenv("MPN_NMS_PRE_TOPN", "1000")
+        assert ops._pre_nms_top_n(None, 100000) == 1000 and ops._pre_nms_top_n(2000, 100000) == 2000
+        monkeypatch.delenv("MPN_NMS_PRE_TOPN")
+        assert ops._pre_nms_top_n(None, 32768) == 0
+        assert not seen and not ops._NMS_WARNED, "a capped call, or 32 768 candidates, must neither warn nor use up the one warning"
+        assert ops._pre_nms_top_n(None, 32769) == 0
+        assert len(seen) == 1 and "32769 candidates" in str(seen[0].message) and "MPN_NMS_PRE_TOPN" in str(seen[0].message)
+        assert ops._pre_nms_top_n(None, 100000) == 0 and ops._pre_nms_top_n(None, 32769) == 0
+        assert len(seen) == 1, "the warning fires once per process"
+
+
 def test_public_interface_carries_the_opt_in_arguments_with_their_defaults():
     import inspect
     from multiposenet.pytorch_amd import ops
