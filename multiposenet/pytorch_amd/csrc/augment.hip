@@ -26,10 +26,13 @@ struct Geo {
     double scale, nw, nh, cw, ch, m00, m01, m02, m10, m11, m12, ox, oy;
     bool flip, ok;
 };
+struct Rect { int x0, y0, w, h; };   // an instance's bounding rectangle inside its H x W source
 
 // Table row -> registers.  `ok` guards the gather: a row whose source does not lie inside the packed buffer is never dereferenced
-// (the element is written as NaN instead); the host wrapper never produces such a row.
-__device__ __forceinline__ Geo load_geo(const double* __restrict__ row, bool mask, long src_bytes, int bytes_per_pixel) {
+// (the element is written as NaN instead); the host wrapper never produces such a row.  What lies at the offset is the whole H x W
+// source, or, for an instance row of mpn_augment_boxes (`rect` given: a sample row whose MASK_OFF / MASK_PITCH address the packed
+// rectangle, plus the MPN_AUGB_* columns), the rectangle, which must itself lie inside the source.
+__device__ __forceinline__ Geo load_geo(const double* __restrict__ row, bool mask, long src_bytes, int bytes_per_pixel, Rect* rect = nullptr) {
     Geo g;
     g.off = (long)row[mask ? MPN_AUG_MASK_OFF : MPN_AUG_IMG_OFF];
     g.pitch = (long)row[mask ? MPN_AUG_MASK_PITCH : MPN_AUG_IMG_PITCH];
@@ -37,8 +40,17 @@ __device__ __forceinline__ Geo load_geo(const double* __restrict__ row, bool mas
     g.ok = H >= 1.0 && H <= 65536.0 && W >= 1.0 && W <= 65536.0;
     g.H = g.ok ? (int)H : 1;
     g.W = g.ok ? (int)W : 1;
-    g.ok = g.ok && g.off >= 0 && g.pitch >= (long)g.W * bytes_per_pixel && g.off <= src_bytes &&
-           g.pitch <= src_bytes && (long)(g.H - 1) * g.pitch + (long)g.W * bytes_per_pixel <= src_bytes - g.off;
+    int rows = g.H, cols = g.W;
+    if (rect) {
+        const double x0 = row[MPN_AUGB_RX0], y0 = row[MPN_AUGB_RY0], w = row[MPN_AUGB_RW], h = row[MPN_AUGB_RH];
+        g.ok = g.ok && x0 >= 0.0 && y0 >= 0.0 && w >= 1.0 && h >= 1.0 && x0 + w <= W && y0 + h <= H;
+        rect->x0 = g.ok ? (int)x0 : 0; rect->y0 = g.ok ? (int)y0 : 0;
+        rect->w = cols = g.ok ? (int)w : 1; rect->h = rows = g.ok ? (int)h : 1;
+    }
+    // the buffer guard: `rows` rows of `row_bytes` bytes, `pitch` bytes apart from byte `off`, lie inside the `src_bytes` of the buffer
+    const long row_bytes = (long)cols * bytes_per_pixel;
+    g.ok = g.ok && g.off >= 0 && g.pitch >= row_bytes && g.off <= src_bytes && g.pitch <= src_bytes &&
+           (long)(rows - 1) * g.pitch + row_bytes <= src_bytes - g.off;
     g.scale = row[MPN_AUG_SCALE];
     g.nw = row[MPN_AUG_NW]; g.nh = row[MPN_AUG_NH]; g.cw = row[MPN_AUG_CW]; g.ch = row[MPN_AUG_CH];
     g.m00 = row[MPN_AUG_MINV + 0]; g.m01 = row[MPN_AUG_MINV + 1]; g.m02 = row[MPN_AUG_MINV + 2];
@@ -46,15 +58,6 @@ __device__ __forceinline__ Geo load_geo(const double* __restrict__ row, bool mas
     g.ox = row[MPN_AUG_OX]; g.oy = row[MPN_AUG_OY];
     g.flip = row[MPN_AUG_FLIP] != 0.0;
     return g;
-}
-
-// OpenCV interpolateCubic (imgproc/resize.cpp), float32, A = -0.75
-__device__ __forceinline__ void cubic_coeffs(float x, float* c) {
-    const float A = -0.75f;
-    c[0] = ((A * (x + 1.0f) - 5.0f * A) * (x + 1.0f) + 8.0f * A) * (x + 1.0f) - 4.0f * A;
-    c[1] = ((A + 2.0f) * x - (A + 3.0f)) * x * x + 1.0f;
-    c[2] = ((A + 2.0f) * (1.0f - x) - (A + 3.0f)) * (1.0f - x) * (1.0f - x) + 1.0f;
-    c[3] = 1.0f - c[0] - c[1] - c[2];
 }
 
 struct Taps {
@@ -89,6 +92,25 @@ __device__ __forceinline__ Taps map_point(const Geo& g, double xr, double yr) {
     return t;
 }
 
+// The 16-term float32 sum of C channels: fetch(k, l, p) supplies the tap of row t.y[k], column t.x[l].  Fixed operation order:
+// row = p * wx[0]; row += p * wx[l]; acc = row * wy[0]; acc += row * wy[k].
+template <int C, typename Fetch>
+__device__ __forceinline__ void cubic_sum(const Taps& t, Fetch fetch, float (&acc)[C]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float row[C];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) {
+            float p[C];
+            fetch(k, l, p);
+#pragma unroll
+            for (int c = 0; c < C; ++c) row[c] = l == 0 ? p[c] * t.wx[0] : row[c] + p[c] * t.wx[l];
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[c] = k == 0 ? row[c] * t.wy[0] : acc[c] + row[c] * t.wy[k];
+    }
+}
+
 __device__ __forceinline__ float clamp255(float v) { return fminf(fmaxf(v, 0.0f), 255.0f); }
 
 struct Norm { float mean[3], stdv[3]; };
@@ -109,20 +131,12 @@ __global__ void __launch_bounds__(256) augment_image_kernel(const uint8_t* __res
         const Taps t = map_point(g, g.ox + (double)up, g.oy + (double)v);
         if (t.inside) {
             const uint8_t* base = src + g.off;
-            float acc[3] = {0.0f, 0.0f, 0.0f};
+            float acc[3];
+            cubic_sum(t, [&](int k, int l, float (&p)[3]) {
+                const uint8_t* q = base + (long)t.y[k] * g.pitch + t.x[l] * 3;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint8_t* r = base + (long)t.y[k] * g.pitch;
-                float row[3];
-#pragma unroll
-                for (int l = 0; l < 4; ++l) {
-                    const uint8_t* p = r + t.x[l] * 3;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) row[c] = l == 0 ? (float)p[c] * t.wx[0] : row[c] + (float)p[c] * t.wx[l];
-                }
-#pragma unroll
-                for (int c = 0; c < 3; ++c) acc[c] = k == 0 ? row[c] * t.wy[0] : acc[c] + row[c] * t.wy[k];
-            }
+                for (int c = 0; c < 3; ++c) p[c] = (float)q[c];
+            }, acc);
 #pragma unroll
             for (int c = 0; c < 3; ++c) bgr[c] = clamp255(acc[c]);
         }
@@ -148,16 +162,9 @@ __global__ void __launch_bounds__(256) augment_mask_kernel(const uint8_t* __rest
         const Taps t = map_point(g, g.ox + pf, g.oy + py);
         if (t.inside) {
             const uint8_t* base = src + g.off;
-            float acc = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const uint8_t* r = base + (long)t.y[k] * g.pitch;
-                float row = (float)r[t.x[0]] * t.wx[0];
-#pragma unroll
-                for (int l = 1; l < 4; ++l) row = row + (float)r[t.x[l]] * t.wx[l];
-                acc = k == 0 ? row * t.wy[0] : acc + row * t.wy[k];
-            }
-            val = clamp255(acc);
+            float acc[1];
+            cubic_sum(t, [&](int k, int l, float (&p)[1]) { p[0] = (float)base[(long)t.y[k] * g.pitch + t.x[l]]; }, acc);
+            val = clamp255(acc[0]);
         }
     }
     val = val / 255.0f;
@@ -176,43 +183,37 @@ constexpr int BOX_TILE_Y = 4 * BOX_ROWS;
 constexpr int BOX_REC = 5;                    // int32 per partial record: min x, max x, min y, max y, flag (0 none, 1 any, -1 bad row)
 constexpr int BOX_EMPTY_MIN = 0x7fffffff;
 
-struct Rect { int x0, y0, w, h; };
-
-// The instance row is a sample row (MASK_OFF / MASK_PITCH address the packed rectangle, H / W are the full source) plus the
-// rectangle.  load_geo's guard speaks about an H x W source at MASK_OFF; what is stored there is the rectangle, so the guard is
-// re-stated for it: the rectangle lies inside the source and its rh rows of rw bytes lie inside the packed buffer.
-__device__ __forceinline__ Geo load_geo_rect(const double* __restrict__ row, long src_bytes, Rect& r) {
-    Geo g = load_geo(row, true, src_bytes, 1);
-    const double H = row[MPN_AUG_H], W = row[MPN_AUG_W];
-    const double x0 = row[MPN_AUGB_RX0], y0 = row[MPN_AUGB_RY0], w = row[MPN_AUGB_RW], h = row[MPN_AUGB_RH];
-    bool ok = H >= 1.0 && H <= 65536.0 && W >= 1.0 && W <= 65536.0;
-    ok = ok && x0 >= 0.0 && y0 >= 0.0 && w >= 1.0 && h >= 1.0 && x0 + w <= W && y0 + h <= H;
-    r.x0 = ok ? (int)x0 : 0; r.y0 = ok ? (int)y0 : 0; r.w = ok ? (int)w : 1; r.h = ok ? (int)h : 1;
-    g.ok = ok && g.off >= 0 && g.pitch >= (long)r.w && g.off <= src_bytes && g.pitch <= src_bytes &&
-           (long)(r.h - 1) * g.pitch + (long)r.w <= src_bytes - g.off;
-    return g;
-}
-
-__device__ __forceinline__ int wave_min(int v) {
+template <typename Op>
+__device__ __forceinline__ int wave_reduce(int v, Op op) {
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
+    for (int d = 32; d >= 1; d >>= 1) v = op(v, __shfl_xor(v, d, 64));
     return v;
 }
-__device__ __forceinline__ int wave_max(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
-}
+__device__ __forceinline__ int imin(int a, int b) { return min(a, b); }
+__device__ __forceinline__ int imax(int a, int b) { return max(a, b); }
+
+// extents of a set of ON pixels; x_hi < 0 = empty.  Every fold is integer min / max in a fixed order.
+struct Extent {
+    int x_lo, x_hi, y_lo, y_hi;
+    __device__ static Extent none() { return {BOX_EMPTY_MIN, -1, BOX_EMPTY_MIN, -1}; }
+    __device__ void merge(const Extent& e) {
+        x_lo = min(x_lo, e.x_lo); x_hi = max(x_hi, e.x_hi); y_lo = min(y_lo, e.y_lo); y_hi = max(y_hi, e.y_hi);
+    }
+    __device__ void add(int u, int v) { merge({u, u, v, v}); }
+    __device__ void wave_fold() {
+        x_lo = wave_reduce(x_lo, imin); x_hi = wave_reduce(x_hi, imax); y_lo = wave_reduce(y_lo, imin); y_hi = wave_reduce(y_hi, imax);
+    }
+};
 
 __global__ void __launch_bounds__(256) augment_box_scan_kernel(const uint8_t* __restrict__ src, long src_bytes, const double* __restrict__ table,
                                                                int32_t* __restrict__ partial, int crop_y, int crop_x) {
     // block = 64 x 16 pixels of the (crop_y + 1) x (crop_x + 1) mask frame of instance blockIdx.z; a wave is 64 consecutive pixels
     // of one row and walks BOX_ROWS rows.  Lanes past the frame stay OFF: no early return, every lane takes part in the reduction.
-    __shared__ int red[4][4];
+    __shared__ Extent red[4];
     const int u = blockIdx.x * 64 + threadIdx.x, inst = blockIdx.z;
     Rect rc;
-    const Geo g = load_geo_rect(table + (long)inst * MPN_AUGB_COLS, src_bytes, rc);
-    int x_lo = BOX_EMPTY_MIN, x_hi = -1, y_lo = BOX_EMPTY_MIN, y_hi = -1;
+    const Geo g = load_geo(table + (long)inst * MPN_AUGB_COLS, true, src_bytes, 1, &rc);
+    Extent e = Extent::none();
     if (g.ok && u <= crop_x) {
         const uint8_t* base = src + g.off;
         const int up = g.flip ? crop_x - u : u;                       // the mask is flipped over its OWN width, crop_x + 1
@@ -222,7 +223,8 @@ __global__ void __launch_bounds__(256) augment_box_scan_kernel(const uint8_t* __
             if (v > crop_y) break;
             const Taps t = map_point(g, g.ox + (double)up, g.oy + (double)v);
             if (!t.inside) continue;                                  // border 0, pad 0
-            // a tap outside the rectangle reads 0 (the mask is 0 there) and is not dereferenced
+            // a tap outside the rectangle reads 0 (the mask is 0 there) and is not dereferenced.  cubic_sum's order, written out: as a
+            // per-tap fetch the rectangle test forms the row address per tap and measures 6 % slower (profiles/augment_one_sampler_ab.txt)
             int cx[4];
             bool inx[4];
 #pragma unroll
@@ -244,27 +246,20 @@ __global__ void __launch_bounds__(256) augment_box_scan_kernel(const uint8_t* __
                 for (int l = 1; l < 4; ++l) row = row + p[l] * t.wx[l];
                 acc = k == 0 ? row * t.wy[0] : acc + row * t.wy[k];
             }
-            if (acc >= 0.5f) {
-                x_lo = min(x_lo, u); x_hi = max(x_hi, u);
-                y_lo = min(y_lo, v); y_hi = max(y_hi, v);
-            }
+            if (acc >= 0.5f) e.add(u, v);
         }
     }
     // stage 1: in the wave; stage 2: the four waves through LDS; one record per (instance, tile), ordinary stores
-    x_lo = wave_min(x_lo); x_hi = wave_max(x_hi); y_lo = wave_min(y_lo); y_hi = wave_max(y_hi);
-    if (threadIdx.x == 0) {
-        red[threadIdx.y][0] = x_lo; red[threadIdx.y][1] = x_hi; red[threadIdx.y][2] = y_lo; red[threadIdx.y][3] = y_hi;
-    }
+    e.wave_fold();
+    if (threadIdx.x == 0) red[threadIdx.y] = e;
     __syncthreads();
     if (threadIdx.x == 0 && threadIdx.y == 0) {
 #pragma unroll
-        for (int w = 1; w < 4; ++w) {
-            x_lo = min(x_lo, red[w][0]); x_hi = max(x_hi, red[w][1]); y_lo = min(y_lo, red[w][2]); y_hi = max(y_hi, red[w][3]);
-        }
+        for (int w = 1; w < 4; ++w) e.merge(red[w]);
         const long tiles = (long)gridDim.x * gridDim.y;
         int32_t* o = partial + ((long)inst * tiles + (long)blockIdx.y * gridDim.x + blockIdx.x) * BOX_REC;
-        o[0] = x_lo; o[1] = x_hi; o[2] = y_lo; o[3] = y_hi;
-        o[4] = !g.ok ? -1 : (x_hi >= 0 ? 1 : 0);
+        o[0] = e.x_lo; o[1] = e.x_hi; o[2] = e.y_lo; o[3] = e.y_hi;
+        o[4] = !g.ok ? -1 : (e.x_hi >= 0 ? 1 : 0);
     }
 }
 
@@ -278,22 +273,22 @@ __global__ void __launch_bounds__(64) augment_box_finalize_kernel(const int32_t*
         if (threadIdx.x < 5) o[threadIdx.x] = inst < 0 ? -1.0f : __builtin_nanf("");
         return;
     }
-    int x_lo = BOX_EMPTY_MIN, x_hi = -1, y_lo = BOX_EMPTY_MIN, y_hi = -1, bad = 0;
+    Extent e = Extent::none();
+    int bad = 0;
     const int32_t* p = partial + (long)inst * tiles * BOX_REC;
     for (int t = threadIdx.x; t < tiles; t += 64) {
         const int32_t* q = p + (long)t * BOX_REC;
-        if (q[4] > 0) {
-            x_lo = min(x_lo, q[0]); x_hi = max(x_hi, q[1]); y_lo = min(y_lo, q[2]); y_hi = max(y_hi, q[3]);
-        }
+        if (q[4] > 0) e.merge({q[0], q[1], q[2], q[3]});
         bad = max(bad, q[4] < 0 ? 1 : 0);
     }
-    x_lo = wave_min(x_lo); x_hi = wave_max(x_hi); y_lo = wave_min(y_lo); y_hi = wave_max(y_hi); bad = wave_max(bad);
+    e.wave_fold();
+    bad = wave_reduce(bad, imax);
     if (threadIdx.x == 0) {
         if (bad) {
             for (int k = 0; k < 5; ++k) o[k] = __builtin_nanf("");
-        } else if (x_hi >= 0) {
+        } else if (e.x_hi >= 0) {
             // COCO_data_pipeline.py:393-398: x2 and y2 are not part of the box, class 0
-            o[0] = (float)x_lo; o[1] = (float)y_lo; o[2] = (float)(x_hi + 1); o[3] = (float)(y_hi + 1); o[4] = 0.0f;
+            o[0] = (float)e.x_lo; o[1] = (float)e.y_lo; o[2] = (float)(e.x_hi + 1); o[3] = (float)(e.y_hi + 1); o[4] = 0.0f;
         } else {
             for (int k = 0; k < 5; ++k) o[k] = -1.0f;                 // :399-402: warped out of the crop
         }
@@ -328,11 +323,15 @@ extern "C" int mpn_augment_mask(const uint8_t* src, int64_t src_bytes, const dou
     return mpn_launch_status();
 }
 
-static inline long box_tiles(int crop_y, int crop_x) { return (long)((crop_x + 1 + 63) / 64) * (long)((crop_y + 1 + BOX_TILE_Y - 1) / BOX_TILE_Y); }
+// 64 x BOX_TILE_Y tiles over the (crop_y + 1) x (crop_x + 1) mask frame: the scan's grid, one partial record per tile
+static inline dim3 box_grid(int crop_y, int crop_x, int n_inst) {
+    return dim3((unsigned)((crop_x + 1 + 63) / 64), (unsigned)((crop_y + 1 + BOX_TILE_Y - 1) / BOX_TILE_Y), (unsigned)n_inst);
+}
 
 extern "C" int64_t mpn_augment_boxes_workspace_bytes(int n_inst, int crop_y, int crop_x) {
     if (n_inst < 0 || n_inst > 65535 || crop_y <= 0 || crop_x <= 0 || crop_y > 65535 || crop_x > 65535) return 0;
-    return (int64_t)n_inst * box_tiles(crop_y, crop_x) * BOX_REC * (int64_t)sizeof(int32_t);
+    const dim3 grid = box_grid(crop_y, crop_x, n_inst);
+    return (int64_t)grid.z * grid.x * grid.y * BOX_REC * (int64_t)sizeof(int32_t);
 }
 
 extern "C" int mpn_augment_boxes(const uint8_t* src, int64_t src_bytes, const double* table, int n_inst, const int32_t* row_inst, int n_rows,
@@ -340,10 +339,10 @@ extern "C" int mpn_augment_boxes(const uint8_t* src, int64_t src_bytes, const do
     MPN_CHECK_ARG(n_inst >= 0 && n_inst <= 65535 && n_rows >= 0 && crop_y > 0 && crop_x > 0 && crop_y <= 65535 && crop_x <= 65535);
     MPN_CHECK_ARG(n_inst == 0 || (src && table && workspace && src_bytes > 0));
     MPN_CHECK_ARG(n_rows == 0 || (row_inst && out));
-    const long tiles = box_tiles(crop_y, crop_x);
+    const dim3 grid = box_grid(crop_y, crop_x, n_inst);
+    const long tiles = (long)grid.x * grid.y;
     MPN_CHECK_ARG(tiles <= 0x7fffffffL / BOX_REC);
     if (n_inst > 0) {
-        dim3 grid((unsigned)((crop_x + 1 + 63) / 64), (unsigned)((crop_y + 1 + BOX_TILE_Y - 1) / BOX_TILE_Y), (unsigned)n_inst);
         hipLaunchKernelGGL(augment_box_scan_kernel, grid, dim3(64, 4), 0, (hipStream_t)stream, src, (long)src_bytes, table,
                            (int32_t*)workspace, crop_y, crop_x);
     }

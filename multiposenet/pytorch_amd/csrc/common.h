@@ -93,6 +93,16 @@ template <> struct Vec16<f16_t> {
     }
 };
 
+// OpenCV interpolateCubic (imgproc/resize.cpp): the four float32 weights of a cubic tap row at fraction x, A = -0.75.  Users are
+// built with -ffp-contract=off: tests restate this operation order.
+__device__ __forceinline__ void cubic_coeffs(float x, float (&c)[4]) {
+    const float A = -0.75f;
+    c[0] = ((A * (x + 1.f) - 5.f * A) * (x + 1.f) + 8.f * A) * (x + 1.f) - 4.f * A;
+    c[1] = ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
+    c[2] = ((A + 2.f) * (1.f - x) - (A + 3.f)) * (1.f - x) * (1.f - x) + 1.f;
+    c[3] = 1.f - c[0] - c[1] - c[2];
+}
+
 // XCD-aware bijective block remap (8 XCDs; block b is observed to run on XCD b % 8): blocks that
 // land on one XCD get a contiguous range of logical tile ids, so neighbouring tiles share an L2.
 __device__ __forceinline__ int xcd_remap(int b, int n) {

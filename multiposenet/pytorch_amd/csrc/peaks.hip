@@ -12,14 +12,6 @@ namespace {
 
 constexpr int PK_THREADS = 256;
 
-__device__ __forceinline__ void cubic_coeffs(float x, float (&c)[4]) {
-    const float A = -0.75f;
-    c[0] = ((A * (x + 1.f) - 5.f * A) * (x + 1.f) + 8.f * A) * (x + 1.f) - 4.f * A;
-    c[1] = ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
-    c[2] = ((A + 2.f) * (1.f - x) - (A + 3.f)) * (1.f - x) * (1.f - x) + 1.f;
-    c[3] = 1.f - c[0] - c[1] - c[2];
-}
-
 __device__ __forceinline__ void cubic_taps(int d, double scale, int n_src, int (&idx)[4], float (&co)[4]) {
     const float fx = (float)(((double)d + 0.5) * scale - 0.5);
     const int sx = (int)floorf(fx);

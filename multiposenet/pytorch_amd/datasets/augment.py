@@ -144,29 +144,17 @@ def _rotatepoint(p, R):
     return p
 
 
-def augment_meta(H, W, scale_provided, objpos, joint_self, joint_others, dice, crop_x, crop_y, params=None, objpos_other=None,
-                 with_mask=True):
-    """The meta-data side of aug_scale -> aug_rotate -> aug_croppad -> aug_flip for one sample, op for op.
-
-    joint_self [18, 3] / joint_others [n, 18, 3] (after :func:`add_neck`), objpos [2] in source pixels; ``dice`` as laid out by
-    :func:`draw_dice`.  Returns a dict: the transformed ``joint_self`` / ``joint_others`` / ``objpos`` / ``objpos_other`` (before
-    :func:`remove_illegal_joint`) and the numbers the kernels need — ``scale``, the scaled size ``(nh, nw)``, the canvas size
-    ``(nH, nW)``, ``M`` (the matrix handed to warpAffine) and ``Minv``, the crop origin ``(ox, oy)`` on the canvas, ``flip`` — plus
-    ``degree`` and ``center``."""
-    p = DEFAULT_PARAMS if params is None else params
+def _sample_dice(dice):
     dice = np.asarray(dice, dtype=np.float64)
     if dice.shape != (N_DICE,):
         raise MpnError("dice must hold %d draws per sample" % N_DICE)
-    crop_x, crop_y = int(crop_x), int(crop_y)
-    objpos = np.array(objpos, dtype=np.float64)
-    js = np.array(joint_self, dtype=np.float64)
-    jo = np.array(joint_others, dtype=np.float64).reshape(-1, 18, 3)
-    n_other = jo.shape[0]
-    oo = np.zeros((n_other, 2)) if objpos_other is None else np.array(objpos_other, dtype=np.float64).reshape(n_other, 2)
-    if js.shape != (18, 3) or objpos.shape != (2,):
-        raise MpnError("joint_self must be [18, 3] and objpos [2]")
+    return dice
 
-    # --- aug_scale (ImageAugmentation.py:25-52)
+
+def _scale_and_canvas(H, W, scale_provided, dice, p):
+    """What both chains do before anything is cropped: aug_scale / aug_scale_bbox (ImageAugmentation.py:25-52, :234-257) and
+    rotate_bound (:179-202).  Returns the geometry dict with ``scale``, the scaled size ``(nh, nw)``, ``degree``, the matrix ``M``
+    handed to warpAffine with ``Minv``, and the canvas size ``(nH, nW)``."""
     if dice[0] > p["scale_prob"]:
         scale_multiplier = 1
     else:
@@ -180,13 +168,6 @@ def augment_meta(H, W, scale_provided, objpos, joint_self, joint_others, dice, c
     nh, nw = int(round(H * scale)), int(round(W * scale))            # cv2.resize with fx, fy: dsize = round(size * f)
     if nh < 1 or nw < 1:
         raise MpnError("the scaled image is empty")
-    objpos *= scale
-    js[:, :2] *= scale
-    if n_other != 0:
-        oo *= scale
-        jo[:, :, :2] *= scale
-
-    # --- aug_rotate (:205-231) with rotate_bound (:179-202)
     degree = (float(dice[2]) - 0.5) * 2 * p["max_rotate_degree"]
     cX, cY = nw // 2, nh // 2
     M = rotation_matrix((cX, cY), -degree, 1.0)
@@ -195,6 +176,57 @@ def augment_meta(H, W, scale_provided, objpos, joint_self, joint_others, dice, c
     nH = int((nh * cos) + (nw * sin))
     M[0, 2] += (nW / 2) - cX
     M[1, 2] += (nH / 2) - cY
+    return {"scale": float(scale), "nh": nh, "nw": nw, "nH": nH, "nW": nW, "M": M, "Minv": invert_affine(M), "degree": degree}
+
+
+def _crop_origin(point, dice, crop_x, crop_y, nW, nH, extra, p):
+    """aug_croppad / aug_croppad_bbox (:55-118, :260-304): the crop centred on ``point`` moved by the perturbation draws.  The slices
+    [center + int(crop / 2), ... + crop + extra) of the canvas padded by crop on every side must lie inside it: a negative start
+    would wrap, an end past the padded size would truncate the crop.  ``extra`` is 1 where a mask is sliced (one longer than the
+    image), else 0.  Returns ``center`` and the canvas pixel ``(ox, oy)`` of crop pixel (0, 0)."""
+    x_offset = int((float(dice[3]) - 0.5) * 2 * p["center_perterb_max"])
+    y_offset = int((float(dice[4]) - 0.5) * 2 * p["center_perterb_max"])
+    center = point + np.array([x_offset, y_offset])
+    if not np.all(np.isfinite(center)):
+        raise MpnError("objpos is not finite")
+    center = center.astype(int)
+    x0, y0 = int(center[0]) + int(crop_x / 2), int(center[1]) + int(crop_y / 2)
+    if x0 < 0 or y0 < 0 or x0 + crop_x + extra > nW + 2 * crop_x or y0 + crop_y + extra > nH + 2 * crop_y:
+        raise MpnError("crop centre (%d, %d) is too far outside the %d x %d canvas: the reference's slices would wrap or truncate"
+                       % (center[0], center[1], nW, nH))
+    return {"center": (int(center[0]), int(center[1])), "ox": x0 - crop_x, "oy": y0 - crop_y}
+
+
+def augment_meta(H, W, scale_provided, objpos, joint_self, joint_others, dice, crop_x, crop_y, params=None, objpos_other=None,
+                 with_mask=True):
+    """The meta-data side of aug_scale -> aug_rotate -> aug_croppad -> aug_flip for one sample, op for op.
+
+    joint_self [18, 3] / joint_others [n, 18, 3] (after :func:`add_neck`), objpos [2] in source pixels; ``dice`` as laid out by
+    :func:`draw_dice`.  Returns a dict: the transformed ``joint_self`` / ``joint_others`` / ``objpos`` / ``objpos_other`` (before
+    :func:`remove_illegal_joint`) and the numbers the kernels need — ``scale``, the scaled size ``(nh, nw)``, the canvas size
+    ``(nH, nW)``, ``M`` (the matrix handed to warpAffine) and ``Minv``, the crop origin ``(ox, oy)`` on the canvas, ``flip`` — plus
+    ``degree`` and ``center``."""
+    p = DEFAULT_PARAMS if params is None else params
+    dice = _sample_dice(dice)
+    crop_x, crop_y = int(crop_x), int(crop_y)
+    objpos = np.array(objpos, dtype=np.float64)
+    js = np.array(joint_self, dtype=np.float64)
+    jo = np.array(joint_others, dtype=np.float64).reshape(-1, 18, 3)
+    n_other = jo.shape[0]
+    oo = np.zeros((n_other, 2)) if objpos_other is None else np.array(objpos_other, dtype=np.float64).reshape(n_other, 2)
+    if js.shape != (18, 3) or objpos.shape != (2,):
+        raise MpnError("joint_self must be [18, 3] and objpos [2]")
+
+    # --- aug_scale (ImageAugmentation.py:25-52)
+    geo = _scale_and_canvas(H, W, scale_provided, dice, p)
+    scale, M = geo["scale"], geo["M"]
+    objpos *= scale
+    js[:, :2] *= scale
+    if n_other != 0:
+        oo *= scale
+        jo[:, :, :2] *= scale
+
+    # --- aug_rotate (:205-231): unlike aug_rotate_bbox it moves objpos and every joint with rotate_bound's matrix
     objpos = _rotatepoint(objpos, M)
     for i in range(18):
         js[i, :] = _rotatepoint(js[i, :], M)
@@ -203,21 +235,9 @@ def augment_meta(H, W, scale_provided, objpos, joint_self, joint_others, dice, c
         for i in range(18):
             jo[j, i, :] = _rotatepoint(jo[j, i, :], M)
 
-    # --- aug_croppad (:55-118)
-    x_offset = int((float(dice[3]) - 0.5) * 2 * p["center_perterb_max"])
-    y_offset = int((float(dice[4]) - 0.5) * 2 * p["center_perterb_max"])
-    center = objpos + np.array([x_offset, y_offset])
-    if not np.all(np.isfinite(center)):
-        raise MpnError("objpos is not finite")
-    center = center.astype(int)
-    # the slices [center + int(crop / 2), ... + crop (+ 1 for the mask)) of the canvas padded by crop on every side must lie inside it:
-    # a negative start would wrap, an end past the padded size would truncate the crop
-    x0, y0 = int(center[0]) + int(crop_x / 2), int(center[1]) + int(crop_y / 2)
-    extra = 1 if with_mask else 0
-    if x0 < 0 or y0 < 0 or x0 + crop_x + extra > nW + 2 * crop_x or y0 + crop_y + extra > nH + 2 * crop_y:
-        raise MpnError("crop centre (%d, %d) is too far outside the %d x %d canvas: the reference's slices would wrap or truncate"
-                       % (center[0], center[1], nW, nH))
-    ox, oy = x0 - crop_x, y0 - crop_y                                 # canvas pixel of crop pixel (0, 0)
+    # --- aug_croppad (:55-118), centred on the ROTATED objpos; the mask slice is one longer than the image's
+    geo.update(_crop_origin(objpos, dice, crop_x, crop_y, geo["nW"], geo["nH"], 1 if with_mask else 0, p))
+    center = geo["center"]
     offset = np.array([crop_x / 2 - center[0], crop_y / 2 - center[1]])
     objpos += offset
     js[:, :2] += offset
@@ -230,8 +250,8 @@ def augment_meta(H, W, scale_provided, objpos, joint_self, joint_others, dice, c
         jo[mask, 2] = 2
 
     # --- aug_flip (:121-158); w is the IMAGE's width (the mask, one pixel wider, is flipped over its own)
-    flip = bool(dice[5] <= p["flip_prob"])
-    if flip:
+    geo["flip"] = bool(dice[5] <= p["flip_prob"])
+    if geo["flip"]:
         w = crop_x
         objpos[0] = w - 1 - objpos[0]
         js[:, 0] = w - 1 - js[:, 0]
@@ -241,9 +261,8 @@ def augment_meta(H, W, scale_provided, objpos, joint_self, joint_others, dice, c
             jo[:, :, 0] = w - 1 - jo[:, :, 0]
             for i in range(n_other):
                 jo[i] = jo[i][FLIP_ORDER]
-    return {"joint_self": js, "joint_others": jo, "objpos": objpos, "objpos_other": oo, "scale": float(scale), "nh": nh, "nw": nw,
-            "nH": nH, "nW": nW, "M": M, "Minv": invert_affine(M), "ox": ox, "oy": oy, "flip": flip, "degree": degree,
-            "center": (int(center[0]), int(center[1]))}
+    geo.update(joint_self=js, joint_others=jo, objpos=objpos, objpos_other=oo)
+    return geo
 
 
 def augment_meta_bbox(H, W, scale_provided, objpos, dice, crop_x, crop_y, params=None):
@@ -258,58 +277,18 @@ def augment_meta_bbox(H, W, scale_provided, objpos, dice, crop_x, crop_y, params
 
     Masks and image share the resize rule (``cv2.resize(fx=scale)``: dsize = round(size * scale)) and ``M``."""
     p = DEFAULT_PARAMS if params is None else params
-    dice = np.asarray(dice, dtype=np.float64)
-    if dice.shape != (N_DICE,):
-        raise MpnError("dice must hold %d draws per sample" % N_DICE)
-    crop_x, crop_y = int(crop_x), int(crop_y)
+    dice = _sample_dice(dice)
     objpos = np.array(objpos, dtype=np.float64)
     if objpos.shape != (2,):
         raise MpnError("objpos must be [2]")
-
-    # --- aug_scale_bbox (:234-257)
-    if dice[0] > p["scale_prob"]:
-        scale_multiplier = 1
-    else:
-        if np.isnan(dice[1]):
-            raise MpnError("dice[1] (aug_scale_bbox's dice2) is needed when dice[0] <= scale_prob")
-        scale_multiplier = (p["scale_max"] - p["scale_min"]) * float(dice[1]) + p["scale_min"]
-    scale_abs = p["target_dist"] / scale_provided
-    scale = scale_abs * scale_multiplier
-    if not (scale > 0 and math.isfinite(scale)):
-        raise MpnError("scale_provided gives a non-positive or non-finite scale")
-    nh, nw = int(round(H * scale)), int(round(W * scale))
-    if nh < 1 or nw < 1:
-        raise MpnError("the scaled image is empty")
-    objpos *= scale
-
-    # --- aug_rotate_bbox (:325-340) with rotate_bound (:179-202); the matrix goes to warpAffine only
-    degree = (float(dice[2]) - 0.5) * 2 * p["max_rotate_degree"]
-    cX, cY = nw // 2, nh // 2
-    M = rotation_matrix((cX, cY), -degree, 1.0)
-    cos, sin = np.abs(M[0, 0]), np.abs(M[0, 1])
-    nW = int((nh * sin) + (nw * cos))
-    nH = int((nh * cos) + (nw * sin))
-    M[0, 2] += (nW / 2) - cX
-    M[1, 2] += (nH / 2) - cY
-
-    # --- aug_croppad_bbox (:260-304)
-    x_offset = int((float(dice[3]) - 0.5) * 2 * p["center_perterb_max"])
-    y_offset = int((float(dice[4]) - 0.5) * 2 * p["center_perterb_max"])
-    center = objpos + np.array([x_offset, y_offset])
-    if not np.all(np.isfinite(center)):
-        raise MpnError("objpos is not finite")
-    center = center.astype(int)
-    # the mask slices [center + int(crop / 2), ... + crop + 1) of the canvas padded by crop on every side must lie inside it
-    x0, y0 = int(center[0]) + int(crop_x / 2), int(center[1]) + int(crop_y / 2)
-    if x0 < 0 or y0 < 0 or x0 + crop_x + 1 > nW + 2 * crop_x or y0 + crop_y + 1 > nH + 2 * crop_y:
-        raise MpnError("crop centre (%d, %d) is too far outside the %d x %d canvas: the reference's slices would wrap or truncate"
-                       % (center[0], center[1], nW, nH))
-    ox, oy = x0 - crop_x, y0 - crop_y
-
-    # --- aug_flip_bbox (:307-322)
-    flip = bool(dice[5] <= p["flip_prob"])
-    return {"objpos": objpos, "scale": float(scale), "nh": nh, "nw": nw, "nH": nH, "nW": nW, "M": M, "Minv": invert_affine(M),
-            "ox": ox, "oy": oy, "flip": flip, "degree": degree, "center": (int(center[0]), int(center[1]))}
+    # aug_scale_bbox (:234-257); aug_rotate_bbox (:325-340) hands rotate_bound's matrix to warpAffine only
+    geo = _scale_and_canvas(H, W, scale_provided, dice, p)
+    objpos *= geo["scale"]
+    # aug_croppad_bbox (:260-304), centred on the UNROTATED objpos; always the mask's slice
+    geo.update(_crop_origin(objpos, dice, int(crop_x), int(crop_y), geo["nW"], geo["nH"], 1, p))
+    # aug_flip_bbox (:307-322)
+    geo.update(objpos=objpos, flip=bool(dice[5] <= p["flip_prob"]))
+    return geo
 
 
 def table_row(geo, H, W, img_off, img_pitch, mask_off=0, mask_pitch=0):
@@ -324,6 +303,51 @@ def table_row(geo, H, W, img_off, img_pitch, mask_off=0, mask_pitch=0):
 
 def _pinned(n, dtype):
     return torch.empty(n, dtype=dtype, pin_memory=True)
+
+
+def _aligned_offsets(sizes):
+    """Byte offsets of consecutive blocks of ``sizes`` bytes, every block starting on a 16-byte boundary -> (offsets, total)."""
+    offsets, n = [], 0
+    for s in sizes:
+        offsets.append(n)
+        n += (s + 15) // 16 * 16
+    return offsets, n
+
+
+def _pack_pinned(tensors):
+    """The contiguous uint8 tensors of a batch, flat, in ONE pinned staging buffer (so one H2D copy) -> (buffer, offsets)."""
+    offsets, n = _aligned_offsets([t.numel() for t in tensors])
+    stage = _pinned(n, torch.uint8)
+    for t, o in zip(tensors, offsets):
+        stage[o: o + t.numel()] = t.view(-1)
+    return stage, offsets
+
+
+def _check_u8(t, what, dims):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.is_cuda or t.dim() != dims or not t.is_contiguous():
+        raise MpnError("%s must be a contiguous uint8 CPU tensor with %d dimensions" % (what, dims))
+
+
+def _batch_front(samples, dice, rng, params):
+    """What both augmenters check before any geometry: the batch is not empty, the dice are [B, 6] (drawn from ``rng`` through
+    :func:`draw_dice` when not given), every ``img`` is a uint8 [H, W, 3] CPU tensor.  Returns (dice, [(H, W)])."""
+    B = len(samples)
+    if B == 0:
+        raise MpnError("empty batch")
+    if dice is None:
+        rng = random if rng is None else rng
+        dice = np.stack([draw_dice(rng, params) for _ in range(B)])
+    dice = np.asarray(dice, dtype=np.float64)
+    if dice.shape != (B, N_DICE):
+        raise MpnError("dice must be [B, %d]" % N_DICE)
+    sizes = []
+    for s in samples:
+        img = s["img"]
+        _check_u8(img, "img", 3)
+        if img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+            raise MpnError("img must be [H, W, 3]")
+        sizes.append((int(img.shape[0]), int(img.shape[1])))
+    return dice, sizes
 
 
 def augment_image(src, table, crop_y, crop_x):
@@ -402,7 +426,7 @@ def boxes_from_rects(rects, metas, S, row_multiple, dev, sample_rows=None):
     N = max(len(r) for r in rects)
     N = (N + row_multiple - 1) // row_multiple * row_multiple
     n_inst = sum(len(r) for r in rects)
-    nbytes = sum((r[3] * r[4] + 15) // 16 * 16 for rs in rects for r in rs)
+    offsets, nbytes = _aligned_offsets([r[3] * r[4] for rs in rects for r in rs])
     stage = _pinned(max(nbytes, 16), torch.uint8)
     t0 = 0 if sample_rows is None else B * T_COLS
     t1 = t0 + n_inst * TB_COLS
@@ -412,16 +436,16 @@ def boxes_from_rects(rects, metas, S, row_multiple, dev, sample_rows=None):
     table = tab[t0:t1].view(n_inst, TB_COLS)
     rowmap = tab[t1:].view(torch.int32)[:B * N].view(B, N)
     rowmap.fill_(-1)
-    off, i = 0, 0
+    i = 0
     for b, (rs, g) in enumerate(zip(rects, metas)):
         for r, (m, rx0, ry0, rw, rh) in enumerate(rs):
+            off = offsets[i]
             stage[off: off + rw * rh].view(rh, rw).copy_(torch.from_numpy(m[ry0:ry0 + rh, rx0:rx0 + rw]))
             row = np.zeros(TB_COLS, dtype=np.float64)
             row[:T_COLS] = table_row(g, g["H"], g["W"], 0, 0, off, rw)
             row[TB_RX0:TB_COLS] = (rx0, ry0, rw, rh)
             table[i] = torch.from_numpy(row)
             rowmap[b, r] = i
-            off += (rw * rh + 15) // 16 * 16
             i += 1
     d_tab = tab.to(dev, non_blocking=True)
     d_samples = d_tab[:t0].view(B, T_COLS) if t0 else None
@@ -431,7 +455,24 @@ def boxes_from_rects(rects, metas, S, row_multiple, dev, sample_rows=None):
     return augment_boxes(d_src, d_table, d_rowmap, B, N, S, S), d_samples
 
 
-class DeviceAugmenter(object):
+class _Augmenter(object):
+    """What the two augmenters share: the sizes, the merged parameters and the device they run on."""
+
+    def __init__(self, inp_size, feat_stride, params=None):
+        self.inp_size, self.stride = int(inp_size), int(feat_stride)
+        if self.inp_size <= 0 or self.stride <= 0 or int(self.inp_size / self.stride) <= 0:
+            raise MpnError("inp_size and feat_stride must be positive, inp_size >= feat_stride")
+        self.params = dict(DEFAULT_PARAMS)
+        if params:
+            self.params.update(params)
+
+    def _device(self):
+        if not torch.cuda.is_available():
+            raise MpnError("%s runs on the MI355X only; there is no CPU path" % type(self).__name__)
+        return torch.device("cuda", torch.cuda.current_device())
+
+
+class DeviceAugmenter(_Augmenter):
     """``DeviceAugmenter(inp_size, feat_stride)(samples)`` -> ``(img, heatmaps, heat_mask, meta)``: the reference's training triple
     for ``keypoint_subnet`` (float32, contiguous, on the current device) plus the host-side geometry of every sample.
 
@@ -447,46 +488,19 @@ class DeviceAugmenter(object):
     :func:`augment_meta_bbox` and :class:`DeviceBBoxAugmenter`.)  ``dice`` [B, 6] makes the draws explicit; otherwise they come from ``rng``
     (a ``random.Random``; default the ``random`` module, as in the reference) through :func:`draw_dice`."""
 
-    def __init__(self, inp_size, feat_stride, params=None):
-        self.inp_size, self.stride = int(inp_size), int(feat_stride)
-        if self.inp_size <= 0 or self.stride <= 0 or int(self.inp_size / self.stride) <= 0:
-            raise MpnError("inp_size and feat_stride must be positive, inp_size >= feat_stride")
-        self.params = dict(DEFAULT_PARAMS)
-        if params:
-            self.params.update(params)
-        self.grid = int(self.inp_size / self.stride)                  # COCO_data_pipeline.py:206-207
-
-    @staticmethod
-    def _check_u8(t, what, dims):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.is_cuda or t.dim() != dims or not t.is_contiguous():
-            raise MpnError("%s must be a contiguous uint8 CPU tensor with %d dimensions" % (what, dims))
-
     def geometry(self, samples, dice=None, rng=None, mask_frame=False):
         """Part 1 for a batch: list of per-sample dicts of :func:`augment_meta` with the final (``remove_illegal_joint``) joints
         under ``joint_self_out`` / ``joint_others_out``.  Needs no GPU.  ``mask_frame`` asks for the ``crop + 1`` slice test of
         the masks even when the batch carries no ``mask_miss`` (instance masks take the same slices)."""
-        B = len(samples)
-        if B == 0:
-            raise MpnError("empty batch")
         with_mask = [s.get("mask_miss") is not None for s in samples]
-        if any(with_mask) != all(with_mask):
+        if samples and any(with_mask) != all(with_mask):               # before the dice are drawn: a refused batch leaves rng alone
             raise MpnError("either every sample of a batch has a mask_miss or none has")
+        dice, sizes = _batch_front(samples, dice, rng, self.params)
         frame = with_mask[0] or mask_frame
-        if dice is None:
-            rng = random if rng is None else rng
-            dice = np.stack([draw_dice(rng, self.params) for _ in range(B)])
-        dice = np.asarray(dice, dtype=np.float64)
-        if dice.shape != (B, N_DICE):
-            raise MpnError("dice must be [B, %d]" % N_DICE)
         metas = []
-        for s, d in zip(samples, dice):
-            img = s["img"]
-            self._check_u8(img, "img", 3)
-            if img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
-                raise MpnError("img must be [H, W, 3]")
-            H, W = int(img.shape[0]), int(img.shape[1])
+        for s, d, (H, W) in zip(samples, dice, sizes):
             if s.get("mask_miss") is not None:
-                self._check_u8(s["mask_miss"], "mask_miss", 2)
+                _check_u8(s["mask_miss"], "mask_miss", 2)
                 if tuple(s["mask_miss"].shape) != (H, W):
                     raise MpnError("mask_miss must have the image's [H, W]")
             js = np.asarray(s["joint_self"], dtype=np.float64)
@@ -513,32 +527,22 @@ class DeviceAugmenter(object):
         return self._run(samples, dice, rng, True)
 
     def _run(self, samples, dice, rng, boxes):
-        if not torch.cuda.is_available():
-            raise MpnError("DeviceAugmenter runs on the MI355X only; there is no CPU path")
+        dev = self._device()
         metas = self.geometry(samples, dice, rng, mask_frame=boxes)
         rects = [instance_rects(s, g["H"], g["W"]) for s, g in zip(samples, metas)] if boxes else None
         B, S = len(samples), self.inp_size
         has_mask = samples[0].get("mask_miss") is not None
-        dev = torch.device("cuda", torch.cuda.current_device())
         # one pinned staging buffer per kind (every source starts on a 16-byte boundary), one H2D copy each
-        img_off, mask_off, ni, nm = [], [], 0, 0
-        for g in metas:
-            img_off.append(ni)
-            mask_off.append(nm)
-            ni += (g["H"] * g["W"] * 3 + 15) // 16 * 16
-            nm += (g["H"] * g["W"] + 15) // 16 * 16
-        stage_i = _pinned(ni, torch.uint8)
-        stage_m = _pinned(nm, torch.uint8) if has_mask else None
+        stage_i, img_off = _pack_pinned([s["img"] for s in samples])
+        # the table carries the masks' offsets with or without a mask buffer, as it always has
+        mask_off = _aligned_offsets([g["H"] * g["W"] for g in metas])[0]
+        stage_m = _pack_pinned([s["mask_miss"] for s in samples])[0] if has_mask else None
         table = _pinned(B * T_COLS, torch.float64).view(B, T_COLS)
         maxP = max(1 + g["joint_others_out"].shape[0] for g in metas)
         joints = _pinned(B * maxP * 18 * 3, torch.float64).view(B, maxP, 18, 3).zero_()
         num = _pinned(B, torch.int32)
         for b, (s, g) in enumerate(zip(samples, metas)):
-            H, W = g["H"], g["W"]
-            stage_i[img_off[b]: img_off[b] + H * W * 3] = s["img"].view(-1)
-            if has_mask:
-                stage_m[mask_off[b]: mask_off[b] + H * W] = s["mask_miss"].view(-1)
-            table[b] = torch.from_numpy(table_row(g, H, W, img_off[b], W * 3, mask_off[b], W))
+            table[b] = torch.from_numpy(table_row(g, g["H"], g["W"], img_off[b], g["W"] * 3, mask_off[b], g["W"]))
             n = g["joint_others_out"].shape[0]
             joints[b, 0] = torch.from_numpy(g["joint_self_out"])
             if n:
@@ -549,7 +553,8 @@ class DeviceAugmenter(object):
         img = augment_image(d_img, d_table, S, S)
         heat_mask = None
         if has_mask:
-            heat_mask = augment_mask(stage_m.to(dev, non_blocking=True), d_table, self.grid, self.grid, self.stride, S)
+            grid = int(S / self.stride)                               # COCO_data_pipeline.py:206-207
+            heat_mask = augment_mask(stage_m.to(dev, non_blocking=True), d_table, grid, grid, self.stride, S)
         heatmaps = put_gaussian_maps(joints.to(dev, non_blocking=True), num.to(dev, non_blocking=True), S, S, self.stride,
                                      self.params["sigma"])
         # the pinned staging buffers may go out of scope here: torch's caching host allocator records the stream of a non_blocking
@@ -559,7 +564,7 @@ class DeviceAugmenter(object):
         return img, heatmaps, heat_mask, metas
 
 
-class DeviceBBoxAugmenter(object):
+class DeviceBBoxAugmenter(_Augmenter):
     """``DeviceBBoxAugmenter(inp_size, feat_stride)(samples)`` -> ``(img, bbox, metas)``: the reference's training pair for
     ``detection_subnet`` (``Cocobbox.__getitem__`` + ``bbox_collater``, COCO_data_pipeline.py:407-458) plus the host geometry.
 
@@ -574,32 +579,17 @@ class DeviceBBoxAugmenter(object):
     shape, ``[B, 0, 5]`` when no image has a row; 8: nothing left to pad for ReplayedTrainStep's ``anno_bucket``)."""
 
     def __init__(self, inp_size, feat_stride, params=None, row_multiple=1):
-        self.inp_size, self.stride, self.row_multiple = int(inp_size), int(feat_stride), int(row_multiple)
-        if self.inp_size <= 0 or self.stride <= 0 or int(self.inp_size / self.stride) <= 0 or self.row_multiple <= 0:
+        super(DeviceBBoxAugmenter, self).__init__(inp_size, feat_stride, params)
+        self.row_multiple = int(row_multiple)
+        if self.row_multiple <= 0:
             raise MpnError("inp_size, feat_stride and row_multiple must be positive, inp_size >= feat_stride")
-        self.params = dict(DEFAULT_PARAMS)
-        if params:
-            self.params.update(params)
 
     def geometry(self, samples, dice=None, rng=None):
         """List of per-sample dicts of :func:`augment_meta_bbox` plus ``H``, ``W``, ``dice`` and ``rects`` (the instances that get a
         row, from :func:`instance_rects`).  Needs no GPU."""
-        B = len(samples)
-        if B == 0:
-            raise MpnError("empty batch")
-        if dice is None:
-            rng = random if rng is None else rng
-            dice = np.stack([draw_dice(rng, self.params) for _ in range(B)])
-        dice = np.asarray(dice, dtype=np.float64)
-        if dice.shape != (B, N_DICE):
-            raise MpnError("dice must be [B, %d]" % N_DICE)
+        dice, sizes = _batch_front(samples, dice, rng, self.params)
         metas = []
-        for s, d in zip(samples, dice):
-            img = s["img"]
-            DeviceAugmenter._check_u8(img, "img", 3)
-            if img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
-                raise MpnError("img must be [H, W, 3]")
-            H, W = int(img.shape[0]), int(img.shape[1])
+        for s, d, (H, W) in zip(samples, dice, sizes):
             geo = augment_meta_bbox(H, W, s["scale_provided"], s["objpos"], d, self.inp_size, self.inp_size, self.params)
             geo["dice"], geo["H"], geo["W"] = d.copy(), H, W
             geo["rects"] = instance_rects(s, H, W)
@@ -607,22 +597,11 @@ class DeviceBBoxAugmenter(object):
         return metas
 
     def __call__(self, samples, dice=None, rng=None):
-        if not torch.cuda.is_available():
-            raise MpnError("DeviceBBoxAugmenter runs on the MI355X only; there is no CPU path")
+        dev = self._device()
         metas = self.geometry(samples, dice, rng)
-        B, S = len(samples), self.inp_size
-        dev = torch.device("cuda", torch.cuda.current_device())
-        img_off, ni = [], 0
-        for g in metas:
-            img_off.append(ni)
-            ni += (g["H"] * g["W"] * 3 + 15) // 16 * 16
-        stage_i = _pinned(ni, torch.uint8)
-        rows = np.zeros((B, T_COLS), dtype=np.float64)
-        for b, (s, g) in enumerate(zip(samples, metas)):
-            H, W = g["H"], g["W"]
-            stage_i[img_off[b]: img_off[b] + H * W * 3] = s["img"].view(-1)
-            rows[b] = table_row(g, H, W, img_off[b], W * 3)
+        stage_i, img_off = _pack_pinned([s["img"] for s in samples])
+        rows = np.stack([table_row(g, g["H"], g["W"], off, g["W"] * 3) for g, off in zip(metas, img_off)])
         # three H2D copies in all: the images, the mask rectangles, the tables
-        bbox, d_table = boxes_from_rects([g["rects"] for g in metas], metas, S, self.row_multiple, dev, rows)
-        img = augment_image(stage_i.to(dev, non_blocking=True), d_table, S, S)
+        bbox, d_table = boxes_from_rects([g["rects"] for g in metas], metas, self.inp_size, self.row_multiple, dev, rows)
+        img = augment_image(stage_i.to(dev, non_blocking=True), d_table, self.inp_size, self.inp_size)
         return img, bbox, metas

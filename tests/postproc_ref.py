@@ -108,7 +108,7 @@ def _neg(a):
 
 
 def coeff_model(t, A=A_CUBIC):
-    """cubic_coeffs (csrc/peaks.hip) in float64 with the running float32 rounding error of every operation.
+    """cubic_coeffs (csrc/common.h) in float64 with the running float32 rounding error of every operation.
     t: float64 array in [0, 1].  Returns (c [4, n], err [3, n] of c0, c1, c2, rho [n]: the roundings of forming c3 = 1 - c0 - c1 - c2)."""
     t = np.asarray(t, dtype=f64)
     zero = np.zeros_like(t)

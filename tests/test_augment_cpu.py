@@ -134,6 +134,50 @@ def test_crop_centre_far_outside_the_canvas_raises():
         aug.augment_meta(objpos=(float("nan"), 1.0), **args)
 
 
+def test_slice_test_is_one_rule_for_both_chains():
+    """The boundary list of test_augment_meta_bbox_refuses_slices_that_would_wrap_or_truncate through BOTH chains.  H = W = 100 at
+    scale 1, 0 degrees (dice 0.5: the keypoint chain's rotation leaves objpos where it is), crop 64: x0 = cx + 32 and the canvas
+    padded by the crop is 100 + 128 = 228 wide.  The mask slice [x0, x0 + 65) fits up to cx = 131; the image slice [x0, x0 + 64) is
+    one shorter and fits up to cx = 132."""
+    from multiposenet.pytorch_amd._lib import MpnError
+    d = np.array([0.7, np.nan, 0.5, 0.5, 0.5, 0.9])
+    p = dict(aug.DEFAULT_PARAMS, scale_prob=0.0)
+    js = np.ones((18, 3))
+
+    def bbox(pos):
+        aug.augment_meta_bbox(100, 100, 0.6, pos, d, 64, 64, p)
+
+    def keypoint(pos, with_mask=True):
+        aug.augment_meta(100, 100, 0.6, pos, js, np.zeros((0, 18, 3)), d, 64, 64, p, with_mask=with_mask)
+
+    def raises(f, *a):
+        try:
+            f(*a)
+        except MpnError:
+            return True
+        return False
+
+    cases = [((50.0, 50.0), False), ((131.0, 50.0), False), ((50.0, 131.0), False), ((-32.0, -32.0), False),
+             ((132.0, 50.0), True), ((50.0, 132.0), True), ((-33.0, 50.0), True), ((50.0, -33.0), True), ((float("nan"), 1.0), True)]
+    for pos, bad in cases:
+        assert raises(bbox, pos) == bad, pos
+        assert raises(keypoint, pos) == bad, pos
+    for pos in ((132.0, 50.0), (50.0, 132.0)):
+        assert not raises(keypoint, pos, False), pos
+    for pos in ((133.0, 50.0), (50.0, 133.0), (-33.0, 50.0)):
+        assert raises(keypoint, pos, False), pos
+
+
+def test_aligned_offsets_start_every_block_on_16_bytes_without_overlap():
+    for sizes in ([1, 16, 17, 0, 48], [], [0], [15, 1, 921600]):
+        offsets, total = aug._aligned_offsets(sizes)
+        assert len(offsets) == len(sizes) and all(o % 16 == 0 for o in offsets)
+        ends = [o + s for o, s in zip(offsets, sizes)]
+        assert all(e <= nxt for e, nxt in zip(ends, offsets[1:] + [total]))            # ranges in order, none overlapping
+        assert total == sum((s + 15) // 16 * 16 for s in sizes)
+    assert aug._aligned_offsets([1, 16, 17, 0, 48]) == ([0, 16, 32, 64, 64], 112)
+
+
 # ---------------------------------------------------------------------------------------------------------------- C ABI
 NEW = ("mpn_augment_image", "mpn_augment_mask")
 

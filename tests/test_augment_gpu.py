@@ -90,6 +90,48 @@ def test_image_and_mask_kernels_vs_float64_restatement(i):
     assert gm.min() >= 0.0 and gm.max() <= 1.0
 
 
+def test_ragged_blocks_of_the_image_and_mask_kernels_in_a_batch_of_two():
+    """The kernels called directly at output shapes that end inside a block: an image of 5 x 65 (one full wave plus one lane, a
+    4-row block plus one row) and a mask grid of 3 x 87 = 261 cells (one full 256-lane workgroup plus five lanes), two samples per
+    launch so blockIdx.z selects the table row and the source.  Geometry of one unflipped and one flipped golden case from the
+    recorded values, the crop origin moved so that the small window lies in the middle of the recorded crop.  Same bound as above."""
+    from multiposenet.pytorch_amd.datasets import augment as aug
+    pair = [next(i for i, c in enumerate(CASES) if int(c["flip"]) == f) for f in (0, 1)]
+    CY, CX, GH, GW = 5, 65, 3, 87
+    srcs = [ar.synth_sources(40 + i, int(CASES[i]["hw"][0]), int(CASES[i]["hw"][1])) for i in pair]
+    ioff, moff = ([0, (srcs[0][k].size + 15) // 16 * 16] for k in (0, 1))       # every source on a 16-byte boundary
+    buf_i, buf_m = (np.zeros(off[1] + srcs[1][k].size, dtype=np.uint8) for k, off in ((0, ioff), (1, moff)))
+    geos = {"image": [], "mask": []}
+    rows = {"image": [], "mask": []}
+    for b, i in enumerate(pair):
+        c, (H, W) = CASES[i], srcs[b][0].shape[:2]
+        buf_i[ioff[b]: ioff[b] + srcs[b][0].size] = srcs[b][0].reshape(-1)
+        buf_m[moff[b]: moff[b] + srcs[b][1].size] = srcs[b][1].reshape(-1)
+        ox, oy = int(c["center"][0]) + INP // 2 - INP, int(c["center"][1]) + INP // 2 - INP
+        for kind, o in (("image", (ox + (INP - CX) // 2, oy + (INP - CY) // 2)),
+                        ("mask", (ox + (INP - GW * STRIDE) // 2, oy + (INP - GH * STRIDE) // 2))):
+            g = ar.geometry(c["M"], c["scale"], c["stage_shapes"][0][:2], c["stage_shapes"][1][:2], o, int(c["flip"]))
+            geos[kind].append(g)
+            rows[kind].append(aug.table_row(g, H, W, ioff[b], W * 3, moff[b], W))
+    img = aug.augment_image(torch.from_numpy(buf_i).cuda(), torch.from_numpy(np.stack(rows["image"])).cuda(), CY, CX)
+    hm = aug.augment_mask(torch.from_numpy(buf_m).cuda(), torch.from_numpy(np.stack(rows["mask"])).cuda(), GH, GW, STRIDE, GW * STRIDE)
+    torch.cuda.synchronize()
+    assert tuple(img.shape) == (2, 3, CY, CX) and tuple(hm.shape) == (2, 18, GH, GW)
+    for b in range(2):
+        ref, mag, wabs = ar.image_ref(srcs[b][0], geos["image"][b], CY, CX)
+        assert (wabs[0] > 0).mean() > 0.25                             # the window shows the source, not only pad
+        r = ar.ratio(img[b].cpu().numpy().astype(np.float64), ref, mag, wabs, ar.C_SUM_IMAGE)
+        print("ragged image sample %d: worst err/bound %.4f" % (b, r.max()))
+        assert r.max() <= 1.0, (b, np.unravel_index(int(np.argmax(r)), r.shape), r.max())
+        gm = hm[b].cpu().numpy()
+        assert all(np.array_equal(gm[k], gm[0]) for k in range(1, 18))
+        ref, mag, wabs = ar.mask_ref(srcs[b][1], geos["mask"][b], GH, GW, STRIDE, GW * STRIDE)
+        assert (wabs > 0).mean() > 0.25
+        r = ar.ratio(gm[0].astype(np.float64), ref, mag, wabs, ar.C_SUM_MASK)
+        print("ragged mask sample %d: worst err/bound %.4f" % (b, r.max()))
+        assert r.max() <= 1.0, (b, np.unravel_index(int(np.argmax(r)), r.shape), r.max())
+
+
 def test_exact_case_identity_transform_returns_the_source_pixels():
     """Even-sized source, scale 1 (scale_provided = target_dist, scale_prob 0), 0 degrees (dice 0.5), no flip, crop inside the image:
     every fraction is 0, the cubic weights are exactly (0, 1, 0, 0), so the image must EQUAL (src / 255 - mean) / std computed in
