@@ -596,6 +596,53 @@ int mpn_augment_boxes(const uint8_t* src, int64_t src_bytes, const double* table
                       float* out, int crop_y, int crop_x, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * COCO segmentations rasterised on the device (csrc/segm.hip; datasets/segm.py packs the tables): annToMask by the rule of
+ * maskApi.c (rleFrPoly on the 5x grid, union of an annotation's parts, rleDecode), byte for byte.
+ *
+ * insts: int64 [n_inst][MPN_SEGI_COLS] (device): the image's H, W; a rectangle (rx0, ry0, rw, rh) inside it that contains every
+ *   ON cell of the instance (it need not be tight); byte offset and row pitch of that rectangle's row-major uint8 output in
+ *   `out`; the instance's parts [p0, p1).
+ * parts: int64 [n_parts][MPN_SEGP_COLS] (device): the part's instance; its vertices [v0, v1) (none for an RLE, which is one
+ *   part); the offset, in 64-bit words, of its toggle bitmap in the workspace: (H / 64 + 1) * rw words, word k of rectangle column
+ *   c at [k * rw + c], slot yd of a column (0 .. H) is bit yd % 64 of word yd / 64.
+ * verts: int32 [n_verts][2], the vertices (int)(5 x + 0.5), (int)(5 y + 0.5); edge e runs from vertex e to vertex e + 1, the
+ *   last edge of a part back to v0.  vpart: int32 [n_verts], the part of each.  estart: int32 [n_verts + 1], estart[0] = 0,
+ *   estart[e + 1] - estart[e] = max(|dX|, |dY|) of edge e; n_steps = estart[n_verts].
+ * toggles: int32 [n_tog][2] = (part, flat column-major index x * H + y) of the RLE parts: the cumulative sums of the run lengths.
+ *
+ * Launches: memset of the workspace (ws_bytes >= mpn_segm_workspace_bytes(total bitmap words)) and of any_on; one lane per
+ * (edge, step) and one per listed toggle flip one bit each (atomic XOR on a word: order-independent, pairs cancel); the fill
+ * launch (grid: 64-column tiles up to max_rw, 512-row tiles up to max_h, instances) takes the prefix parity along the flat index
+ * of every part, ORs the parts and stores the rectangle; any_on int32 [n_inst] = 1 where an instance has an ON cell, else 0.
+ * dense = 1 zeroes all out_bytes of `out` first (rectangles inside [n][H][W] planes); dense = 0 writes the rectangles only.
+ * A table row that names something outside its table, its image or its buffer is skipped, never dereferenced.
+ * MPN_E_BADARG before any HIP call: null or misaligned pointer, n_inst outside 1..65535, a negative count, n_steps >= 2^31 or > 0
+ * without vertices, max_rw / max_h outside 1..65536, out_bytes outside 1..2^40, ws_bytes < 8 or no multiple of 8, dense not 0 / 1.
+ * mpn_segm_workspace_bytes: 8 * max(words, 1); 0 for words < 0 or >= 2^31.  Nothing is allocated or synchronised.
+ * -------------------------------------------------------------------------------------------*/
+#define MPN_SEGI_H 0
+#define MPN_SEGI_W 1
+#define MPN_SEGI_RX0 2
+#define MPN_SEGI_RY0 3
+#define MPN_SEGI_RW 4
+#define MPN_SEGI_RH 5
+#define MPN_SEGI_OUT_OFF 6
+#define MPN_SEGI_OUT_PITCH 7
+#define MPN_SEGI_P0 8
+#define MPN_SEGI_P1 9
+#define MPN_SEGI_COLS 10
+#define MPN_SEGP_INST 0
+#define MPN_SEGP_V0 1
+#define MPN_SEGP_V1 2
+#define MPN_SEGP_BM 3
+#define MPN_SEGP_COLS 4
+int64_t mpn_segm_workspace_bytes(int64_t words);
+int mpn_segm_rasterize(const int64_t* insts, int n_inst, const int64_t* parts, int n_parts, const int32_t* verts,
+                       const int32_t* vpart, const int32_t* estart, int n_verts, int64_t n_steps, const int32_t* toggles,
+                       int n_tog, int max_rw, int max_h, uint8_t* out, int64_t out_bytes, int dense, int32_t* any_on,
+                       void* workspace, int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * PRN training pairs from raw COCO annotations (datasets/coco_data/prn_data_pipeline.py:33-111), one launch per batch.
  * Per sample b: box[b] = the annotation's raw (x, y, w, h); own_kp[b] = its 17 (x, y, v) keypoints; the annotations of its image
  * (the own one, crowds and people with few keypoints among them), in the image's annotation order, are rows

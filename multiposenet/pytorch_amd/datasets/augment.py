@@ -31,6 +31,7 @@ import torch
 
 from .._lib import MpnError, call
 from .. import ops
+from . import segm
 from .heatmap import put_gaussian_maps
 
 # COCO_data_pipeline.py:25-42
@@ -417,17 +418,45 @@ def instance_rects(sample, H, W):
     return rects
 
 
-def boxes_from_rects(rects, metas, S, row_multiple, dev, sample_rows=None):
+def batch_kind(samples):
+    """"instances" or "segmentations": what every sample of the batch carries its objects as.  A sample with both or neither, and
+    a batch that mixes the two, raise — before any dice are drawn."""
+    kinds = set()
+    for s in samples:
+        has = [k for k in ("instances", "segmentations") if s.get(k) is not None]
+        if len(has) != 1:
+            raise MpnError("a sample carries either 'instances' or 'segmentations'")
+        kinds.add(has[0])
+    if len(kinds) > 1:
+        raise MpnError("a batch carries either 'instances' or 'segmentations', not both kinds")
+    return kinds.pop() if kinds else "instances"
+
+
+def segmentation_pack(sample, H, W, strict=True):
+    """The ``segmentations`` path's counterpart of :func:`instance_rects`: the sample's non-crowd annotations packed for
+    mpn_segm_rasterize (:func:`..segm.pack_segmentations`; O(vertices), no pixel is touched).  A crowd yields no row and is not
+    rasterised; EVERY non-crowd annotation keeps a row, in annotation order, whether or not its mask comes out empty (that is known
+    only on the device).  An empty list raises, as it does for ``instances``."""
+    sg, crowd = sample.get("segmentations"), sample.get("iscrowd")
+    if sg is None or crowd is None or len(sg) != len(crowd):
+        raise MpnError("a sample needs 'segmentations' and an 'iscrowd' entry for each of them")
+    if len(sg) == 0:
+        raise MpnError("a sample has no annotation")
+    return segm.pack_segmentations([g for g, c in zip(sg, crowd) if not int(c)], H, W, strict)
+
+
+def boxes_from_rects(rects, metas, S, row_multiple, dev, sample_rows=None, d_src=None):
     """Packs the rectangles of a batch (rects[b] from :func:`instance_rects`, metas[b] the sample's geometry with H, W) and launches
     mpn_augment_boxes.  One pinned buffer and one H2D copy for the rectangles; one pinned block of doubles and one H2D copy for the
     tables: the sample table ``sample_rows`` [B, 20] when given (returned as a device tensor), the instance table, and the int32
-    row map in the tail.  Returns (bbox [B, N, 5], device sample table or None)."""
+    row map in the tail.  With ``d_src`` the rectangles already lie on the device at these offsets (:func:`..segm.rasterize_packed`
+    wrote them; the masks of ``rects`` are None) and nothing is staged.  Returns (bbox [B, N, 5], device sample table or None)."""
     B = len(rects)
     N = max(len(r) for r in rects)
     N = (N + row_multiple - 1) // row_multiple * row_multiple
     n_inst = sum(len(r) for r in rects)
     offsets, nbytes = _aligned_offsets([r[3] * r[4] for rs in rects for r in rs])
-    stage = _pinned(max(nbytes, 16), torch.uint8)
+    stage = _pinned(max(nbytes, 16), torch.uint8) if d_src is None else None
     t0 = 0 if sample_rows is None else B * T_COLS
     t1 = t0 + n_inst * TB_COLS
     tab = _pinned(max(t1 + (B * N + 1) // 2, 1), torch.float64)
@@ -440,7 +469,8 @@ def boxes_from_rects(rects, metas, S, row_multiple, dev, sample_rows=None):
     for b, (rs, g) in enumerate(zip(rects, metas)):
         for r, (m, rx0, ry0, rw, rh) in enumerate(rs):
             off = offsets[i]
-            stage[off: off + rw * rh].view(rh, rw).copy_(torch.from_numpy(m[ry0:ry0 + rh, rx0:rx0 + rw]))
+            if stage is not None:
+                stage[off: off + rw * rh].view(rh, rw).copy_(torch.from_numpy(m[ry0:ry0 + rh, rx0:rx0 + rw]))
             row = np.zeros(TB_COLS, dtype=np.float64)
             row[:T_COLS] = table_row(g, g["H"], g["W"], 0, 0, off, rw)
             row[TB_RX0:TB_COLS] = (rx0, ry0, rw, rh)
@@ -451,12 +481,23 @@ def boxes_from_rects(rects, metas, S, row_multiple, dev, sample_rows=None):
     d_samples = d_tab[:t0].view(B, T_COLS) if t0 else None
     d_table = d_tab[t0:t1].view(n_inst, TB_COLS) if n_inst else None
     d_rowmap = d_tab[t1:].view(torch.int32)[:B * N]
-    d_src = stage.to(dev, non_blocking=True) if n_inst else None
+    if d_src is None:
+        d_src = stage.to(dev, non_blocking=True) if n_inst else None
     return augment_boxes(d_src, d_table, d_rowmap, B, N, S, S), d_samples
+
+
+def _segm_boxes(metas, S, row_multiple, dev, sample_rows=None):
+    """The ``segmentations`` path of both augmenters: the batch's packs (``metas[b]["segm"]``) rasterised into the packed rectangles
+    of :func:`boxes_from_rects` on the device, then the same box launch.  Nothing waits for the device."""
+    pack = segm.concat_packs([g["segm"] for g in metas])
+    d_src = segm.rasterize_packed(pack, dev)[0] if pack.n else None
+    return boxes_from_rects([g["rects"] for g in metas], metas, S, row_multiple, dev, sample_rows, d_src=d_src)
 
 
 class _Augmenter(object):
     """What the two augmenters share: the sizes, the merged parameters and the device they run on."""
+
+    segm_strict = True                  # a malformed polygon part raises; False drops it (segm.pack_segmentations)
 
     def __init__(self, inp_size, feat_stride, params=None):
         self.inp_size, self.stride = int(inp_size), int(feat_stride)
@@ -522,14 +563,20 @@ class DeviceAugmenter(_Augmenter):
         return self._run(samples, dice, rng, False)
 
     def call_with_boxes(self, samples, dice=None, rng=None):
-        """For ``train_both``: ``(img, heatmaps, heat_mask, bbox, metas)``.  The samples also carry ``instances`` / ``iscrowd`` as for
-        :class:`DeviceBBoxAugmenter`; the boxes are read under THIS chain's geometry (rotated ``objpos``), through the same kernel."""
+        """For ``train_both``: ``(img, heatmaps, heat_mask, bbox, metas)``.  The samples also carry ``instances`` / ``iscrowd`` — or
+        ``segmentations`` / ``iscrowd`` — as for :class:`DeviceBBoxAugmenter`; the boxes are read under THIS chain's geometry (rotated
+        ``objpos``), through the same kernel."""
         return self._run(samples, dice, rng, True)
 
     def _run(self, samples, dice, rng, boxes):
         dev = self._device()
+        kind = batch_kind(samples) if boxes else None
         metas = self.geometry(samples, dice, rng, mask_frame=boxes)
-        rects = [instance_rects(s, g["H"], g["W"]) for s, g in zip(samples, metas)] if boxes else None
+        if kind == "segmentations":
+            for s, g in zip(samples, metas):
+                g["segm"] = segmentation_pack(s, g["H"], g["W"], self.segm_strict)
+                g["rects"] = [(None,) + r for r in g["segm"].rects()]
+        rects = [instance_rects(s, g["H"], g["W"]) for s, g in zip(samples, metas)] if kind == "instances" else None
         B, S = len(samples), self.inp_size
         has_mask = samples[0].get("mask_miss") is not None
         # one pinned staging buffer per kind (every source starts on a 16-byte boundary), one H2D copy each
@@ -559,6 +606,8 @@ class DeviceAugmenter(_Augmenter):
                                      self.params["sigma"])
         # the pinned staging buffers may go out of scope here: torch's caching host allocator records the stream of a non_blocking
         # copy and hands a block out again only after that copy has finished
+        if kind == "segmentations":
+            return img, heatmaps, heat_mask, _segm_boxes(metas, S, 1, dev)[0], metas
         if boxes:
             return img, heatmaps, heat_mask, boxes_from_rects(rects, metas, S, 1, dev)[0], metas
         return img, heatmaps, heat_mask, metas
@@ -576,7 +625,21 @@ class DeviceBBoxAugmenter(_Augmenter):
     ``img`` is float32 [B, 3, S, S] from mpn_augment_image under the bbox chain's geometry (:func:`augment_meta_bbox`); ``bbox`` is
     float32 [B, N, 5] on the device, rows ``[x1, y1, x2, y2, 0]`` in the ``(S + 1)``-wide mask frame, ``-1`` rows for an instance
     warped out of the crop and for padding.  ``N`` is the batch maximum of rows rounded up to ``row_multiple`` (1: bbox_collater's
-    shape, ``[B, 0, 5]`` when no image has a row; 8: nothing left to pad for ReplayedTrainStep's ``anno_bucket``)."""
+    shape, ``[B, 0, 5]`` when no image has a row; 8: nothing left to pad for ReplayedTrainStep's ``anno_bucket``).
+
+    Instead of ``instances`` a sample may carry the raw COCO fields, ``"segmentations": [polygon parts | RLE dict per annotation]``
+    (:func:`..segm.pack_segmentations`), which are rasterised on the device (csrc/segm.hip) into the same packed rectangles; the
+    host then touches no pixel and pycocotools is not needed.  A sample with both keys or neither, and a batch that mixes the two
+    kinds, raise.  What differs on that path, because whether a mask is empty is known only on the device and nothing here waits
+    for the device:
+
+    * crowd annotations get no row and are not rasterised (as with ``instances``);
+    * EVERY non-crowd annotation keeps its row slot, in annotation order.  One whose mask comes out empty reads ``-1`` in its slot
+      (the consumers drop ``-1`` rows wherever they stand), where the ``instances`` path drops that row before numbering;
+    * a sample whose masks are all empty yields ``-1`` rows and no error;
+    * ``N`` is the batch maximum of non-crowd annotations rounded up to ``row_multiple``.
+
+    ``segm_strict = False`` (attribute) drops polygon parts with an odd length or fewer than 6 numbers instead of raising."""
 
     def __init__(self, inp_size, feat_stride, params=None, row_multiple=1):
         super(DeviceBBoxAugmenter, self).__init__(inp_size, feat_stride, params)
@@ -586,13 +649,19 @@ class DeviceBBoxAugmenter(_Augmenter):
 
     def geometry(self, samples, dice=None, rng=None):
         """List of per-sample dicts of :func:`augment_meta_bbox` plus ``H``, ``W``, ``dice`` and ``rects`` (the instances that get a
-        row, from :func:`instance_rects`).  Needs no GPU."""
+        row, from :func:`instance_rects`; on the ``segmentations`` path the conservative rectangles of :func:`segmentation_pack`,
+        masks None, with the pack itself under ``segm``).  Needs no GPU."""
+        kind = batch_kind(samples)
         dice, sizes = _batch_front(samples, dice, rng, self.params)
         metas = []
         for s, d, (H, W) in zip(samples, dice, sizes):
             geo = augment_meta_bbox(H, W, s["scale_provided"], s["objpos"], d, self.inp_size, self.inp_size, self.params)
             geo["dice"], geo["H"], geo["W"] = d.copy(), H, W
-            geo["rects"] = instance_rects(s, H, W)
+            if kind == "segmentations":
+                geo["segm"] = segmentation_pack(s, H, W, self.segm_strict)
+                geo["rects"] = [(None,) + r for r in geo["segm"].rects()]
+            else:
+                geo["rects"] = instance_rects(s, H, W)
             metas.append(geo)
         return metas
 
@@ -602,6 +671,9 @@ class DeviceBBoxAugmenter(_Augmenter):
         stage_i, img_off = _pack_pinned([s["img"] for s in samples])
         rows = np.stack([table_row(g, g["H"], g["W"], off, g["W"] * 3) for g, off in zip(metas, img_off)])
         # three H2D copies in all: the images, the mask rectangles, the tables
-        bbox, d_table = boxes_from_rects([g["rects"] for g in metas], metas, self.inp_size, self.row_multiple, dev, rows)
+        if "segm" in metas[0]:
+            bbox, d_table = _segm_boxes(metas, self.inp_size, self.row_multiple, dev, rows)
+        else:
+            bbox, d_table = boxes_from_rects([g["rects"] for g in metas], metas, self.inp_size, self.row_multiple, dev, rows)
         img = augment_image(stage_i.to(dev, non_blocking=True), d_table, self.inp_size, self.inp_size)
         return img, bbox, metas
