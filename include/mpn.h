@@ -642,6 +642,38 @@ int mpn_segm_rasterize(const int64_t* insts, int n_inst, const int64_t* parts, i
                        int n_tog, int max_rw, int max_h, uint8_t* out, int64_t out_bytes, int dense, int32_t* any_on,
                        void* workspace, int64_t ws_bytes, void* stream);
 
+/* mask_miss of n_img images from their person annotations (what the reference reads as the mask_miss PNGs under mask2014,
+ * datasets/coco_data/COCO_data_pipeline.py:244-250), composed on the device without any instance mask in memory.
+ *
+ * insts, parts, verts, vpart, estart, toggles, workspace: as for mpn_segm_rasterize (its toggle launches run unchanged); the OUT
+ *   columns of insts are not used.  n_inst may be 0 (no image has an annotation to rasterise): insts, kind, parts may then be null.
+ * kind: int32 [n_inst], MPN_SEGK_KEYPOINTS / _NO_KEYPOINTS / _CROWD.
+ * imgs: int64 [n_img][MPN_SEGM_COLS] (device): the image's H, W; its instances [i0, i1) in annotation order (each with this H, W);
+ *   byte offset and row pitch of its H x W uint8 plane in `out`.
+ * Rule, with M the annToMask of an instance, walking an image's instances in order from all = miss = 0:
+ *   KEYPOINTS: all |= M;   NO_KEYPOINTS: all |= M, miss |= M;   CROWD: miss |= M & ~all (all as accumulated so far);
+ *   plane = 255 where miss == 0, else 0.  An image without instances is all 255.
+ * Launches: the workspace memset and the toggle launches, then one compose launch (grid: 64-column tiles up to max_w, 512-row
+ * tiles up to max_h, images).  No atomics in the compose launch; every byte of every plane is written, nothing between planes.
+ * A table row that names something outside its table, its image or its buffer is skipped, never dereferenced.
+ * MPN_E_BADARG before any HIP call: null or misaligned pointer, n_img outside 1..65535, n_inst outside 0..65535, a negative count,
+ * n_steps >= 2^31 or > 0 without vertices, max_w / max_h outside 1..65536, out_bytes outside 1..2^40, ws_bytes < 8 or no multiple
+ * of 8.  Nothing is allocated or synchronised.                                                                                  */
+#define MPN_SEGK_KEYPOINTS 0
+#define MPN_SEGK_NO_KEYPOINTS 1
+#define MPN_SEGK_CROWD 2
+#define MPN_SEGM_H 0
+#define MPN_SEGM_W 1
+#define MPN_SEGM_I0 2
+#define MPN_SEGM_I1 3
+#define MPN_SEGM_OUT_OFF 4
+#define MPN_SEGM_OUT_PITCH 5
+#define MPN_SEGM_COLS 6
+int mpn_segm_mask_miss(const int64_t* imgs, int n_img, const int64_t* insts, const int32_t* kind, int n_inst, const int64_t* parts,
+                       int n_parts, const int32_t* verts, const int32_t* vpart, const int32_t* estart, int n_verts, int64_t n_steps,
+                       const int32_t* toggles, int n_tog, int max_w, int max_h, uint8_t* out, int64_t out_bytes, void* workspace,
+                       int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * PRN training pairs from raw COCO annotations (datasets/coco_data/prn_data_pipeline.py:33-111), one launch per batch.
  * Per sample b: box[b] = the annotation's raw (x, y, w, h); own_kp[b] = its 17 (x, y, v) keypoints; the annotations of its image

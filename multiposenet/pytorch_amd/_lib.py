@@ -77,6 +77,7 @@ SIGNATURES = {
     "mpn_augment_boxes": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "mpn_segm_workspace_bytes": (_i64, [_i64]),
     "mpn_segm_rasterize": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _i64, _i, _vp, _vp, _i64, _vp]),
+    "mpn_segm_mask_miss": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _i64, _vp, _i64, _vp]),
     "mpn_prn_train_maps": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpn_heatmap_peaks_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "mpn_heatmap_peaks": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _f, ctypes.c_double, _i, _vp, _vp, _i, _vp, _vp]),

@@ -19,6 +19,10 @@
 // column the parity of everything before the tile's first row (earlier columns, then earlier words of the column) is a popcount
 // fold; inside a word the prefix parity is six shift-XORs.  Parts are ORed in registers, the four waves' words meet in LDS (the
 // column-major to row-major turn), and the stores run along rows: 64 consecutive bytes per wave.  Ordinary stores only.
+//
+// mpn_segm_mask_miss shares the toggle launches and the per-part words (or_part_words) and replaces the fill launch by a compose
+// launch per IMAGE tile: the image's person annotations are walked in order and combined by kind into mask_miss, without any
+// instance mask in memory (segm_mask_miss_kernel).
 #include "common.h"
 
 namespace {
@@ -33,7 +37,8 @@ struct SegInst {
 };
 
 // Instance row -> registers.  `ok` guards every use: a row whose rectangle leaves the image, whose parts leave the part table or
-// whose output leaves the buffer is skipped, never dereferenced (the host wrapper never produces one).
+// whose output leaves the buffer is skipped, never dereferenced (the host wrapper never produces one).  out_bytes < 0: the OUT
+// columns are not used by this launch (mask_miss writes whole image planes) and are not looked at.
 __device__ __forceinline__ SegInst load_inst(const int64_t* __restrict__ row, int n_parts, long out_bytes) {
     SegInst s;
     const int64_t h = row[MPN_SEGI_H], w = row[MPN_SEGI_W], x0 = row[MPN_SEGI_RX0], y0 = row[MPN_SEGI_RY0], rw = row[MPN_SEGI_RW],
@@ -42,7 +47,8 @@ __device__ __forceinline__ SegInst load_inst(const int64_t* __restrict__ row, in
     s.pitch = row[MPN_SEGI_OUT_PITCH];
     s.ok = h >= 1 && h <= 65536 && w >= 1 && w <= 65536 && h * w <= 0x7fffffffL && x0 >= 0 && y0 >= 0 && rw >= 1 && rh >= 1 &&
            x0 <= w - rw && y0 <= h - rh && p0 >= 0 && p0 <= p1 && p1 <= n_parts;
-    s.ok = s.ok && s.off >= 0 && s.pitch >= rw && s.off <= out_bytes && s.pitch <= out_bytes && (rh - 1) * s.pitch + rw <= out_bytes - s.off;
+    if (out_bytes >= 0)
+        s.ok = s.ok && s.off >= 0 && s.pitch >= rw && s.off <= out_bytes && s.pitch <= out_bytes && (rh - 1) * s.pitch + rw <= out_bytes - s.off;
     s.h = s.ok ? (int)h : 1; s.w = s.ok ? (int)w : 1;
     s.rx0 = s.ok ? (int)x0 : 0; s.ry0 = s.ok ? (int)y0 : 0; s.rw = s.ok ? (int)rw : 1; s.rh = s.ok ? (int)rh : 1;
     s.p0 = s.ok ? (int)p0 : 0; s.p1 = s.ok ? (int)p1 : 0;
@@ -144,6 +150,52 @@ __global__ void __launch_bounds__(256) segm_toggle_rle_kernel(const int32_t* __r
 
 __device__ __forceinline__ unsigned long long wave_parity(unsigned long long bit) { return __popcll(__ballot((bit & 1) != 0)) & 1; }
 
+// The words k0 .. k0 + NW - 1 (64 rows each) of ONE part at rectangle column c, ORed into acc: bit b of word k = the cell is ON.
+// bm: the part's bitmap (rw columns, cw words each).  c0: the rectangle column of the wave's lane 0 (c = c0 + lane; it may be
+// negative, and lanes with cin false lie outside the rectangle and get nothing).  Per column the parity of everything before
+// word k0 (earlier columns, then earlier words of the column) is a popcount fold; inside a word the prefix parity is six
+// shift-XORs.  Every lane of the wave must call this together (ballots).
+template <int NW>
+__device__ __forceinline__ void or_part_words(const unsigned long long* __restrict__ bm, int rw, int cw, int c0, int c, bool cin, int k0,
+                                              int lane, unsigned long long (&acc)[NW]) {
+    // parity of every toggle in the columns before this tile (an RLE run may span columns; a closed outline leaves none)
+    unsigned long long base = 0;
+    for (int cc = lane; cc < c0; cc += 64)
+        for (int k = 0; k < cw; ++k) base ^= (unsigned long long)__popcll(bm[(long)k * rw + cc]);
+    base = wave_parity(base);
+    // this column: all of it (for the columns to its right) and what lies above the tile
+    unsigned long long tot = 0, pre = 0;
+    if (cin)
+        for (int k = 0; k < cw; ++k) {
+            const unsigned long long pc = (unsigned long long)__popcll(bm[(long)k * rw + c]) & 1;
+            tot ^= pc;
+            if (k < k0) pre ^= pc;
+        }
+    const unsigned long long left = __popcll(__ballot(tot != 0) & ((1ull << lane) - 1)) & 1;
+    unsigned long long run = base ^ left ^ pre;
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        const int k = k0 + j;
+        if (cin && k < cw) {
+            const unsigned long long wd = bm[(long)k * rw + c];
+            unsigned long long y = wd;                             // bit i = parity of bits 0 .. i
+            y ^= y << 1; y ^= y << 2; y ^= y << 4; y ^= y << 8; y ^= y << 16; y ^= y << 32;
+            acc[j] |= run ? ~y : y;
+            run ^= (unsigned long long)__popcll(wd) & 1;
+        }
+    }
+}
+
+// Bitmap of part p of instance `inst` (p lies inside the part table: load_inst), or null: the part must name this instance and its
+// bitmap must lie in the workspace.
+__device__ __forceinline__ const unsigned long long* part_bitmap(const int64_t* __restrict__ parts, int p, int inst, const SegInst& in,
+                                                                 const unsigned long long* __restrict__ ws, long ws_words) {
+    const int64_t off = parts[(long)p * MPN_SEGP_COLS + MPN_SEGP_BM];
+    if (parts[(long)p * MPN_SEGP_COLS + MPN_SEGP_INST] != inst || off < 0 || off > ws_words || (long)(in.h / 64 + 1) * in.rw > ws_words - off)
+        return nullptr;
+    return ws + off;
+}
+
 __global__ void __launch_bounds__(256) segm_fill_kernel(const int64_t* __restrict__ parts, int n_parts, const int64_t* __restrict__ insts,
                                                         const unsigned long long* __restrict__ ws, long ws_words,
                                                         uint8_t* __restrict__ out, long out_bytes, int32_t* __restrict__ any_on) {
@@ -159,37 +211,8 @@ __global__ void __launch_bounds__(256) segm_fill_kernel(const int64_t* __restric
 #pragma unroll
     for (int j = 0; j < SEG_KC; ++j) acc[j] = 0;
     for (int p = in.p0 + wave; p < in.p1; p += 4) {
-        // p lies inside the part table (load_inst); the part must name this instance and its bitmap must lie in the workspace
-        const int64_t off = parts[(long)p * MPN_SEGP_COLS + MPN_SEGP_BM];
-        if (parts[(long)p * MPN_SEGP_COLS + MPN_SEGP_INST] != inst || off < 0 || off > ws_words || (long)cw * in.rw > ws_words - off)
-            continue;                                                 // the same for the whole wave
-        const unsigned long long* bm = ws + off;
-        // parity of every toggle in the columns before this tile (an RLE run may span columns; a closed outline leaves none)
-        unsigned long long base = 0;
-        for (int cc = lane; cc < c0; cc += 64)
-            for (int k = 0; k < cw; ++k) base ^= (unsigned long long)__popcll(bm[(long)k * in.rw + cc]);
-        base = wave_parity(base);
-        // this column: all of it (for the columns to its right) and what lies above the tile
-        unsigned long long tot = 0, pre = 0;
-        if (cin)
-            for (int k = 0; k < cw; ++k) {
-                const unsigned long long pc = (unsigned long long)__popcll(bm[(long)k * in.rw + c]) & 1;
-                tot ^= pc;
-                if (k < k0) pre ^= pc;
-            }
-        const unsigned long long left = __popcll(__ballot(tot != 0) & ((1ull << lane) - 1)) & 1;
-        unsigned long long run = base ^ left ^ pre;
-#pragma unroll
-        for (int j = 0; j < SEG_KC; ++j) {
-            const int k = k0 + j;
-            if (cin && k < cw) {
-                const unsigned long long wd = bm[(long)k * in.rw + c];
-                unsigned long long y = wd;                             // bit i = parity of bits 0 .. i
-                y ^= y << 1; y ^= y << 2; y ^= y << 4; y ^= y << 8; y ^= y << 16; y ^= y << 32;
-                acc[j] |= run ? ~y : y;
-                run ^= (unsigned long long)__popcll(wd) & 1;
-            }
-        }
+        const unsigned long long* bm = part_bitmap(parts, p, inst, in, ws, ws_words);
+        if (bm) or_part_words<SEG_KC>(bm, in.rw, cw, c0, c, cin, k0, lane, acc);          // the same for the whole wave
     }
 #pragma unroll
     for (int j = 0; j < SEG_KC; ++j) slab[wave][j][lane] = acc[j];
@@ -214,6 +237,140 @@ __global__ void __launch_bounds__(256) segm_fill_kernel(const int64_t* __restric
     if (__ballot(on) != 0 && lane == 0) any_on[inst] = 1;
 }
 
+struct SegImg {
+    int h, w, i0, i1;
+    long off, pitch;
+    bool ok;
+};
+
+// Image row -> registers.  ok: its instances lie in the instance table and its H x W plane lies in the output.
+__device__ __forceinline__ SegImg load_img(const int64_t* __restrict__ row, int n_inst, long out_bytes) {
+    SegImg s;
+    const int64_t h = row[MPN_SEGM_H], w = row[MPN_SEGM_W], i0 = row[MPN_SEGM_I0], i1 = row[MPN_SEGM_I1];
+    s.off = row[MPN_SEGM_OUT_OFF];
+    s.pitch = row[MPN_SEGM_OUT_PITCH];
+    s.ok = h >= 1 && h <= 65536 && w >= 1 && w <= 65536 && h * w <= 0x7fffffffL && i0 >= 0 && i0 <= i1 && i1 <= n_inst;
+    s.ok = s.ok && s.off >= 0 && s.pitch >= w && s.off <= out_bytes && s.pitch <= out_bytes && (h - 1) * s.pitch + w <= out_bytes - s.off;
+    s.h = s.ok ? (int)h : 1; s.w = s.ok ? (int)w : 1;
+    s.i0 = s.ok ? (int)i0 : 0; s.i1 = s.ok ? (int)i1 : 0;
+    return s;
+}
+
+// bits lo .. hi - 1 of a word (any lo, hi; empty when hi <= lo)
+__device__ __forceinline__ unsigned long long bit_range(int lo, int hi) {
+    if (hi <= 0 || lo >= 64 || hi <= lo) return 0;
+    const unsigned long long below_hi = hi >= 64 ? ~0ull : (1ull << hi) - 1;
+    return lo <= 0 ? below_hi : below_hi & (~0ull << lo);
+}
+
+// mask_miss of one image from its person annotations IN ORDER (datasets/segm.py states the rule): workgroup = 64 image columns x
+// 512 image rows of one image.  Wave v owns words 2 v and 2 v + 1 of the tile's eight through every instance, so `all` and `miss`
+// stay in its registers and nothing crosses waves before the turn: for an instance whose rectangle meets its words it ORs the
+// instance's parts (or_part_words, image column x = rectangle column x - rx0, cells outside the rectangle read 0) and only then
+// applies the kind.  ~miss goes column-major -> row-major through LDS (4 KiB) and is stored as 0 / 255 along rows, four bytes per lane
+// where the plane's rows are 4-byte aligned.  No atomics: the bytes are the same on every run.
+__global__ void __launch_bounds__(256) segm_mask_miss_kernel(const int64_t* __restrict__ imgs, const int64_t* __restrict__ insts, int n_inst,
+                                                             const int32_t* __restrict__ kind, const int64_t* __restrict__ parts, int n_parts,
+                                                             const unsigned long long* __restrict__ ws, long ws_words,
+                                                             uint8_t* __restrict__ out, long out_bytes) {
+    constexpr int NW = SEG_KC / 4;                                       // words per wave
+    __shared__ unsigned long long slab[SEG_KC][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const SegImg im = load_img(imgs + (long)blockIdx.z * MPN_SEGM_COLS, n_inst, out_bytes);
+    const int x0 = blockIdx.x * 64, k0 = blockIdx.y * SEG_KC;
+    if (!im.ok || x0 >= im.w || k0 * 64 >= im.h) return;                 // the same for the whole workgroup
+    const int kw = k0 + wave * NW;                                       // this wave's first word
+    unsigned long long all[NW], miss[NW];
+#pragma unroll
+    for (int j = 0; j < NW; ++j) all[j] = miss[j] = 0;
+    for (int i = im.i0; i < im.i1; ++i) {
+        const SegInst in = load_inst(insts + (long)i * MPN_SEGI_COLS, n_parts, -1);
+        const int kd = kind[i];
+        if (!in.ok || in.h != im.h || in.w != im.w || kd < MPN_SEGK_KEYPOINTS || kd > MPN_SEGK_CROWD) continue;
+        // the rectangle misses the tile: the same for the whole workgroup
+        if (in.rx0 >= x0 + 64 || in.rx0 + in.rw <= x0 || in.ry0 >= (k0 + SEG_KC) * 64 || in.ry0 + in.rh <= k0 * 64) continue;
+        // ... or this wave's words of it: the same for the whole wave
+        if (in.ry0 >= (kw + NW) * 64 || in.ry0 + in.rh <= kw * 64) continue;
+        const int c = x0 + lane - in.rx0, cw = in.h / 64 + 1;
+        const bool cin = c >= 0 && c < in.rw;
+        unsigned long long m[NW];
+#pragma unroll
+        for (int j = 0; j < NW; ++j) m[j] = 0;
+        for (int p = in.p0; p < in.p1; ++p) {
+            const unsigned long long* bm = part_bitmap(parts, p, i, in, ws, ws_words);
+            if (bm) or_part_words<NW>(bm, in.rw, cw, x0 - in.rx0, c, cin, kw, lane, m);
+        }
+        // every part is in: now the kind
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            const unsigned long long mj = m[j] & bit_range(in.ry0 - (kw + j) * 64, in.ry0 + in.rh - (kw + j) * 64);
+            if (kd == MPN_SEGK_CROWD) {
+                miss[j] |= mj & ~all[j];
+            } else {
+                all[j] |= mj;
+                if (kd == MPN_SEGK_NO_KEYPOINTS) miss[j] |= mj;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NW; ++j) slab[wave * NW + j][lane] = ~miss[j];
+    __syncthreads();
+    // rows: a lane holds four consecutive columns, 16 lanes are the 64 bytes of one row, a wave stores four rows at a time; wave v
+    // stores rows 16 v .. 16 v + 15 of every word
+    const int cg = (lane & 15) * 4, x = x0 + cg;
+    uint8_t* plane = out + im.off;
+    const bool wide = (((uintptr_t)plane | (uintptr_t)im.pitch) & 3) == 0 && x + 3 < im.w;
+#pragma unroll 1
+    for (int j = 0; j < SEG_KC; ++j) {
+        if ((k0 + j) * 64 >= im.h) break;
+        unsigned long long wd[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) wd[t] = slab[j][cg + t];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int b = wave * 16 + r * 4 + (lane >> 4), y = (k0 + j) * 64 + b;
+            if (y >= im.h || x >= im.w) continue;
+            uint32_t v = 0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) v |= (0u - (uint32_t)((wd[t] >> b) & 1) & 0xffu) << (8 * t);
+            uint8_t* q = plane + (long)y * im.pitch + x;
+            if (wide) {
+                *reinterpret_cast<uint32_t*>(q) = v;
+            } else {
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    if (x + t < im.w) q[t] = (uint8_t)(v >> (8 * t));
+            }
+        }
+    }
+}
+
+// The toggle stage both entry points start with: the workspace zeroed, then one bit flipped per crossing of a polygon outline and
+// per listed RLE toggle.  out_bytes < 0: the instances' OUT columns are not checked (load_inst).  Validates what it uses before its
+// first HIP call.
+int segm_toggle_stage(const int64_t* insts, int n_inst, const int64_t* parts, int n_parts, const int32_t* verts, const int32_t* vpart,
+                      const int32_t* estart, int n_verts, int64_t n_steps, const int32_t* toggles, int n_tog, long out_bytes,
+                      void* workspace, int64_t ws_bytes, hipStream_t st) {
+    MPN_CHECK_ARG(workspace && estart && n_inst >= 0 && n_inst <= 65535 && n_parts >= 0 && n_verts >= 0 && n_tog >= 0 && n_steps >= 0 && n_steps <= 0x7fffffffL);
+    MPN_CHECK_ARG((n_inst == 0 || insts) && (n_parts == 0 || parts));
+    MPN_CHECK_ARG(n_verts == 0 || (verts && vpart));
+    MPN_CHECK_ARG(n_verts > 0 || n_steps == 0);
+    MPN_CHECK_ARG(n_tog == 0 || toggles);
+    MPN_CHECK_ARG(ws_bytes >= 8 && ws_bytes % 8 == 0 && ws_bytes / 8 <= 0x7fffffffL);
+    MPN_CHECK_ARG(((uintptr_t)insts | (uintptr_t)parts | (uintptr_t)workspace) % 8 == 0);
+    MPN_CHECK_ARG(((uintptr_t)verts | (uintptr_t)vpart | (uintptr_t)estart | (uintptr_t)toggles) % 4 == 0);
+    const long ws_words = (long)(ws_bytes / 8);
+    unsigned long long* ws = (unsigned long long*)workspace;
+    if (hipMemsetAsync(workspace, 0, (size_t)ws_bytes, st) != hipSuccess) return mpn_launch_status();
+    if (n_steps > 0)
+        hipLaunchKernelGGL(segm_toggle_poly_kernel, dim3((unsigned)((n_steps + 255) / 256)), dim3(256), 0, st, verts, vpart, estart, n_verts,
+                           (long)n_steps, parts, n_parts, insts, n_inst, out_bytes, ws, ws_words);
+    if (n_tog > 0)
+        hipLaunchKernelGGL(segm_toggle_rle_kernel, dim3((unsigned)((n_tog + 255) / 256)), dim3(256), 0, st, toggles, n_tog, parts, n_parts,
+                           insts, n_inst, n_verts, out_bytes, ws, ws_words);
+    return mpn_launch_status();
+}
+
 }  // namespace
 
 extern "C" int64_t mpn_segm_workspace_bytes(int64_t words) {
@@ -225,31 +382,36 @@ extern "C" int mpn_segm_rasterize(const int64_t* insts, int n_inst, const int64_
                                   const int32_t* vpart, const int32_t* estart, int n_verts, int64_t n_steps, const int32_t* toggles,
                                   int n_tog, int max_rw, int max_h, uint8_t* out, int64_t out_bytes, int dense, int32_t* any_on,
                                   void* workspace, int64_t ws_bytes, void* stream) {
-    MPN_CHECK_ARG(insts && parts && out && any_on && workspace && estart);
-    MPN_CHECK_ARG(n_inst >= 1 && n_inst <= 65535 && n_parts >= 0 && n_verts >= 0 && n_tog >= 0 && n_steps >= 0 && n_steps <= 0x7fffffffL);
-    MPN_CHECK_ARG(n_verts == 0 || (verts && vpart));
-    MPN_CHECK_ARG(n_verts > 0 || n_steps == 0);
-    MPN_CHECK_ARG(n_tog == 0 || toggles);
+    MPN_CHECK_ARG(insts && parts && out && any_on && n_inst >= 1);
     MPN_CHECK_ARG(max_rw >= 1 && max_rw <= 65536 && max_h >= 1 && max_h <= 65536 && out_bytes >= 1 && out_bytes <= (1L << 40) && (dense == 0 || dense == 1));
-    MPN_CHECK_ARG(ws_bytes >= 8 && ws_bytes % 8 == 0 && ws_bytes / 8 <= 0x7fffffffL);
-    MPN_CHECK_ARG(((uintptr_t)insts | (uintptr_t)parts | (uintptr_t)workspace) % 8 == 0);
-    MPN_CHECK_ARG(((uintptr_t)verts | (uintptr_t)vpart | (uintptr_t)estart | (uintptr_t)toggles | (uintptr_t)any_on) % 4 == 0);
+    MPN_CHECK_ARG((uintptr_t)any_on % 4 == 0);
     hipStream_t st = (hipStream_t)stream;
-    const long ws_words = (long)(ws_bytes / 8);
-    unsigned long long* ws = (unsigned long long*)workspace;
-    if (hipMemsetAsync(workspace, 0, (size_t)ws_bytes, st) != hipSuccess) return mpn_launch_status();
+    const int rc = segm_toggle_stage(insts, n_inst, parts, n_parts, verts, vpart, estart, n_verts, n_steps, toggles, n_tog, (long)out_bytes,
+                                     workspace, ws_bytes, st);
+    if (rc != 0) return rc;
     if (hipMemsetAsync(any_on, 0, (size_t)n_inst * sizeof(int32_t), st) != hipSuccess) return mpn_launch_status();
     // dense: the planes are zero outside the rectangles; packed: the rectangles are written whole (the padding between them is not read)
     if (dense && hipMemsetAsync(out, 0, (size_t)out_bytes, st) != hipSuccess) return mpn_launch_status();
-    if (n_steps > 0)
-        hipLaunchKernelGGL(segm_toggle_poly_kernel, dim3((unsigned)((n_steps + 255) / 256)), dim3(256), 0, st, verts, vpart, estart, n_verts,
-                           (long)n_steps, parts, n_parts, insts, n_inst, (long)out_bytes, ws, ws_words);
-    if (n_tog > 0)
-        hipLaunchKernelGGL(segm_toggle_rle_kernel, dim3((unsigned)((n_tog + 255) / 256)), dim3(256), 0, st, toggles, n_tog, parts, n_parts,
-                           insts, n_inst, n_verts, (long)out_bytes, ws, ws_words);
     const int words = max_h / 64 + 1;
     dim3 grid((unsigned)((max_rw + 63) / 64), (unsigned)((words + SEG_KC - 1) / SEG_KC), (unsigned)n_inst);
-    hipLaunchKernelGGL(segm_fill_kernel, grid, dim3(256), 0, st, parts, n_parts, insts, (const unsigned long long*)ws, ws_words, out,
-                       (long)out_bytes, any_on);
+    hipLaunchKernelGGL(segm_fill_kernel, grid, dim3(256), 0, st, parts, n_parts, insts, (const unsigned long long*)workspace, (long)(ws_bytes / 8),
+                       out, (long)out_bytes, any_on);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_segm_mask_miss(const int64_t* imgs, int n_img, const int64_t* insts, const int32_t* kind, int n_inst, const int64_t* parts,
+                                  int n_parts, const int32_t* verts, const int32_t* vpart, const int32_t* estart, int n_verts, int64_t n_steps,
+                                  const int32_t* toggles, int n_tog, int max_w, int max_h, uint8_t* out, int64_t out_bytes, void* workspace,
+                                  int64_t ws_bytes, void* stream) {
+    MPN_CHECK_ARG(imgs && out && n_img >= 1 && n_img <= 65535 && n_inst >= 0 && (n_inst == 0 || kind));
+    MPN_CHECK_ARG(max_w >= 1 && max_w <= 65536 && max_h >= 1 && max_h <= 65536 && out_bytes >= 1 && out_bytes <= (1L << 40));
+    MPN_CHECK_ARG((uintptr_t)imgs % 8 == 0 && (uintptr_t)kind % 4 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    const int rc = segm_toggle_stage(insts, n_inst, parts, n_parts, verts, vpart, estart, n_verts, n_steps, toggles, n_tog, -1L, workspace,
+                                     ws_bytes, st);
+    if (rc != 0) return rc;
+    dim3 grid((unsigned)((max_w + 63) / 64), (unsigned)((max_h + 64 * SEG_KC - 1) / (64 * SEG_KC)), (unsigned)n_img);
+    hipLaunchKernelGGL(segm_mask_miss_kernel, grid, dim3(256), 0, st, imgs, insts, n_inst, kind, parts, n_parts,
+                       (const unsigned long long*)workspace, (long)(ws_bytes / 8), out, (long)out_bytes);
     return mpn_launch_status();
 }

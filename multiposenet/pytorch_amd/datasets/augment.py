@@ -432,6 +432,24 @@ def batch_kind(samples):
     return kinds.pop() if kinds else "instances"
 
 
+def mask_source(samples):
+    """"mask_miss", "person_anns" or None: where every sample of the batch gets its mask_miss from — the uint8 plane itself, the
+    image's person annotations (rasterised and composed on the device, :func:`..segm.mask_miss_batch`) or nowhere (the image-only
+    form).  A sample with both keys, a batch that mixes the two and a batch where only some samples have one raise — before any dice
+    are drawn."""
+    kinds = set()
+    for s in samples:
+        has = [k for k in ("mask_miss", "person_anns") if s.get(k) is not None]
+        if len(has) > 1:
+            raise MpnError("a sample carries either 'mask_miss' or 'person_anns'")
+        kinds.add(has[0] if has else None)
+    if "mask_miss" in kinds and "person_anns" in kinds:
+        raise MpnError("a batch carries either 'mask_miss' or 'person_anns', not both kinds")
+    if len(kinds) > 1:
+        raise MpnError("either every sample of a batch has a mask_miss or none has")
+    return kinds.pop() if kinds else None
+
+
 def segmentation_pack(sample, H, W, strict=True):
     """The ``segmentations`` path's counterpart of :func:`instance_rects`: the sample's non-crowd annotations packed for
     mpn_segm_rasterize (:func:`..segm.pack_segmentations`; O(vertices), no pixel is touched).  A crowd yields no row and is not
@@ -524,7 +542,10 @@ class DeviceAugmenter(_Augmenter):
          "objpos_other": [n, 2] (optional)}
 
     ``joint_self`` / ``joint_others`` with 18 rows are taken as already in this work's order (no neck is added).  With
-    ``mask_miss`` None in every sample the image-only form is returned: ``heat_mask`` is None.  (The ``aug_*_bbox`` chain of the
+    ``mask_miss`` None in every sample the image-only form is returned: ``heat_mask`` is None.  Instead of ``mask_miss`` a sample may
+    carry ``"person_anns"``: the image's person annotation dicts in json order (``segmentation``, ``iscrowd``, ``num_keypoints`` or
+    ``keypoints``; an empty list is allowed), from which the plane is built on the device by the rule of :mod:`..segm`, so no PNG
+    is read and no H x W plane is uploaded; ``segm_strict`` applies (:func:`mask_source` states what a batch may mix).  (The ``aug_*_bbox`` chain of the
     detection loader is NOT this chain with the mask left out: it never rotates ``objpos`` and so crops elsewhere; see
     :func:`augment_meta_bbox` and :class:`DeviceBBoxAugmenter`.)  ``dice`` [B, 6] makes the draws explicit; otherwise they come from ``rng``
     (a ``random.Random``; default the ``random`` module, as in the reference) through :func:`draw_dice`."""
@@ -533,17 +554,17 @@ class DeviceAugmenter(_Augmenter):
         """Part 1 for a batch: list of per-sample dicts of :func:`augment_meta` with the final (``remove_illegal_joint``) joints
         under ``joint_self_out`` / ``joint_others_out``.  Needs no GPU.  ``mask_frame`` asks for the ``crop + 1`` slice test of
         the masks even when the batch carries no ``mask_miss`` (instance masks take the same slices)."""
-        with_mask = [s.get("mask_miss") is not None for s in samples]
-        if samples and any(with_mask) != all(with_mask):               # before the dice are drawn: a refused batch leaves rng alone
-            raise MpnError("either every sample of a batch has a mask_miss or none has")
+        source = mask_source(samples)                                  # before the dice are drawn: a refused batch leaves rng alone
         dice, sizes = _batch_front(samples, dice, rng, self.params)
-        frame = with_mask[0] or mask_frame
+        frame = source is not None or mask_frame
         metas = []
         for s, d, (H, W) in zip(samples, dice, sizes):
             if s.get("mask_miss") is not None:
                 _check_u8(s["mask_miss"], "mask_miss", 2)
                 if tuple(s["mask_miss"].shape) != (H, W):
                     raise MpnError("mask_miss must have the image's [H, W]")
+            if s.get("person_anns") is not None and not isinstance(s["person_anns"], (list, tuple)):
+                raise MpnError("person_anns must be the list of the image's annotation dicts")
             js = np.asarray(s["joint_self"], dtype=np.float64)
             jo = np.asarray(s.get("joint_others", np.zeros((0,) + js.shape)), dtype=np.float64)
             if js.shape == (17, 3):
@@ -578,12 +599,12 @@ class DeviceAugmenter(_Augmenter):
                 g["rects"] = [(None,) + r for r in g["segm"].rects()]
         rects = [instance_rects(s, g["H"], g["W"]) for s, g in zip(samples, metas)] if kind == "instances" else None
         B, S = len(samples), self.inp_size
-        has_mask = samples[0].get("mask_miss") is not None
+        source = mask_source(samples)
         # one pinned staging buffer per kind (every source starts on a 16-byte boundary), one H2D copy each
         stage_i, img_off = _pack_pinned([s["img"] for s in samples])
         # the table carries the masks' offsets with or without a mask buffer, as it always has
         mask_off = _aligned_offsets([g["H"] * g["W"] for g in metas])[0]
-        stage_m = _pack_pinned([s["mask_miss"] for s in samples])[0] if has_mask else None
+        stage_m = _pack_pinned([s["mask_miss"] for s in samples])[0] if source == "mask_miss" else None
         table = _pinned(B * T_COLS, torch.float64).view(B, T_COLS)
         maxP = max(1 + g["joint_others_out"].shape[0] for g in metas)
         joints = _pinned(B * maxP * 18 * 3, torch.float64).view(B, maxP, 18, 3).zero_()
@@ -599,9 +620,15 @@ class DeviceAugmenter(_Augmenter):
         d_table = table.to(dev, non_blocking=True)
         img = augment_image(d_img, d_table, S, S)
         heat_mask = None
-        if has_mask:
+        if source is not None:
             grid = int(S / self.stride)                               # COCO_data_pipeline.py:206-207
-            heat_mask = augment_mask(stage_m.to(dev, non_blocking=True), d_table, grid, grid, self.stride, S)
+            if source == "person_anns":
+                # the planes are composed on the device at the offsets and pitch W the table rows carry
+                d_mask = segm.mask_miss_batch([s["person_anns"] for s in samples], [(g["H"], g["W"]) for g in metas], mask_off,
+                                              self.segm_strict, dev)[0]
+            else:
+                d_mask = stage_m.to(dev, non_blocking=True)
+            heat_mask = augment_mask(d_mask, d_table, grid, grid, self.stride, S)
         heatmaps = put_gaussian_maps(joints.to(dev, non_blocking=True), num.to(dev, non_blocking=True), S, S, self.stride,
                                      self.params["sigma"])
         # the pinned staging buffers may go out of scope here: torch's caching host allocator records the stream of a non_blocking

@@ -7,6 +7,20 @@ The host side here is O(vertices): :func:`pack_segmentations` upsamples the vert
 every instance a rectangle that is certain to contain its ON cells; no pixel is touched.  The device side flips one bit per
 crossing (mpn_segm_rasterize's toggle launch) and turns the bits into uint8 cells by prefix parity (its fill launch), either as the
 packed rectangles ``mpn_augment_boxes`` reads (:func:`rasterize_packed`) or as dense masks (:func:`rasterize_segmentations`).
+
+``mask_miss`` — the uint8 [H, W] image that takes unlabelled people and crowds out of the heat-map loss, which the reference reads
+as a PNG written by a MATLAB step (``COCO_data_pipeline.py:244-250``) — comes from the same toggle launch and ONE compose launch
+(mpn_segm_mask_miss) over an image's person annotations in json order, with ``M_p`` the ``annToMask`` of annotation ``p``::
+
+    all = 0; miss = 0
+    for p in order:
+        if iscrowd(p):            miss |= M_p & ~all          # "all" as accumulated SO FAR, not the final union
+        else:                     all  |= M_p
+                                  if num_keypoints(p) <= 0: miss |= M_p
+    mask_miss = 255 where miss == 0, else 0
+
+With at most one crowd per image this is what the known scripts compute; they refuse, or leave undefined, more than one crowd, and
+here every crowd contributes as above.  No instance mask is ever in memory (:func:`mask_miss_batch`).
 """
 import math
 
@@ -23,6 +37,9 @@ MAX_INSTANCES = 65535
 # columns of the int64 instance table and of the int64 part table (include/mpn.h: MPN_SEGI_*, MPN_SEGP_*)
 I_H, I_W, I_RX0, I_RY0, I_RW, I_RH, I_OUT_OFF, I_OUT_PITCH, I_P0, I_P1, I_COLS = range(11)
 P_INST, P_V0, P_V1, P_BM, P_COLS = range(5)
+# columns of mpn_segm_mask_miss's int64 image table (MPN_SEGM_*) and the kinds of a person annotation (MPN_SEGK_*)
+M_H, M_W, M_I0, M_I1, M_OUT_OFF, M_OUT_PITCH, M_COLS = range(7)
+KIND_KEYPOINTS, KIND_NO_KEYPOINTS, KIND_CROWD = 0, 1, 2
 
 
 def string_counts(s):
@@ -219,9 +236,10 @@ def concat_packs(packs):
     return pack
 
 
-def _upload(pack, dev):
-    """Every table in ONE pinned block and one H2D copy (the int64 tables first, so each keeps its alignment) -> device views."""
-    arrs = [pack.insts, pack.parts, pack.verts, pack.vpart, pack.estart, pack.toggles]
+def _upload(pack, dev, extra=()):
+    """Every table (and the arrays of ``extra`` after them) in ONE pinned block and one H2D copy, each starting on an 8-byte
+    boundary -> (device views, bytes uploaded)."""
+    arrs = [pack.insts, pack.parts, pack.verts, pack.vpart, pack.estart, pack.toggles] + list(extra)
     sizes = [(a.nbytes + 7) // 8 * 8 for a in arrs]
     stage = torch.empty(max(sum(sizes), 8), dtype=torch.uint8, pin_memory=True)
     off, offs = 0, []
@@ -269,6 +287,87 @@ def rasterize_segmentations(segms, H, W, strict=True):
         return torch.zeros((0, int(H), int(W)), dtype=torch.uint8, device=dev)
     out, _, _ = _rasterize(pack, pack.dense_layout(), True, dev)
     return out[:pack.n * int(H) * int(W)].view(pack.n, int(H), int(W))
+
+
+def annotation_kind(ann):
+    """KIND_CROWD if ``iscrowd`` is truthy (whatever its ``num_keypoints``), KIND_NO_KEYPOINTS if ``num_keypoints <= 0``, else
+    KIND_KEYPOINTS.  Without ``num_keypoints`` it is the count of ``v > 0`` entries of ``keypoints``; MpnError without both."""
+    if ann.get("iscrowd"):
+        return KIND_CROWD
+    n = ann.get("num_keypoints")
+    if n is None:
+        kp = ann.get("keypoints")
+        if kp is None:
+            raise MpnError("a person annotation needs 'num_keypoints' or 'keypoints'")
+        n = int(np.count_nonzero(_numbers(kp, "keypoints")[2::3] > 0))
+    return KIND_NO_KEYPOINTS if n <= 0 else KIND_KEYPOINTS
+
+
+def pack_mask_miss(anns, H, W, strict=True):
+    """The person annotations of one H x W image, in json order -> (:class:`SegmPack`, ``kinds`` int32 [n]) for mpn_segm_mask_miss.
+
+    A KIND_KEYPOINTS annotation after the image's last crowd cannot change the result (``all`` is read by crowds only) and is
+    dropped here, before anything is uploaded: most COCO images have no crowd, so only their KIND_NO_KEYPOINTS annotations get
+    rasterised.  Refusals: those of :func:`pack_segmentations`, an annotation without ``segmentation``, and the one of
+    :func:`annotation_kind`."""
+    kinds = [annotation_kind(a) for a in anns]
+    last_crowd = max([i for i, k in enumerate(kinds) if k == KIND_CROWD] or [-1])
+    keep = [i for i, k in enumerate(kinds) if k != KIND_KEYPOINTS or i < last_crowd]
+    segms = []
+    for i in keep:
+        if anns[i].get("segmentation") is None:
+            raise MpnError("a person annotation needs a 'segmentation'")
+        segms.append(anns[i]["segmentation"])
+    return pack_segmentations(segms, H, W, strict), np.asarray([kinds[i] for i in keep], dtype=np.int32)
+
+
+def pack_mask_miss_batch(list_of_anns, sizes, offsets=None, strict=True):
+    """The host side of :func:`mask_miss_batch`: the images' packs as one, their kinds, and the int64 image table [B, 6] (H, W, the
+    image's instances [i0, i1), byte offset of its plane, row pitch W) -> (pack, kinds, imgs, offsets, bytes of the output)."""
+    if len(list_of_anns) == 0 or len(list_of_anns) != len(sizes) or len(sizes) > MAX_INSTANCES:
+        raise MpnError("a batch needs 1..%d images and one (H, W) for each" % MAX_INSTANCES)
+    sizes = [(int(H), int(W)) for H, W in sizes]
+    packed = [pack_mask_miss(anns, H, W, strict) for anns, (H, W) in zip(list_of_anns, sizes)]
+    if offsets is None:
+        from .augment import _aligned_offsets
+        offsets = _aligned_offsets([H * W for H, W in sizes])[0]
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != len(sizes) or min(offsets) < 0:
+        raise MpnError("one non-negative byte offset per image")
+    imgs = np.zeros((len(sizes), M_COLS), dtype=np.int64)
+    i0 = 0
+    for b, ((H, W), (pk, _), off) in enumerate(zip(sizes, packed, offsets)):
+        imgs[b] = (H, W, i0, i0 + pk.n, off, W)
+        i0 += pk.n
+    nbytes = max(off + H * W for (H, W), off in zip(sizes, offsets))
+    return concat_packs([pk for pk, _ in packed]), np.concatenate([k for _, k in packed]), imgs, offsets, nbytes
+
+
+def mask_miss_batch(list_of_anns, sizes, offsets=None, strict=True, dev=None):
+    """``mask_miss`` of every image of a batch (``list_of_anns[b]`` the person annotations of image ``b`` in json order, an empty
+    list allowed; ``sizes[b]`` its (H, W)) -> (uint8 device buffer, byte offsets): image ``b`` is the row-major H x W plane at
+    ``offsets[b]`` (default: consecutive planes, each starting on a 16-byte boundary, the layout ``mpn_augment_mask`` reads); the
+    bytes between planes hold nothing.  One pinned upload and two launches for the whole batch; nothing waits for the device."""
+    dev = _device() if dev is None else dev
+    pack, kinds, imgs, offsets, nbytes = pack_mask_miss_batch(list_of_anns, sizes, offsets, strict)
+    out = torch.empty(max((nbytes + 15) // 16 * 16, 16), dtype=torch.uint8, device=dev)
+    (insts, parts, verts, vpart, estart, toggles, d_imgs, d_kinds), _ = _upload(pack, dev, (imgs, kinds))
+    ws_bytes = int(call("mpn_segm_workspace_bytes", pack.words))
+    if ws_bytes <= 0:
+        raise MpnError("mpn_segm_workspace_bytes refused %d words" % pack.words)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    n, npt, nv, nt = pack.n, int(pack.parts.shape[0]), int(pack.verts.shape[0]), int(pack.toggles.shape[0])
+    call("mpn_segm_mask_miss", ops.ptr(d_imgs), int(imgs.shape[0]), ops.ptr(insts) if n else None, ops.ptr(d_kinds) if n else None, n,
+         ops.ptr(parts) if npt else None, npt, ops.ptr(verts) if nv else None, ops.ptr(vpart) if nv else None, ops.ptr(estart), nv,
+         int(pack.estart[-1]), ops.ptr(toggles) if nt else None, nt, int(imgs[:, M_W].max()), int(imgs[:, M_H].max()),
+         ops.ptr(out), out.numel(), ops.ptr(ws), ws_bytes, ops.stream_ptr())
+    return out, offsets
+
+
+def mask_miss_from_annotations(anns, H, W):
+    """``mask_miss`` of one H x W image from its person annotations in json order -> uint8 [H, W] on the device."""
+    out, _ = mask_miss_batch([anns], [(H, W)])
+    return out[:int(H) * int(W)].view(int(H), int(W))
 
 
 def _device():
