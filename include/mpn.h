@@ -747,6 +747,38 @@ int mpn_heatmap_peaks_smooth(const float* heat, int64_t sB, int64_t sJ, int64_t 
 int mpn_resize(const float* src, int64_t sY, int64_t sX, int64_t sC, int Hs, int Ws, int C, float* dst, int Hd, int Wd,
                int cubic, double inv_fy, double inv_fx, void* stream);
 
+/* Multi-scale + flip test-time augmentation (evaluate/tester.py:143-175,256-331), the element-wise ends around the network.
+ *
+ * mpn_tta_input: the network input of ONE scale for the pair {image, horizontally mirrored image} in one launch.  img: the decoded
+ * float32 image, element (y, x, c) at img[y*sY + x*sX + c*sC], [H][W][3] BGR 0..255.  out: dense float32 [2][3][hp][wp]; image 0 is
+ * the original, image 1 the mirrored one (it reads source column W - 1 - x; no mirrored copy exists).  Per image exactly
+ * crop_with_factor + resnet_preprocess: INTER_LINEAR resize to (h, w) in the fx/fy form with inv_scale = 1/f as the scale on both
+ * axes and mpn_resize's clamp rules, the value 128 from (h, w) up to (hp, wp), then BGR -> RGB, times the float32 reciprocal of 255
+ * (how the tensor library divides a float32 tensor by a host scalar), minus mean, correctly rounded division by std, channel-planar.
+ * MPN_E_BADARG before any HIP call for null pointers, non-positive sizes or scale, h > hp or w > wp. */
+int mpn_tta_input(const float* img, int64_t sY, int64_t sX, int64_t sC, int H, int W, float* out, int h, int w, int hp, int wp,
+                  double inv_scale, void* stream);
+
+/* One scale of mpn_tta_merge: the x4-upsampled, cropped pair map, float32, element (y, x, ch) at u[y*pitch + x*36 + ch] for
+ * y < rh, x < rw; channels 0..17 from the pass over the original image, 18..35 from the pass over the mirrored one. */
+typedef struct MpnTtaScale {
+    const float* u;
+    int32_t rh, rw;
+    int64_t pitch;           /* floats between rows, >= 36 * rw */
+} MpnTtaScale;
+
+/* mpn_tta_merge: the averaged maps of an image from the pair maps of its n_scales (1..8) scales in one launch.  scales: HOST table
+ * (copied into the launch); swap: HOST pointer to the 18-entry left/right channel permutation (validated, copied into the launch);
+ * out: dense float32 [H][W][18].  With R(U, y, x, ch) the INTER_CUBIC sample of U[:rh, :rw, ch] at destination (y, x) of an (H, W)
+ * grid in the dsize form, computed as mpn_resize computes it, and r = (float)(1.0 / n_scales):
+ *   a_o = sum over the table, in order, of (double)(R(U_s, y, x, c) * r)                      (float32 product, float64 sum)
+ *   a_f = sum over the table, in order, of (double)(R(U_s, y, W - 1 - x, 18 + swap[c]) * r)
+ *   out[y][x][c] = (float)((a_o + a_f) / 2)
+ * — _get_outputs for both images, _handle_heat and the final .float() with their rounding points.
+ * MPN_E_BADARG before any HIP call for null pointers, n_scales outside 1..8, a non-positive size, a pitch below 36 * rw or a swap
+ * table that is not a permutation of 0..17. */
+int mpn_tta_merge(const MpnTtaScale* scales, int n_scales, const int32_t* swap, float* out, int H, int W, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Pose-residual-network person assignment, device half (evaluate/tester.py:333-513; crop/gaussian helpers
  * datasets/coco_data/prn_gaussian.py:2,134-158).

@@ -63,6 +63,11 @@ class WgradParams(ctypes.Structure):
     ]
 
 
+class TtaScale(ctypes.Structure):
+    """MpnTtaScale: one scale of mpn_tta_merge."""
+    _fields_ = [("u", ctypes.c_void_p), ("rh", ctypes.c_int32), ("rw", ctypes.c_int32), ("pitch", ctypes.c_int64)]
+
+
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 _PC = ctypes.POINTER(ConvParams)
 _PW = ctypes.POINTER(WgradParams)
@@ -84,6 +89,8 @@ SIGNATURES = {
     "mpn_heatmap_peaks_smooth": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _f, ctypes.c_double, _i, ctypes.POINTER(ctypes.c_double), _i,
                                       _vp, _vp, _i, _vp, _vp]),
     "mpn_resize": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),
+    "mpn_tta_input": (_i, [_vp, _i64, _i64, _i64, _i, _i, _vp, _i, _i, _i, _i, ctypes.c_double, _vp]),
+    "mpn_tta_merge": (_i, [ctypes.POINTER(TtaScale), _i, ctypes.POINTER(ctypes.c_int32), _vp, _i, _i, _vp]),
     "mpn_prn_build_maps": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     "mpn_prn_scores": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mpn_prn_scores_compact": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

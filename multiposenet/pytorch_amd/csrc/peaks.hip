@@ -6,22 +6,12 @@
 // The refinement restates cv2.resize(INTER_CUBIC) (float32, A = -0.75, s = (d + 0.5)/f - 0.5, taps clamped to the patch,
 // horizontal then vertical pass) op for op with oracle/joint_oracle.py; built with -ffp-contract=off.
 #include "common.h"
+#include "resize_taps.h"
 #include <string.h>
 
 namespace {
 
 constexpr int PK_THREADS = 256;
-
-__device__ __forceinline__ void cubic_taps(int d, double scale, int n_src, int (&idx)[4], float (&co)[4]) {
-    const float fx = (float)(((double)d + 0.5) * scale - 0.5);
-    const int sx = (int)floorf(fx);
-    cubic_coeffs(fx - (float)sx, co);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        int s = sx - 1 + k;
-        idx[k] = s < 0 ? 0 : (s > n_src - 1 ? n_src - 1 : s);
-    }
-}
 
 // ---- round 6: three bandwidth-shaped launches instead of one workgroup per plane --------------------------------------------
 //   flags   : every cell's peak test, lanes on CONSECUTIVE addresses of whichever layout the caller passes (channels-last: the

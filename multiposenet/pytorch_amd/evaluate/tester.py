@@ -5,6 +5,9 @@
     results = tester.infer_image_multiscale(img, 'name.jpg', image_id)    # body of Tester.coco_eval() for one image (:143-175):
                                                                 # 5 scales x {original, flipped} test-time augmentation
 
+    results = tester.infer_image_multiscale_fused(img, 'name.jpg', image_id)   # the same dicts from 5 paired forwards and csrc/tta.hip
+    results = tester.infer_images_multiscale(images, names, ids)   # ... over many images, post-processing under the next image's network
+
     results = tester.coco_eval(images)                         # :131-191 from decoded images on: results file in COCO order
     mean, std = tester.val()                                   # :515-543 validation-loss loop
 
@@ -15,6 +18,7 @@ exists in this image; the result files (:176-178, :243-245) are written here.  E
 assignment (prn_process.py).  ``cv2.resize`` is restated, not linked: parity with OpenCV is unpinned (no cv2 here), see
 DESIGN.md.
 """
+import ctypes
 import json
 import logging
 import os
@@ -23,7 +27,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from .._lib import call
+from .._lib import TtaScale, call
 from ..network import net_utils
 from ..network.joint_utils import get_joint_list
 from .prn_process import prn_process
@@ -55,6 +59,7 @@ class TestParams(object):
     print_freq = 20
     gaussian_filt = False             # NMS(..., bool_gaussian_filt=True): smooth every up-sampled peak patch (sigma 3) before its arg-max
     category_ids = [1]                # detect_images / coco_eval_bbox: class index of the detection head -> COCO category id
+    tta_fused = False                 # coco_eval: the fused, flip-paired test-time augmentation (infer_images_multiscale; same results)
     nms_per_class = False             # detect_images / coco_eval_bbox: every (anchor, class) score is a candidate, NMS per class (not in the reference)
 
 
@@ -74,15 +79,21 @@ def _round_half_even(v):
     return int(np.rint(v))          # cv::saturate_cast<int> of a double = cvRound
 
 
-def crop_with_factor(im, dest_size, factor=32, pad_val=0, basedon='min'):
-    """tester.py:38-82 for a CUDA [H, W, C] tensor: scale so that the chosen side becomes dest_size (cv2.resize with fx = fy =
-    scale, bilinear), pad bottom/right with pad_val to a multiple of `factor`.  Returns (padded, scale, unpadded shape)."""
-    h0, w0 = im.shape[0], im.shape[1]
+def scale_geometry(h0, w0, dest_size, factor=32, basedon='min'):
+    """The host arithmetic of crop_with_factor (tester.py:38-82) for an h0 x w0 image: (im_scale, h, w, padded h, padded w) — the
+    scale that brings the chosen side to dest_size, the resized shape and its round-up to a multiple of `factor`."""
     base = {'min': min(h0, w0), 'max': max(h0, w0), 'w': w0, 'h': h0}.get(basedon, min(h0, w0))
     im_scale = float(dest_size) / base
     h, w = _round_half_even(h0 * im_scale), _round_half_even(w0 * im_scale)       # dsize = round(src * f)
-    scaled = resize(im, (h, w), cubic=False, inv_scale=(1.0 / im_scale, 1.0 / im_scale))       # cv2.resize(im, None, fx=s, fy=s), tester.py:68
     new_h, new_w = int(np.ceil(float(h) / factor)) * factor, int(np.ceil(float(w) / factor)) * factor
+    return im_scale, h, w, new_h, new_w
+
+
+def crop_with_factor(im, dest_size, factor=32, pad_val=0, basedon='min'):
+    """tester.py:38-82 for a CUDA [H, W, C] tensor: scale so that the chosen side becomes dest_size (cv2.resize with fx = fy =
+    scale, bilinear), pad bottom/right with pad_val to a multiple of `factor`.  Returns (padded, scale, unpadded shape)."""
+    im_scale, h, w, new_h, new_w = scale_geometry(im.shape[0], im.shape[1], dest_size, factor, basedon)
+    scaled = resize(im, (h, w), cubic=False, inv_scale=(1.0 / im_scale, 1.0 / im_scale))       # cv2.resize(im, None, fx=s, fy=s), tester.py:68
     padded = torch.full((new_h, new_w, im.shape[2]), float(pad_val), dtype=torch.float32, device=im.device)
     padded[:h, :w] = scaled
     return padded, im_scale, (h, w, im.shape[2])
@@ -95,6 +106,41 @@ def resnet_preprocess(image):
     mean = torch.tensor([0.485, 0.456, 0.406], dtype=torch.float32, device=img.device)
     std = torch.tensor([0.229, 0.224, 0.225], dtype=torch.float32, device=img.device)
     return ((img - mean) / std).permute(2, 0, 1).contiguous()
+
+
+def tta_input(img, h, w, hp, wp, inv_scale):
+    """mpn_tta_input: float32 [2, 3, hp, wp], ``resnet_preprocess(crop_with_factor(x, ..., pad_val=128)[0])`` for x = img (image 0) and
+    x = img.flip(1) (image 1) in one launch; (h, w, hp, wp) and inv_scale = 1 / im_scale from ``scale_geometry``.  img: CUDA float32
+    [H, W, 3] BGR 0..255, any strides."""
+    x = torch.empty((2, 3, hp, wp), dtype=torch.float32, device=img.device)
+    call("mpn_tta_input", ops.ptr(img), img.stride(0), img.stride(1), img.stride(2), int(img.shape[0]), int(img.shape[1]), ops.ptr(x), h, w, hp, wp,
+         float(inv_scale), ops.stream_ptr())
+    return x
+
+
+def tta_upsample(heat, rh, rw):
+    """The pair map of one scale: heat [2, 18, hq, wq] read as one 36-channel image, the first rh x rw of its x4 INTER_CUBIC map (scale
+    1/4 exactly, which is what the dsize form gives for the whole map) -> float32 [rh, rw, 36].  One mpn_resize."""
+    if heat.stride(0) != 18 * heat.stride(1):
+        heat = heat.contiguous()
+    u = torch.empty((rh, rw, 36), dtype=torch.float32, device=heat.device)
+    call("mpn_resize", ops.ptr(heat), heat.stride(2), heat.stride(3), heat.stride(1), int(heat.shape[2]), int(heat.shape[3]), 36, ops.ptr(u), rh, rw, 1,
+         0.25, 0.25, ops.stream_ptr())
+    return u
+
+
+def tta_merge(pair_maps, H, W, swap=SWAP_HEAT):
+    """mpn_tta_merge: the averaged float32 [H, W, 18] maps from the pair maps ([rh, rw, 36], channel stride 1, pixel stride 36) of every
+    scale — both ``_get_outputs`` accumulations, ``_handle_heat`` and the final ``.float()`` in one launch."""
+    n = len(pair_maps)
+    table = (TtaScale * max(n, 1))()
+    for s, u in enumerate(pair_maps):
+        if u.dtype != torch.float32 or u.shape[2] != 36 or u.stride(2) != 1 or u.stride(1) != 36:
+            raise ValueError("pair map %d: float32 [rh, rw, 36] with dense pixels expected" % s)
+        table[s].u, table[s].rh, table[s].rw, table[s].pitch = u.data_ptr(), int(u.shape[0]), int(u.shape[1]), int(u.stride(0))
+    out = torch.empty((H, W, 18), dtype=torch.float32, device=pair_maps[0].device)
+    call("mpn_tta_merge", table, n, (ctypes.c_int32 * 18)(*swap), ops.ptr(out), H, W, ops.stream_ptr())
+    return out
 
 
 def _to_device_image(img, dev):
@@ -342,9 +388,15 @@ class Tester(object):
         the device instead (oks_eval.KeypointEval over the evaluated image ids): the ten COCO lines are logged, the result dict is
         kept in ``self.last_eval`` and the file is removed unless ``params.testresult_write_json``.  Returns the result list."""
         results, img_ids = [], []
-        for image_id, file_name, img in images:
-            img_ids.append(image_id)
-            results.extend(self.infer_image_multiscale(img, file_name, image_id))
+        if getattr(self.params, 'tta_fused', False):
+            images = list(images)
+            img_ids = [image_id for image_id, _, _ in images]
+            for res in self.infer_images_multiscale([img for _, _, img in images], [name for _, name, _ in images], img_ids):
+                results.extend(res)
+        else:
+            for image_id, file_name, img in images:
+                img_ids.append(image_id)
+                results.extend(self.infer_image_multiscale(img, file_name, image_id))
         ann_filename = self.params.coco_result_filename
         with open(ann_filename, "w") as f:
             json.dump(results, f, indent=4)
@@ -478,3 +530,92 @@ class Tester(object):
             kp = result['keypoints']
             result['keypoints'] = [kp[COCO_ORDER[i] * 3 + j] for i in range(17) for j in range(3)]
         return results
+
+    # ------------------------------------------------------------------ the same, fused and flip-paired (params.tta_fused)
+    def _tta_enqueue(self, img, pair=True):
+        """Everything of ``infer_image_multiscale`` up to the averaged maps, enqueued on the current stream without a host read: per
+        scale ONE mpn_tta_input (the original and the mirrored network input), ONE forward over the pair — keypoint-only except for
+        scale index 1, the only scale whose boxes are used (tester.py:169) — and ONE mpn_resize (the x4 up-sampling of both maps,
+        only the region that survives the crop); then ONE mpn_tta_merge.  ``pair=False``: the two images of a pair go through the
+        network one at a time.  Returns the item ``_tta_finish`` takes; it owns every tensor another stream may still read."""
+        img = _to_device_image(img, self.dev)
+        H, W = int(img.shape[0]), int(img.shape[1])
+        multiplier = self._get_multiplier(img)
+        alive, det, pair_maps = [img], None, []
+        for si, scale in enumerate(multiplier):
+            im_scale, h, w, hp, wp = scale_geometry(H, W, scale * H, 32)
+            x = tta_input(img, h, w, hp, wp, 1.0 / im_scale)
+            with torch.no_grad():
+                if si == 1:
+                    heat, anchors, cls, keep = self.model.forward_padded_begin(x if pair else x[:1])
+                    det = (anchors[:1], cls[:1], 1.0 / im_scale)
+                else:
+                    heat, keep = self.model.forward_heat(x if pair else x[:1])
+                alive.append(keep)
+                if not pair:
+                    heat1, keep = self.model.forward_heat(x[1:])
+                    alive.append(keep)
+                    heat = torch.cat([heat, heat1])
+            hq, wq = int(hp / 4), int(wp / 4)
+            heat = heat[:, :, :hq, :wq]
+            pair_maps.append(tta_upsample(heat, min(h, 4 * hq), min(w, 4 * wq)))       # only the region that survives the crop
+            alive += [x, heat]
+        return img, tta_merge(pair_maps, H, W), det, alive + pair_maps
+
+    def _tta_finish(self, item, file_name, image_id):
+        """Boxes of scale index 1 (image 0 of the pair), peaks of the averaged maps, PRN assignment, COCO order — on the current stream."""
+        img, heat, (anchors, cls, box_scale), _alive = item
+        multi = cls.shape[-1] > 1
+        det = self.model.detect_padded(anchors, cls, return_class=multi)
+        boxes, scores, kept = det[:3]
+        bboxs = []
+        k = int(kept[0]) if boxes.shape[1] else 0
+        if k:
+            scores_h, boxes_h = scores[0, :k].cpu().numpy(), boxes[0, :k].cpu().numpy()
+            classes_h = det[3][0, :k].cpu().numpy() if multi else np.zeros(k, dtype=np.int64)
+            for j in np.where(scores_h > 0.5)[0]:                     # _boxes: score > 0.5, class 0, box * scale in float32
+                if int(classes_h[j]) == 0:
+                    bboxs.append((boxes_h[j, :] * box_scale).tolist())
+        param = {'thre1': 0.1, 'thre2': 0.05, 'thre3': 0.5}
+        joint_list = get_joint_list(img, param, heat, 1, bool_gaussian_filt=self.params.gaussian_filt)
+        results = self.prn_process(self._body_joints(joint_list), bboxs, file_name, image_id)
+        for result in results:
+            kp = result['keypoints']
+            result['keypoints'] = [kp[COCO_ORDER[i] * 3 + j] for i in range(17) for j in range(3)]
+        return results
+
+    def infer_image_multiscale_fused(self, img, file_name='', image_id=0, pair=True):
+        """``infer_image_multiscale`` with the same result dicts, value for value, from 5 paired forwards instead of 10 single ones
+        (one detection head instead of ten) and two fused element-wise kernels around them (csrc/tta.hip); the only host reads are
+        those of the detections, the peaks and the PRN assignment."""
+        return self._tta_finish(self._tta_enqueue(img, pair), file_name, image_id)
+
+    def infer_images_multiscale(self, images, file_names=None, image_ids=None, pipeline=True, pair=True):
+        """``infer_image_multiscale_fused`` over many images.  ``pipeline``: the launches of image k + 1 up to and including its merge are
+        enqueued BEFORE image k's detections, peaks and PRN assignment are read; those go to the post-processing stream behind an event,
+        as in ``infer_images_batched``.  Same launches on the same data: results identical to ``pipeline=False``."""
+        images = list(images)
+        n = len(images)
+        file_names = file_names if file_names is not None else [''] * n
+        image_ids = image_ids if image_ids is not None else [0] * n
+        out = [None] * n
+        post = self._post_stream() if pipeline else None
+        pending = None
+        for i in list(range(n)) + [None]:
+            nxt = None
+            if i is not None:
+                item = self._tta_enqueue(images[i], pair)
+                if post is None:
+                    out[i] = self._tta_finish(item, file_names[i], image_ids[i])
+                else:
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    nxt = (i, item, ev)
+            if pending is not None:
+                k, item, ev = pending
+                post.wait_event(ev)
+                with torch.cuda.stream(post):
+                    out[k] = self._tta_finish(item, file_names[k], image_ids[k])
+                torch.cuda.current_stream(self.dev).wait_stream(post)      # the item's tensors return to this stream's allocator pool
+            pending = nxt
+        return out

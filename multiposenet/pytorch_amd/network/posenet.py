@@ -356,6 +356,12 @@ class poseNet(nn.Module):
         transformed_anchors = decode_and_clip(self.anchors(img_batch), regression, img_batch)
         return predict_keypoint, transformed_anchors, classification, (ctx, regression)
 
+    def forward_heat(self, img_batch):
+        """The keypoint-only inference pass (no detection pyramid, towers, decode or NMS), ENQUEUED like forward_padded_begin: nothing is
+        read back.  Returns (heat-maps [B,18,H/4,W/4], keep-alive); hold on to the keep-alive until the maps have been consumed."""
+        ctx, _, (predict_keypoint, _, _, _) = self._run_net(img_batch, False, det=False)
+        return predict_keypoint, ctx
+
     @staticmethod
     def detect_padded(transformed_anchors, classification, pre_nms_top_n=None, return_class=False, class_wise=False):
         """Second half: score filter + per-image NMS + gather on the CURRENT stream (two host reads) -> (boxes, scores, kept[, classes]).
