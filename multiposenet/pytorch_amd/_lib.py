@@ -199,8 +199,8 @@ SIGNATURES = {
     "mpn_conv2cls_expand": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mpn_conv2cls_classsum": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "mpn_conv2cls_pool": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "mpn_conv2cls_tapsum": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "mpn_conv2cls_fold": (_i, [_vp, _vp, _i, _i, _vp]),
+    "mpn_conv2cls_tapsum": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mpn_conv2cls_fold": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "mpn_oks_eval_workspace_bytes": (_i64, [_i64, _i, _i]),
     "mpn_oks_matrix": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpn_oks_match": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -20,6 +20,13 @@
 //                                                                               of the low-resolution tensor — 9x fewer FLOPs than the frames)
 //              dW   += fold(dWtap_8, dWtap_4, dW_main)                          (this file)
 // (The forward keeps the frame convolutions: the per-tap form would hand the 9-term sums to the full-resolution expansion.)
+//
+// fp16 only: P_s and G_s are unweighted sums of up to 36 / 64 dy, so a loss-scaled dy (|dy| >= 1024 of one sign over a block) passes
+// 65504 before any filter multiply, where the plain route (f32 accumulation of W dy, one rounding) is finite.  There P_s is stored in
+// f32 (PoolT) and G_s is stored as G_s / s^2 (a mean: never above max |dy|; a power of two, exact outside the subnormals).  Both consumers
+// give the s^2 back in f32, after their contraction: the input-gradient launch through its per-channel epilogue multiplier (ops.py:
+// Conv2ClsOperands.tap_unscale; the filters themselves stay as they are, so no filter magnitude can overflow), fold for the filter gradients.
+// bf16 (dy's own range) and f32 compile the code they always had.
 // Everything here is streaming / tiny; the arithmetic that matters stays in the convolution kernels.
 #include "common.h"
 
@@ -113,6 +120,13 @@ template <typename T> struct Vec8 {
     }
 };
 
+// storage type of the class sums P: f32 for fp16 (see the head of the file), else the compute type itself
+template <typename T> struct PoolT { using type = T; };
+template <> struct PoolT<f16_t> { using type = float; };
+// tapsum stores G * gscale (1 / s^2) where GScale<T>::on (fp16), else G itself (no multiply compiled)
+template <typename T> struct GScale { static constexpr bool on = false; };
+template <> struct GScale<f16_t> { static constexpr bool on = true; };
+
 // E[b, y, x, o] = M8[b, y / 8, x / 8, cls * O + o] + M4[b, y / 4, x / 4, cls' * O + o]; 4 channels per thread, f32 sums, one rounding
 template <typename T>
 __global__ void __launch_bounds__(256) conv2cls_expand_kernel(const float* __restrict__ m8, const float* __restrict__ m4, T* __restrict__ e, int B, int H, int W, int O) {
@@ -166,9 +180,10 @@ __global__ void __launch_bounds__(256) conv2cls_classsum_kernel(const float* __r
 // Class pooling of dy [B, H, W, O]: P4[b, i, j, k * O + o] = sum over the pixels (4 i + a, 4 j + c) of class k of dy; P8 likewise over 8 x 8
 // blocks.  One thread per (4 x 4 quadrant, 4 channels): its 16 pixels (all sixteen 8-byte loads in flight) give the nine P4 sums
 // outright; the four quadrants of an 8 x 8 block sit in four adjacent lanes and their partial P8 sums meet through two xor-shuffles
-// (fixed order: deterministic).  f32 sums, rounded once on store.
+// (fixed order: deterministic).  f32 sums, rounded once on store (fp16: stored as they are, in f32).
 template <typename T>
-__global__ void __launch_bounds__(256) conv2cls_pool_kernel(const T* __restrict__ dy, T* __restrict__ p8, T* __restrict__ p4, int B, int H, int W, int O) {
+__global__ void __launch_bounds__(256) conv2cls_pool_kernel(const T* __restrict__ dy, typename PoolT<T>::type* __restrict__ p8, typename PoolT<T>::type* __restrict__ p4, int B, int H, int W, int O) {
+    using TP = typename PoolT<T>::type;
     constexpr int V = 4;
     const int og = O / V;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -201,10 +216,10 @@ __global__ void __launch_bounds__(256) conv2cls_pool_kernel(const T* __restrict_
             for (int e = 0; e < V; ++e) s4[k][e] += px[a][c].v[e];
         }
     if (live) {
-        T* __restrict__ o4 = p4 + (((long)b * (H >> 2) + (y0 >> 2)) * (W >> 2) + (x0 >> 2)) * 9 * O + g * V;
+        TP* __restrict__ o4 = p4 + (((long)b * (H >> 2) + (y0 >> 2)) * (W >> 2) + (x0 >> 2)) * 9 * O + g * V;
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
-            Vec8<T> v;
+            Vec8<TP> v;
 #pragma unroll
             for (int e = 0; e < V; ++e) v.v[e] = s4[k][e];
             v.store(o4 + (long)k * O);
@@ -212,7 +227,7 @@ __global__ void __launch_bounds__(256) conv2cls_pool_kernel(const T* __restrict_
     }
     // 8 x 8 classes from the quadrant's own nine sums.  Rows of the block: quadrant row qa = 0 holds block rows 0 (first) and 1..3 (mid);
     // qa = 1 holds 4..6 (mid) and 7 (last): block class R takes the quadrant's row classes in `rsel` (bit = quadrant row class).
-    T* __restrict__ o8 = p8 + (((long)b * (H >> 3) + bi) * (W >> 3) + bj) * 9 * O + g * V;
+    TP* __restrict__ o8 = p8 + (((long)b * (H >> 3) + bi) * (W >> 3) + bj) * 9 * O + g * V;
 #pragma unroll
     for (int R = 0; R < 3; ++R) {
         // quadrant row classes (first = 1, mid = 2, last = 4) that belong to block row class R
@@ -237,7 +252,7 @@ __global__ void __launch_bounds__(256) conv2cls_pool_kernel(const T* __restrict_
                 part[e] += __shfl_xor(part[e], 2);
             }
             if (live && quad == 0) {
-                Vec8<T> v;
+                Vec8<TP> v;
 #pragma unroll
                 for (int e = 0; e < V; ++e) v.v[e] = part[e];
                 v.store(o8 + (long)(R * 3 + Cc) * O);
@@ -247,7 +262,9 @@ __global__ void __launch_bounds__(256) conv2cls_pool_kernel(const T* __restrict_
 }
 
 // dW[o][t][c] += dWtap_member[t * O + o][c] (members 0, 1: their per-tap 1x1 filter gradients) or the main part's (members 2, 3);
-// dcomb = dWm [O][9][2C] | dWtap8 [9 O][C] | dWtap4 [9 O][C]
+// dcomb = dWm [O][9][2C] | dWtap8 [9 O][C] | dWtap4 [9 O][C].  SCALED (fp16): the per-tap gradients were contracted with G / s^2 and take
+// their 64 / 16 back here, in f32 (exact).
+template <bool SCALED>
 __global__ void conv2cls_fold_kernel(const float* __restrict__ dcomb, float* __restrict__ dw, int O, int C) {
     const int K = 4 * C;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -262,6 +279,7 @@ __global__ void conv2cls_fold_kernel(const float* __restrict__ dcomb, float* __r
     } else {
         const int member = c / C;
         g = dcomb[nm + (long)member * nt + ((long)t * O + o) * C + (c - member * C)];
+        if constexpr (SCALED) g *= member ? 16.f : 64.f;
     }
     dw[i] += g;
 }
@@ -269,9 +287,9 @@ __global__ void conv2cls_fold_kernel(const float* __restrict__ dcomb, float* __r
 // G[b, i, j, t * O + o] = sum of dy over the output pixels whose filter tap t = (r, s) reads the low-resolution pixel (i, j), from the
 // class sums P[b, i', j', k * O + o] of the neighbouring blocks.  Per axis (F / M / L = first / mid / last class of a block):
 //   r = 0:  M[i] + L[i] + F[i + 1]      r = 1:  F[i] + M[i] + L[i]      r = 2:  L[i - 1] + F[i] + M[i]
-// f32 sums in this fixed order, one rounding.  8 channels per thread.
+// f32 sums in this fixed order, one rounding (fp16: of the sum times gscale = 1 / s^2, from the f32 class sums).  4 channels per thread.
 template <typename T>
-__global__ void __launch_bounds__(256) conv2cls_tapsum_kernel(const T* __restrict__ pc, T* __restrict__ g, int B, int h, int w, int O) {
+__global__ void __launch_bounds__(256) conv2cls_tapsum_kernel(const typename PoolT<T>::type* __restrict__ pc, T* __restrict__ g, int B, int h, int w, int O, float gscale) {
     const int og = O / 4;
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long)B * h * w * 9 * og) return;
@@ -299,7 +317,7 @@ __global__ void __launch_bounds__(256) conv2cls_tapsum_kernel(const T* __restric
         for (int c = 0; c < 3; ++c) {
             const int jj = j + dj[c];
             if (jj < 0 || jj >= w) continue;
-            Vec8<T> v;
+            Vec8<typename PoolT<T>::type> v;
             v.load(pc + (((long)b * h + ii) * w + jj) * 9 * O + (long)(ci[a] * 3 + cj[c]) * O + gch * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) acc[e] += v.v[e];
@@ -307,7 +325,10 @@ __global__ void __launch_bounds__(256) conv2cls_tapsum_kernel(const T* __restric
     }
     Vec8<T> out;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) out.v[e] = acc[e];
+    for (int e = 0; e < 4; ++e) {
+        if constexpr (GScale<T>::on) out.v[e] = acc[e] * gscale;
+        else out.v[e] = acc[e];
+    }
     out.store(g + (((long)b * h + i) * w + j) * 9 * O + (long)t * O + gch * 4);
 }
 
@@ -347,21 +368,23 @@ extern "C" int mpn_conv2cls_pool(const void* dy, void* p8, void* p4, int B, int 
     MPN_CHECK_ARG(dy && p8 && p4 && B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && O > 0 && O % 8 == 0 && mpn_dtype_ok(dtype));
     const long n = (long)B * (H / 8) * (W / 8) * (O / 4) * 4;
     MPN_CHECK_ARG(n < 0x7fffffffL * 256L);
-    MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((conv2cls_pool_kernel<T>), dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (T*)p8, (T*)p4, B, H, W, O));
+    MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((conv2cls_pool_kernel<T>), dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)dy, (typename PoolT<T>::type*)p8, (typename PoolT<T>::type*)p4, B, H, W, O));
     return mpn_launch_status();
 }
 
-extern "C" int mpn_conv2cls_tapsum(const void* pc, void* g, int B, int h, int w, int O, int dtype, void* stream) {
-    MPN_CHECK_ARG(pc && g && B > 0 && h > 0 && w > 0 && O > 0 && O % 8 == 0 && mpn_dtype_ok(dtype));
+extern "C" int mpn_conv2cls_tapsum(const void* pc, void* g, int B, int h, int w, int O, int s, int dtype, void* stream) {
+    MPN_CHECK_ARG(pc && g && B > 0 && h > 0 && w > 0 && O > 0 && O % 8 == 0 && (s == 8 || s == 4) && mpn_dtype_ok(dtype));
+    const float gscale = 1.f / (float)(s * s);
     const long n = (long)B * h * w * 9 * (O / 4);
     MPN_CHECK_ARG(n < 0x7fffffffL * 256L);
-    MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((conv2cls_tapsum_kernel<T>), dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, (const T*)pc, (T*)g, B, h, w, O));
+    MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((conv2cls_tapsum_kernel<T>), dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, (const typename PoolT<T>::type*)pc, (T*)g, B, h, w, O, gscale));
     return mpn_launch_status();
 }
 
-extern "C" int mpn_conv2cls_fold(const float* dcomb, float* dw, int O, int C, void* stream) {
-    MPN_CHECK_ARG(dcomb && dw && O > 0 && C > 0);
+extern "C" int mpn_conv2cls_fold(const float* dcomb, float* dw, int O, int C, int dtype, void* stream) {
+    MPN_CHECK_ARG(dcomb && dw && O > 0 && C > 0 && mpn_dtype_ok(dtype));
     const long n = (long)O * 9 * 4 * C;
-    hipLaunchKernelGGL(conv2cls_fold_kernel, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, dcomb, dw, O, C);
+    if (dtype == MPN_F16) hipLaunchKernelGGL(conv2cls_fold_kernel<true>, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, dcomb, dw, O, C);
+    else hipLaunchKernelGGL(conv2cls_fold_kernel<false>, dim3(nblk(n, 256)), dim3(256), 0, (hipStream_t)stream, dcomb, dw, O, C);
     return mpn_launch_status();
 }

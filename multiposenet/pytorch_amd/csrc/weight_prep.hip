@@ -326,4 +326,4 @@ extern "C" int mpn_fill_f32(float* dst, float v, int64_t n, void* stream) {
     return mpn_launch_status();
 }
 
-extern "C" const char* mpn_version(void) { return "mpn-hip 0.2 (gfx950) src:" MPN_BUILD_ID; }
+extern "C" const char* mpn_version(void) { return "mpn-hip 0.3 (gfx950) src:" MPN_BUILD_ID; }

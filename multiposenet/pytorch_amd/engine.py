@@ -723,11 +723,12 @@ class Engine(object):
             # by the main stream a dozen launches later — ctx.cls_ev is recorded HERE, the main stream must not wait for the
             # weight gradients that follow in the same closure)
             p8, p4 = ops.conv2cls_pool(dy)
-            tap[:] = g8, g4t = ops.conv2cls_tapsum(p8), ops.conv2cls_tapsum(p4)
+            # (fp16: P in f32, G / s^2, and the s^2 back in the epilogue of the two launches below and in the fold — include/mpn.h)
+            tap[:] = g8, g4t = ops.conv2cls_tapsum(p8, 8, dy.t.dtype), ops.conv2cls_tapsum(p4, 4, dy.t.dtype)
             if g5 is not None:
-                ops.conv_forward(g8, wo.wtap_t[0], C, 1, 1, 1, 0, mode=1, out_hw=(q5.H, q5.W), cin=9 * O, out=g5)
+                ops.conv_forward(g8, wo.wtap_t[0], C, 1, 1, 1, 0, mode=1, out_hw=(q5.H, q5.W), cin=9 * O, out=g5, scale=wo.tap_unscale[0])
             if g4 is not None:
-                ops.conv_forward(g4t, wo.wtap_t[1], C, 1, 1, 1, 0, mode=1, out_hw=(q4.H, q4.W), cin=9 * O, out=g4)
+                ops.conv_forward(g4t, wo.wtap_t[1], C, 1, 1, 1, 0, mode=1, out_hw=(q4.H, q4.W), cin=9 * O, out=g4, scale=wo.tap_unscale[1])
             if g5 is not None or g4 is not None:
                 ctx.cls_ev = torch.cuda.Event()
                 gpu_op(ctx.cls_ev.record, ops.launch_stream(dev))
@@ -745,7 +746,7 @@ class Engine(object):
                 fused = ops.conv_wgrad(cat2, dy, dcomb[: wo.nm], O, 3, 3, 1, 1, db=db)
             ops.conv_wgrad(q5, g8, dcomb[wo.nm: wo.nm + wo.nt], 9 * O, 1, 1, 1, 0)
             ops.conv_wgrad(q4, g4t, dcomb[wo.nm + wo.nt:], 9 * O, 1, 1, 1, 0)
-            call("mpn_conv2cls_fold", ops.ptr(dcomb), ops.ptr(dw), O, C, ops.stream_ptr())
+            call("mpn_conv2cls_fold", ops.ptr(dcomb), ops.ptr(dw), O, C, ops.dtype_code(dy.t.dtype), ops.stream_ptr())
             ctx.side_keep.append((dcomb,))
             return fused
         self._param_grads(ctx, layer, (dy,), (srcs, dy, g5, g4, wo, cat2), wgrad, first=class_grads)

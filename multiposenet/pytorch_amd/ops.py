@@ -398,9 +398,24 @@ def conv2cls_supported(srcs, H, W):
     return [(a.H * f, a.W * f) for a, f in zip(srcs, (8, 4, 2, 1))] == [(H, W)] * 4
 
 
+_CONST_F32 = {}
+
+
+def _const_f32(dev, value, n):
+    """A constant f32 vector on ``dev``, filled once (on the launch stream of its first user) and kept for the life of the process."""
+    key = (str(dev), value, n)
+    t = _CONST_F32.get(key)
+    if t is None:
+        t = _CONST_F32[key] = torch.empty(n, dtype=torch.float32, device=dev)
+        call("mpn_fill_f32", ptr(t), value, n, stream_ptr())
+    return t
+
+
 class Conv2ClsOperands(object):
     """Per-forward operands of the class formulation, all derived from the f32 master filter [O][3][3][4 C] in four launches: the
-    combined filters (f32), their compute-dtype copies, and the transposed (input-gradient) copies when a backward pass will follow."""
+    combined filters (f32), their compute-dtype copies, and the transposed (input-gradient) copies when a backward pass will follow.
+    tap_unscale[m] (fp16 only, else None): the per-channel epilogue multiplier s^2 (s = 8, 4) of the tap input-gradient launch, which
+    contracts conv2cls_tapsum's G / s^2 there (include/mpn.h)."""
 
     def __init__(self, w_master, O, C, dtype, want_t):
         dev = w_master.device
@@ -419,7 +434,10 @@ class Conv2ClsOperands(object):
         self.wc = [self.comb[self.nm + m * self.nc: self.nm + (m + 1) * self.nc] for m in range(2)]      # [9 O][3][3][C], members q5 / q4
         self.wtap = [self.comb[nf + m * self.nt: nf + (m + 1) * self.nt] for m in range(2)]              # [9 O][C]: nine 1x1 filters
         self.wm_t = self.wtap_t = None
+        self.tap_unscale = [None, None]
         if want_t:
+            if dtype == torch.float16:
+                self.tap_unscale = [_const_f32(dev, 64.0, C), _const_f32(dev, 16.0, C)]
             self.wm_t = torch.empty((2 * C, 3, 3, O), dtype=dtype, device=dev)
             weight_transpose(comb32[: self.nm], self.wm_t, O, 9, 2 * C, O)
             self.wtap_t = []                                                    # [C][1][1][9 O]: the member as nine 1x1 convolutions, transposed
@@ -461,14 +479,21 @@ def conv2cls_expand(m8, m4, B, H, W, O, dtype):
     return e
 
 
+def pool_dtype(dtype):
+    """Storage type of the class sums of a dy of type ``dtype``: sums of up to 36 fp16 values do not fit fp16 (csrc/conv2cls.hip)."""
+    return torch.float32 if dtype == torch.float16 else dtype
+
+
 def conv2cls_pool(dy):
-    """(P8 [B, H/8, W/8, 9 O], P4 [B, H/4, W/4, 9 O]): per-class sums of dy over 8 x 8 / 4 x 4 blocks (one pass over dy)."""
+    """(P8 [B, H/8, W/8, 9 O], P4 [B, H/4, W/4, 9 O]): per-class sums of dy over 8 x 8 / 4 x 4 blocks (one pass over dy), in pool_dtype(dy's
+    type): f32 for an fp16 dy."""
     B, H, W = dy.B, dy.H, dy.W
     O = _cls_operand("conv2cls_pool", dy, _CLS_TYPES, 8, per_class=False)
     if H <= 0 or W <= 0 or H % 8 or W % 8:
         raise _lib.MpnError("conv2cls_pool: %d x %d is not a positive multiple of 8 x 8" % (H, W))
-    p8 = Act(torch.empty((B, H // 8, W // 8, 9 * O), dtype=dy.t.dtype, device=dy.t.device), 9 * O)
-    p4 = Act(torch.empty((B, H // 4, W // 4, 9 * O), dtype=dy.t.dtype, device=dy.t.device), 9 * O)
+    pt = pool_dtype(dy.t.dtype)
+    p8 = Act(torch.empty((B, H // 8, W // 8, 9 * O), dtype=pt, device=dy.t.device), 9 * O)
+    p4 = Act(torch.empty((B, H // 4, W // 4, 9 * O), dtype=pt, device=dy.t.device), 9 * O)
     call("mpn_conv2cls_pool", ptr(dy.t), ptr(p8.t), ptr(p4.t), B, H, W, O, dtype_code(dy.t.dtype), stream_ptr())
     return p8, p4
 
@@ -481,11 +506,20 @@ def conv2cls_classsum(t):
     return m
 
 
-def conv2cls_tapsum(pc):
-    """Class sums [B, h, w, 9 O] -> per-tap sums of the same shape (csrc/conv2cls.hip: conv2cls_tapsum_kernel)."""
-    O = _cls_operand("conv2cls_tapsum", pc, _CLS_TYPES, 8)
-    g = Act(torch.empty_like(pc.t), pc.C)
-    call("mpn_conv2cls_tapsum", ptr(pc.t), ptr(g.t), pc.B, pc.H, pc.W, O, dtype_code(pc.t.dtype), stream_ptr())
+def conv2cls_tapsum(pc, s=None, dtype=None):
+    """Class sums [B, h, w, 9 O] (conv2cls_pool's, of the member up-sampled by s = 8 or 4, for a dy of type ``dtype``; default: pc's own
+    type) -> per-tap sums of the same shape in ``dtype``; fp16: divided by s^2, so s must be given there (csrc/conv2cls.hip:
+    conv2cls_tapsum_kernel)."""
+    dtype = pc.t.dtype if dtype is None else dtype
+    if dtype not in _CLS_TYPES:
+        raise _lib.MpnError("conv2cls_tapsum: unsupported dtype %s" % dtype)
+    if s is None and dtype != torch.float16:
+        s = 8                                                                   # (nothing is scaled: either member's value does)
+    if s not in (8, 4):
+        raise _lib.MpnError("conv2cls_tapsum: the member is up-sampled by 8 or 4, not %r" % (s,))
+    O = _cls_operand("conv2cls_tapsum", pc, (pool_dtype(dtype),), 8)
+    g = Act(torch.empty(pc.t.shape, dtype=dtype, device=pc.t.device), pc.C)
+    call("mpn_conv2cls_tapsum", ptr(pc.t), ptr(g.t), pc.B, pc.H, pc.W, O, s, dtype_code(dtype), stream_ptr())
     return g
 
 

@@ -14,8 +14,19 @@ fp32 sum in the order asked for.  Bounds (u = 2^-24, helpers.check_elementwise t
     any fp32 summation of n terms, in any order or tree:   (n - 1) u sum |t|     (n - 1 additions, each off by at most u |partial|)
     + half a spacing of the output type where the result is stored in 16 bits
     elements with n <= 1 (combine, f32 expand: n <= 2, one correctly rounded add) must be bit-equal to the fp32 value
-The chain dy -> pool -> tapsum adds, as extra_abs, half a spacing of every stored P term that enters the element."""
+The chain dy -> pool -> tapsum adds, as extra_abs, half a spacing of every stored P term that enters the element.
+
+Storage contract of the backward (`pool_store`, `g_scale`; csrc/conv2cls.hip): bf16 / f32 store P and G in the compute type; fp16 stores P
+in f32 and G as G / s^2, and both consumers of G (the 1x1 input-gradient launch, fold) multiply by s^2 in f32 behind their contraction.
+
+The last section is conv2's WHOLE backward (`bwd_case`): a float64 reference per member from the definition — autograd of
+conv2d(cat(up8(q5), up4(q4), up2(q3), q2), W, pad 1) — on input sets that span the fp16 range, the structural per-element bound of the
+class route and of the plain route (`bwd_specs`), and fp32 models of both routes and of the faults the bound must reject (`class_model`)."""
+import functools
+import math
+
 import torch
+import torch.nn.functional as F
 
 from helpers import check_elementwise, report, rng_normal, ulp_out
 from stream_ref import exact, roundings
@@ -332,20 +343,43 @@ def tap_direct(dy, s):
     return S
 
 
+def pool_store(dtype):
+    """The type P is stored in: f32 for an fp16 backward (36 fp16 values of one sign pass 65504 from |dy| ~ 1820), else the type itself."""
+    return F32 if dtype == H16 else dtype
+
+
+def g_scale(dtype, s):
+    """The factor G_s is stored with: 1 / s^2 in fp16 (G_s sums up to s^2 dy: the mean is never above max |dy|), else 1."""
+    return 1.0 / (s * s) if dtype == H16 else 1.0
+
+
+def scaled(S, k):
+    """The Sum of k * terms, k a power of two (every part scales exactly)."""
+    T = Sum()
+    T.ref, T.mag, T.n, T.f32 = S.ref * k, S.mag * k, S.n, None if S.f32 is None else S.f32 * k
+    return T
+
+
 def chain_extra(P_stored, dtype):
     """Half a spacing of every stored P term that enters an element of G (the intermediate rounding of the chain)."""
     return reduce_terms(tapsum_terms(0.5 * ulp_out(P_stored.double(), dtype))).ref
 
 
 # ------------------------------------------------------------------------------------------------ fold
-def fold_ref(dcomb, dw0, O, C, mut=None):
+def fold_scale(dtype):
+    """What fold multiplies the two per-tap slices of dcomb by: 1 / g_scale (the launches that made them contracted G * g_scale)."""
+    return (1.0 / g_scale(dtype, 8), 1.0 / g_scale(dtype, 4))
+
+
+def fold_ref(dcomb, dw0, O, C, mut=None, scale=(1.0, 1.0)):
     """dw0 [O][9][4 C] + g in fp32 (one correctly rounded add), g from dcomb = dWm [O][9][2C] | dWtap8 [9][O][C] | dWtap4 [9][O][C]: the
-    gradient of row t * O + o of a per-tap set belongs to tap t of output channel o.  mut: 'tap_rows' | 'members' | 'assign'."""
+    gradient of row t * O + o of a per-tap set belongs to tap t of output channel o, times scale[member] (a power of two: exact in
+    fp32).  mut: 'tap_rows' | 'members' | 'assign'."""
     nm, _, nt = comb_sizes(O, C)
     g = torch.empty(O, 9, 4 * C, dtype=F32)
     g[..., 2 * C:] = dcomb[:nm].reshape(O, 9, 2 * C)
     for m in range(2):
-        src = dcomb[nm + m * nt: nm + (m + 1) * nt]
+        src = dcomb[nm + m * nt: nm + (m + 1) * nt] * scale[m]
         dst = (1 - m) if mut == "members" else m
         g[..., dst * C: (dst + 1) * C] = src.reshape(O, 9, C) if mut == "tap_rows" else src.reshape(9, O, C).permute(1, 0, 2)
     return g if mut == "assign" else dw0.reshape(O, 9, 4 * C) + g
@@ -447,3 +481,214 @@ def assert_decided(tag, S, alt64, out_dtype, plane=-2):
         dims = [i for i in range(d.dim()) if i != plane]
         assert bool((far.sum(dims) > 0)[touched.sum(dims) > 0].all()), "%s: a plane the alternative touches has no decided element" % tag
     return int(touched.sum()), int((touched & ~far).sum())
+
+
+# ================================================================================================ conv2's backward as a whole
+O2, C2 = 256, 128                                    # the production sizes (Engine.conv2cls_begin takes nothing else)
+U24 = 2.0 ** -24
+BWD_SHAPES = {             # (B, H, W)
+    "1x16x16": ((1, 16, 16), "two 8-blocks per axis: every block touches a border"),
+    "2x24x16": ((2, 24, 16), "an interior 8-block with both neighbours on one axis; pool runs 3072 threads = 12 full workgroups"),
+}
+BWD_SETS = {
+    "nominal": "unit normals, random signs",
+    "scaled1536": "dy = 1536 (1 + u / 4) sgn(o): G8 and the mid class of P8 pass 65504, G4 does not",
+    "scaled6144": "dy = 6144 (1 + u / 4) sgn(o), below 7680: G4 passes 65504 too",
+    "tiny": "|dy| in [2^-14, 2^-10], around fp16's smallest normal",
+}
+BWD_OUTPUTS = ("dq5", "dq4", "dW5", "dW4", "dWm", "db")          # what the GPU test compares
+BWD_STORED16 = ("dq5", "dq4", "dx32", "dq3", "dq2")              # what a 16-bit run stores in 16 bits (dx32: the q3 / q2 gradient at H x W)
+# log2 of the weight scale per (set, shape, type): the largest power of two for which every BWD_STORED16 reference stays below 2^15
+# (tests/test_conv2cls_parity_cpu.py::test_bwd_inputs_are_fair asserts that it is).  f32 runs nominal only, with bf16's scale.
+# In fp16 the tiny set stops where the weights themselves leave the type (2^14 x a 4-sigma normal > 65504), not at the outputs.
+BWD_WLOG2 = {
+    ("nominal", "1x16x16", "bf16"): 4, ("nominal", "1x16x16", "f16"): 4, ("nominal", "2x24x16", "bf16"): 4, ("nominal", "2x24x16", "f16"): 4,
+    ("scaled1536", "1x16x16", "bf16"): -9, ("scaled1536", "1x16x16", "f16"): -9, ("scaled1536", "2x24x16", "bf16"): -9, ("scaled1536", "2x24x16", "f16"): -9,
+    ("scaled6144", "1x16x16", "bf16"): -11, ("scaled6144", "1x16x16", "f16"): -11, ("scaled6144", "2x24x16", "bf16"): -11, ("scaled6144", "2x24x16", "f16"): -11,
+    ("tiny", "1x16x16", "bf16"): 15, ("tiny", "1x16x16", "f16"): 13, ("tiny", "2x24x16", "bf16"): 16, ("tiny", "2x24x16", "f16"): 13,
+}
+
+
+def bwd_dy(setname, seed, dtype, B, H, W):
+    g = torch.Generator().manual_seed(seed)
+    if setname == "nominal":
+        dy = torch.randn(B, H, W, O2, generator=g)
+    elif setname.startswith("scaled"):
+        u = (2.0 * torch.rand(B, H, W, O2, generator=g) - 1.0) * (1.0 - 2.0 ** -6)      # (so that bf16's rounding cannot reach 1.25 A)
+        sgn = torch.where(torch.arange(O2) % 2 == 0, 1.0, -1.0)
+        dy = float(setname[6:]) * (1.0 + u / 4.0) * sgn
+    else:
+        mag = torch.exp2(-14.0 + 4.0 * torch.rand(B, H, W, O2, generator=g)).clamp(2.0 ** -14, 2.0 ** -10)
+        dy = mag * torch.where(torch.rand(B, H, W, O2, generator=g) < 0.5, -1.0, 1.0)
+    return dy.to(dtype).float()
+
+
+def bwd_inputs(shape, setname, dtype, wlog2=None):
+    """q5 .. q2 (NHWC), W [O][3][3][4 C] and dy [B, H, W, O] as f32 tensors holding exactly the values the device reads (quantised
+    through the storage type; the weights AFTER their scale)."""
+    (B, H, W), _ = BWD_SHAPES[shape]
+    seed = 8000 + 100 * list(BWD_SHAPES).index(shape) + 10 * list(BWD_SETS).index(setname)
+    if wlog2 is None:
+        wlog2 = BWD_WLOG2[setname, shape, dn(BF if dtype == F32 else dtype)]
+    q = [qnormal(seed + 1 + m, dtype, B, H >> sh, W >> sh, C2) for m, sh in enumerate((3, 2, 1, 0))]
+    w = (rng_normal(seed + 5, O2, 3, 3, 4 * C2) * 2.0 ** wlog2).to(dtype).float()
+    return q, w, bwd_dy(setname, seed + 6, dtype, B, H, W)
+
+
+def _block_sum(t, s):
+    B, H, W, K = t.shape
+    return t.reshape(B, H // s, s, W // s, s, K).sum((2, 4))
+
+
+def conv2_bwd_f64(q, w, dy):
+    """Float64 autograd of sum(conv2d(cat(up8(q5), up4(q4), up2(q3), q2), W, pad 1) * dy).  -> dict: dq5 .. dq2 (NHWC at the member's
+    resolution), dx32 [B, H, W, 2 C] (the gradient of cat(up2(q3), q2)), dx [B, H, W, 4 C], dW5 / dW4 [O][3][3][C], dWm [O][3][3][2 C], db."""
+    qs = [t.double().permute(0, 3, 1, 2).contiguous().requires_grad_(True) for t in q]
+    wd = w.double().permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    x = torch.cat([F.interpolate(t, scale_factor=f, mode="nearest") if f > 1 else t for t, f in zip(qs, (8, 4, 2, 1))], 1)
+    x.retain_grad()
+    (F.conv2d(x, wd, padding=1) * dy.double().permute(0, 3, 1, 2)).sum().backward()
+    dw = wd.grad.permute(0, 2, 3, 1)
+    dx = x.grad.permute(0, 2, 3, 1)
+    out = {"dq%d" % (5 - m): qs[m].grad.permute(0, 2, 3, 1).contiguous() for m in range(4)}
+    out.update(dx=dx.contiguous(), dx32=dx[..., 2 * C2:].contiguous(), dW5=dw[..., :C2].contiguous(), dW4=dw[..., C2: 2 * C2].contiguous(),
+               dWm=dw[..., 2 * C2:].contiguous(), db=dy.double().sum((0, 1, 2)))
+    return out
+
+
+class BwdCase(object):
+    """Inputs, float64 reference and magnitudes (the same operation on absolute values) of one (shape, set, type)."""
+
+    def __init__(self, shape, setname, dtype, wlog2=None):
+        self.shape, self.set, self.dtype = shape, setname, dtype
+        (self.B, self.H, self.W), _ = BWD_SHAPES[shape]
+        self.q, self.w, self.dy = bwd_inputs(shape, setname, dtype, wlog2)
+        self.ref = conv2_bwd_f64(self.q, self.w, self.dy)
+        self._mag = None
+
+    @property
+    def mag(self):
+        if self._mag is None:
+            self._mag = conv2_bwd_f64([t.abs() for t in self.q], self.w.abs(), self.dy.abs())
+        return self._mag
+
+    def stored16_max(self):
+        return max(float(self.ref[k].abs().max()) for k in BWD_STORED16)
+
+
+@functools.lru_cache(maxsize=None)
+def bwd_case(shape, setname, dtype):
+    return BwdCase(shape, setname, dtype)
+
+
+def _slices(P):
+    """Split-K slices of a weight-gradient launch over P pixels: at most one per 512 pixels (mpn_conv_wgrad_chunks), each one more add."""
+    return max(1, -(-P // 512))
+
+
+def class_allowance(case, p_store, gs):
+    """Per member m (s = 8, 4): E [B, h, w, 9, O] = what the STORED intermediates may be off in an element of G_s — half a spacing (of the
+    storage type at that magnitude, subnormal-aware; nothing for f32) of every stored P term that enters it, plus half a spacing of
+    the stored G itself (stored as gs[s] G: the spacing of gs[s] |G|, divided by gs[s]).  Magnitudes are upper bounds of what the
+    device holds: |reference| + the fp32 summation error + the allowances already made."""
+    out = []
+    for s in (8, 4):
+        P = reduce_terms(pool_terms(case.dy, s))
+        p_up = P.ref.abs() + (P.n - 1).clamp(min=0).double() * U24 * P.mag
+        EP = reduce_terms(tapsum_terms(0.5 * ulp_out(p_up, p_store))).ref
+        G = tap_direct(case.dy, s)
+        g_up = G.ref.abs() + EP + (G.n - 1).clamp(min=0).double() * U24 * G.mag
+        out.append(EP + 0.5 * ulp_out(g_up * gs[s], case.dtype) / gs[s])
+    return out
+
+
+def bwd_specs(case, route, p_store=None, gs=None):
+    """name -> check_elementwise arguments (ref64, mag64, out_dtype, k_step, K, extra_terms, extra_abs, names) for every BWD_OUTPUTS
+    entry of the class route or the plain route.  Nothing fitted:
+      accumulation: the convolution launches at their real contraction length (K / k_step + k_step + 2 roundings on the magnitude;
+        k_step 32 for the 16-bit MFMA, 4 for the exact-fp32 one), + one per split-K slice of a weight gradient, + the s^2 - 1 fp32
+        additions of pool and tapsum behind an element of G (class route) or of the block sum of the up-sampled member's slice
+        (plain route);  db: P - 1 additions in any order;
+      stored intermediates: class route — `class_allowance` carried through |W| (input gradients) or |q| (filter gradients);
+        plain route — half a spacing of every stored element of the full-resolution input gradient in the block;
+      + half a spacing of the stored output (16-bit input gradients; the filter gradients are f32)."""
+    dt = case.dtype
+    ks = 4 if dt == F32 else 32
+    B, H, W = case.B, case.H, case.W
+    P = B * H * W
+    specs = {}
+    if route == "class":
+        p_store = pool_store(dt) if p_store is None else p_store
+        gs = {8: g_scale(dt, 8), 4: g_scale(dt, 4)} if gs is None else gs
+        E = class_allowance(case, p_store, gs)
+        for m, s in ((0, 8), (1, 4)):
+            wm = case.w[..., m * C2: (m + 1) * C2].double().abs().reshape(O2, 9, C2)
+            n = "%d" % (5 - m)
+            specs["dq" + n] = dict(out_dtype=dt, k_step=ks, K=9 * O2, extra_terms=s * s - 1, names="bhwc",
+                                   extra_abs=torch.einsum("bijto,otc->bijc", E[m], wm))
+            specs["dW" + n] = dict(out_dtype=F32, k_step=ks, K=P // (s * s), extra_terms=s * s - 1 + _slices(P // (s * s)), names="orsc",
+                                   extra_abs=torch.einsum("bijto,bijc->otc", E[m], case.q[m].double().abs()).reshape(O2, 3, 3, C2))
+    else:
+        dx_up = case.ref["dx"].abs() + (9 * O2 / float(ks) + ks + 2) * U24 * case.mag["dx"]
+        half = 0.5 * ulp_out(dx_up, dt)
+        for m, s in ((0, 8), (1, 4)):
+            n = "%d" % (5 - m)
+            specs["dq" + n] = dict(out_dtype=dt, k_step=ks, K=9 * O2, extra_terms=s * s - 1, names="bhwc",
+                                   extra_abs=_block_sum(half[..., m * C2: (m + 1) * C2], s))
+            specs["dW" + n] = dict(out_dtype=F32, k_step=ks, K=P, extra_terms=_slices(P), extra_abs=None, names="orsc")
+    specs["dWm"] = dict(out_dtype=F32, k_step=ks, K=P, extra_terms=_slices(P), extra_abs=None, names="orsc")
+    specs["db"] = dict(out_dtype=F32, k_step=1, K=P, extra_terms=_slices(P), extra_abs=None, names="o")
+    for k, v in specs.items():
+        v["ref64"], v["mag64"] = case.ref[k], case.mag[k]
+    return specs
+
+
+def check_bwd(tag, got, specs, route=""):
+    """Every BWD_OUTPUTS entry of `got` element by element (one report line each; an element that is not finite where the reference is
+    fails whatever the bound says: check_elementwise counts NaN and an infinite error as violations).  -> {name: worst err / bound}."""
+    worst = {}
+    for k in BWD_OUTPUTS:
+        g = got[k].detach().cpu()
+        assert bool(torch.isfinite(specs[k]["ref64"]).all())
+        worst[k] = check_elementwise("%s %s" % (tag, k), g, route=route, **specs[k])
+        assert bool(torch.isfinite(g.double()).all()), "%s %s: non-finite element" % (tag, k)
+    return worst
+
+
+def error_ratio(got_a, got_b, ref):
+    """Element-wise errors of two results against the same float64 reference: (rms a / rms b, max a / max b)."""
+    ea, eb = (got_a.double().cpu() - ref).abs(), (got_b.double().cpu() - ref).abs()
+    rms = lambda e: float(e.pow(2).mean().sqrt())
+    div = lambda a, b: a / b if b > 0 else (0.0 if a == 0 else float("inf"))
+    return div(rms(ea), rms(eb)), div(float(ea.max()), float(eb.max()))
+
+
+# fp32 models of the two routes.  `fault` (class route): None | 'parent' (P and G in the compute type, unscaled: what the kernels did
+# before P went to f32 in fp16) | 'dgrad' (the input-gradient launch without its s^2) | 'fold' (fold without its s^2) | 'swapped' (the
+# consumers take 16 for s = 8 and 64 for s = 4)
+BWD_FAULTS = ("parent", "dgrad", "fold", "swapped")
+
+
+def class_model(case, fault=None):
+    """The class route in fp32 under the storage contract: pool (quadrant tree) -> P stored -> tapsum (the kernel's order) times the G
+    factor -> G stored -> fp32 contractions -> the consumers' factors -> outputs rounded once."""
+    dt = case.dtype
+    ps = dt if fault == "parent" else pool_store(dt)
+    out = {}
+    for m, s, P in zip((0, 1), (8, 4), pool_tree(case.dy, F32)):
+        gk = 1.0 if fault == "parent" else g_scale(dt, s)
+        back = 1.0 / gk
+        if fault == "swapped" and gk != 1.0:
+            back = 1.0 / g_scale(dt, 12 - s)
+        G = (reduce_terms(tapsum_terms(P.to(ps).float())).f32 * gk).to(dt).float()
+        wm = case.w[..., m * C2: (m + 1) * C2].reshape(O2, 9, C2)
+        n = "%d" % (5 - m)
+        out["dq" + n] = (torch.einsum("bijto,otc->bijc", G, wm) * (1.0 if fault == "dgrad" else back)).to(dt)
+        out["dW" + n] = (torch.einsum("bijto,bijc->otc", G, case.q[m]) * (1.0 if fault == "fold" else back)).reshape(O2, 3, 3, C2)
+    out["dWm"], out["db"] = case.ref["dWm"].float(), case.ref["db"].float()      # (these two are plain launches in both routes)
+    return out
+
+
+def plain_model(case):
+    """The plain route as fp32 accumulation of W dy rounded once: the float64 reference through f32 into the output type."""
+    return {k: case.ref[k].float().to(case.dtype if k.startswith("dq") else F32) for k in BWD_OUTPUTS}

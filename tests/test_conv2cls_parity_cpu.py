@@ -8,7 +8,13 @@
 3. Generator conditions: where another class or neighbour would give a different value, it is further than the bound away
    (conv2cls_ref.assert_decided); the launch sizes are the stated ones; pool's one-pixel classes hold one pixel.
 4. The ops.conv2cls_* wrappers refuse a non-dense operand, a channel width the kernel would misread and a dtype the entry point rejects,
-   before they allocate anything."""
+   before they allocate anything.
+5. conv2's whole backward (conv2cls_ref.bwd_case; the GPU tier drives the engine's own composition against it): the input sets are fair
+   — the weight scale of every set is the largest power of two for which the float64 reference of everything a 16-bit run stores in
+   16 bits stays below 2^15, and an fp32-accumulate, round-once model of the plain route passes the bound with finite outputs — the
+   loss-scaled sets really take the unscaled 16-bit intermediates past 65504, the bound accepts the fp32 model of the class route
+   under the storage contract (fp16: P in f32, G / s^2, the s^2 back behind both contractions) and rejects the kernels' former
+   behaviour (inf on the loss-scaled sets), a compensation factor missing from either consumer, and swapped s = 8 / s = 4 factors."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -234,17 +240,21 @@ def test_pool_bound_accepts_fp32_models_and_rejects_faults(name, dtype):
         for S, s in ((S8, 8), (S4, 4)):
             assert torch.equal(S.f32[:, :, :, k], dy[:, a * (s - 1)::s, c * (s - 1)::s])
     tag = "pool %s %s " % (name, dn(dtype))
-    c8 = lambda t, g: R.check_sum(t, g, S8, dtype, "cpu")
-    c4 = lambda t, g: R.check_sum(t, g, S4, dtype, "cpu")
+    pt = R.pool_store(dtype)                                                     # fp16: P is stored in f32 — no output spacing to allow for
+    assert pt == (F32 if dtype == H16 else dtype)
+    c8 = lambda t, g: R.check_sum(t, g, S8, pt, "cpu")
+    c4 = lambda t, g: R.check_sum(t, g, S4, pt, "cpu")
     p8, p4 = R.pool_tree(dy, F32)
-    _accept(tag + "P8", c8, {"quadrant / shuffle tree": p8.to(dtype), "sequential": S8.f32.to(dtype)})
-    _accept(tag + "P4", c4, {"quadrant order": p4.to(dtype), "reversed": R.reduce_terms(R.pool_terms(dy, 4), order=REV9 + list(range(15, 8, -1))).f32.to(dtype)})
+    _accept(tag + "P8", c8, {"quadrant / shuffle tree": p8.to(pt), "sequential": S8.f32.to(pt)})
+    _accept(tag + "P4", c4, {"quadrant order": p4.to(pt), "reversed": R.reduce_terms(R.pool_terms(dy, 4), order=REV9 + list(range(15, 8, -1))).f32.to(pt)})
+    if dtype == H16:                                                             # ... so a P rounded to fp16 on the way is outside the bound
+        assert rejected(c8, "P8 through fp16", p8.to(H16).float()) and rejected(c4, "P4 through fp16", p4.to(H16).float())
     res = {}
     for m in MUTANTS["pool"]:
         a8, a4 = R.pool_tree(dy, F64, mut=m)
         assert torch.equal(a4, R.pool_tree(dy, F64)[1])                          # (all three faults live in the 8 x 8 part)
-        R.assert_decided(tag + "vs " + m, S8, a8, dtype)
-        res[m] = rejected(c8, "mutant", R.pool_tree(dy, F32, mut=m)[0].to(dtype))
+        R.assert_decided(tag + "vs " + m, S8, a8, pt)
+        res[m] = rejected(c8, "mutant", R.pool_tree(dy, F32, mut=m)[0].to(pt))
     _judge("pool", name, res)
 
 
@@ -252,18 +262,23 @@ def test_pool_bound_accepts_fp32_models_and_rejects_faults(name, dtype):
 @pytest.mark.parametrize("name", list(R.LOW_CASES))
 def test_tapsum_bound_accepts_fp32_models_and_rejects_faults(name, dtype):
     (B, h, w, O), _ = R.LOW_CASES[name]
-    P = R.low_input("tapsum", name, dtype)
-    S = R.reduce_terms(R.tapsum_terms(P))
-    chk = lambda t, g: R.check_sum(t, g, S, dtype, "cpu")
-    _accept("tapsum %s %s" % (name, dn(dtype)), chk,
-            {"the kernel's order": S.f32.to(dtype), "reversed": R.reduce_terms(R.tapsum_terms(P), order=REV9).f32.to(dtype)})
-    assert int(S.n.min()) >= 4 and int(S.n.max()) == 9                           # r = 1 / s = 1 read the block's own three classes; r = 0 at least M and L
-    res = {}
-    for m in MUTANTS["tapsum"]:
-        alt = R.reduce_terms(R.tapsum_terms(P, mut=m))
-        R.assert_decided("tapsum %s %s vs %s" % (name, dn(dtype), m), S, alt.ref, dtype)
-        res[m] = rejected(chk, "mutant", alt.f32.to(dtype))
-    _judge("tapsum", name, res)
+    P = R.low_input("tapsum", name, R.pool_store(dtype))                         # the values the kernel reads: f32 class sums in fp16
+    for s in ((8, 4) if dtype == H16 else (8,)):                                 # (the member's scale only matters where G is stored scaled)
+        k = R.g_scale(dtype, s)
+        assert k == (1.0 / (s * s) if dtype == H16 else 1.0)
+        S = R.scaled(R.reduce_terms(R.tapsum_terms(P)), k)                       # a scaled G is referenced as the scaled sum
+        chk = lambda t, g: R.check_sum(t, g, S, dtype, "cpu")
+        _accept("tapsum %s %s x %g" % (name, dn(dtype), k), chk,
+                {"the kernel's order": S.f32.to(dtype), "reversed": (R.reduce_terms(R.tapsum_terms(P), order=REV9).f32 * k).to(dtype)})
+        assert int(S.n.min()) >= 4 and int(S.n.max()) == 9                       # r = 1 / s = 1 read the block's own three classes; r = 0 at least M and L
+        if k != 1.0:                                                             # the unscaled sum, and the other member's factor, are outside
+            assert rejected(chk, "unscaled", (S.f32 / k).to(dtype)) and rejected(chk, "the other member's factor", (S.f32 / k * R.g_scale(dtype, 12 - s)).to(dtype))
+        res = {}
+        for m in MUTANTS["tapsum"]:
+            alt = R.scaled(R.reduce_terms(R.tapsum_terms(P, mut=m)), k)
+            R.assert_decided("tapsum %s %s vs %s" % (name, dn(dtype), m), S, alt.ref, dtype)
+            res[m] = rejected(chk, "mutant", alt.f32.to(dtype))
+        _judge("tapsum", name, res)
 
 
 @pytest.mark.parametrize("name", list(R.COMBINE_CASES))
@@ -276,6 +291,16 @@ def test_fold_reference_rejects_faults(name):
     g64 = ref.double() - dw0.reshape(O, 9, 4 * C).double()
     assert float((g64.abs() - g64.abs().round()).abs().max()) <= 2.0 ** -24 * float(ref.abs().max())
     _judge("fold", name, {m: not torch.equal(R.fold_ref(dcomb, dw0, O, C, mut=m), ref) for m in MUTANTS["fold"]})
+    # fp16: the per-tap slices come back times 64 / 16 (exact: the ramp stays below 2^30 with 24 significant bits); a factor missing
+    # from fold, or the two swapped, moves every element of those slices
+    assert R.fold_scale(H16) == (64.0, 16.0) and R.fold_scale(BF) == R.fold_scale(F32) == (1.0, 1.0)
+    ref16 = R.fold_ref(dcomb, dw0, O, C, scale=R.fold_scale(H16))
+    g16 = ref16.double() - dw0.reshape(O, 9, 4 * C).double()
+    assert torch.equal(ref16[..., 2 * C:], ref[..., 2 * C:])
+    for m, k in ((0, 64.0), (1, 16.0)):
+        assert float(((g16 - k * g64)[..., m * C: (m + 1) * C].abs() / (k * g64[..., m * C: (m + 1) * C].abs())).max()) <= 2.0 ** -23
+    for wrong in ((1.0, 1.0), (16.0, 64.0)):
+        assert bool((R.fold_ref(dcomb, dw0, O, C, scale=wrong) != ref16)[..., : 2 * C].all())
     for m in ("tap_rows", "members"):                                            # an index fault moves (nearly) every element it can
         moved = (R.fold_ref(dcomb, dw0, O, C, mut=m) != ref)[..., : 2 * C]
         assert float(moved.double().mean()) > 0.7, (m, float(moved.double().mean()))
@@ -284,17 +309,19 @@ def test_fold_reference_rejects_faults(name):
 @pytest.mark.parametrize("dtype", TYPES, ids=dn)
 @pytest.mark.parametrize("name", list(R.CHAIN_CASES))
 def test_chain_bound_accepts_the_fp32_model(name, dtype):
-    """dy -> pool -> (stored in dtype) -> tapsum against G straight from dy: the bound holds for the fp32 model of both kernels, and is
-    missed by a chain whose pool is faulty."""
+    """dy -> pool -> (stored in pool_store(dtype)) -> tapsum (times g_scale) against G straight from dy: the bound holds for the fp32 model
+    of both kernels, and is missed by a chain whose pool is faulty."""
     (B, H, W, O), _ = R.CHAIN_CASES[name]
     dy = R.pool_input("chain", name, dtype)
+    pt = R.pool_store(dtype)
     for mut, want_reject in ((None, False), ("one_step", True), ("mid_rows", True)):
         p8, p4 = R.pool_tree(dy, F32, mut=mut)
         for s, P in ((8, p8), (4, p4)):
-            Pst = P.to(dtype).float()
-            G = R.reduce_terms(R.tapsum_terms(Pst)).f32.to(dtype)
-            D = R.tap_direct(dy, s)
-            chk = lambda: R.check_sum("chain %s %s G%d [fp32 model]" % (name, dn(dtype), s), G, D, dtype, "cpu", exact_n=-1, extra_abs=R.chain_extra(Pst, dtype))
+            k = R.g_scale(dtype, s)
+            Pst = P.to(pt).float()
+            G = (R.reduce_terms(R.tapsum_terms(Pst)).f32 * k).to(dtype)
+            D = R.scaled(R.tap_direct(dy, s), k)
+            chk = lambda: R.check_sum("chain %s %s G%d [fp32 model]" % (name, dn(dtype), s), G, D, dtype, "cpu", exact_n=-1, extra_abs=k * R.chain_extra(Pst, pt))
             if mut is None:
                 chk()
             elif s == 8:
@@ -334,25 +361,119 @@ def test_wrappers_refuse_what_the_kernels_would_misread(ops_noalloc):
     for t in (wide, perm):
         assert not t.is_contiguous()
         bad(ops.conv2cls_classsum, A(t, 72))
-        bad(ops.conv2cls_tapsum, A(t, 72))
+        bad(ops.conv2cls_tapsum, A(t, 72), 8, F32)
     bad(ops.conv2cls_pool, A(torch.zeros(1, 8, 8, 16)[..., :8], 8))
     bad(ops.conv2cls_expand, A(wide, 72), A(torch.zeros(1, 4, 4, 72), 72), 1, 16, 16, 8, torch.float32)
     # widths the kernel would misread
     bad(ops.conv2cls_classsum, A(torch.zeros(1, 2, 2, 64), 64))                 # not 9 planes
     bad(ops.conv2cls_classsum, A(torch.zeros(1, 2, 2, 54), 54))                 # O = 6: no multiple of 4
-    bad(ops.conv2cls_tapsum, A(torch.zeros(1, 2, 2, 64), 64))
-    bad(ops.conv2cls_tapsum, A(torch.zeros(1, 2, 2, 36), 36))                   # O = 4: tapsum's entry point needs O % 8
+    bad(ops.conv2cls_tapsum, A(torch.zeros(1, 2, 2, 64), 64), 8, F32)
+    bad(ops.conv2cls_tapsum, A(torch.zeros(1, 2, 2, 36), 36), 8, F32)           # O = 4: tapsum's entry point needs O % 8
+    bad(ops.conv2cls_tapsum, A(dense, 72), 2, F32)                               # the member's scale is 8 or 4
     bad(ops.conv2cls_pool, A(torch.zeros(1, 8, 8, 12), 12))                     # O % 8
     bad(ops.conv2cls_pool, A(torch.zeros(1, 8, 12, 8), 8))                      # W % 8
     bad(ops.conv2cls_expand, A(dense, 72), A(torch.zeros(1, 4, 4, 72), 72), 1, 16, 16, 16, torch.float32)      # O is not Cs / 9
     bad(ops.conv2cls_expand, A(dense, 72), A(torch.zeros(1, 2, 2, 72), 72), 1, 16, 16, 8, torch.float32)       # m4 at the wrong resolution
     # dtypes the entry points reject
     bad(ops.conv2cls_classsum, A(dense.to(BF), 72))                              # classsum is f32 only
-    bad(ops.conv2cls_tapsum, A(dense.double(), 72))
+    bad(ops.conv2cls_tapsum, A(dense.double(), 72), 8, F64)
+    bad(ops.conv2cls_tapsum, A(dense.to(H16), 72), 8, H16)                       # fp16's class sums are f32 (conv2cls_pool writes them so)
+    bad(ops.conv2cls_tapsum, A(dense, 72), 4, BF)                                # bf16's are bf16
     bad(ops.conv2cls_pool, A(torch.zeros(1, 8, 8, 8, dtype=F64), 8))
     bad(ops.conv2cls_expand, A(dense.to(H16), 72), A(torch.zeros(1, 4, 4, 72), 72), 1, 16, 16, 8, torch.float32)   # class maps are f32
     bad(ops.conv2cls_expand, A(dense, 72), A(torch.zeros(1, 4, 4, 72), 72), 1, 16, 16, 8, F64)
     # a well-formed operand passes the checks and reaches the allocation
-    for fn, a in ((ops.conv2cls_classsum, A(dense, 72)), (ops.conv2cls_tapsum, A(dense.to(BF), 72)), (ops.conv2cls_pool, A(torch.zeros(1, 8, 8, 8), 8))):
+    for fn, a in ((ops.conv2cls_classsum, (A(dense, 72),)), (ops.conv2cls_tapsum, (A(dense.to(BF), 72), 8, BF)), (ops.conv2cls_tapsum, (A(dense, 72), 4, H16)),
+                  (ops.conv2cls_pool, (A(torch.zeros(1, 8, 8, 8), 8),)), (ops.conv2cls_pool, (A(torch.zeros(1, 8, 8, 8, dtype=H16), 8),))):
         with pytest.raises(RuntimeError, match="allocated"):
-            fn(a)
+            fn(*a)
+
+
+# ====================================================================================================== 5. conv2's whole backward
+BWD_CASES = [(sh, st, dt) for dt in TYPES for sh in R.BWD_SHAPES for st in R.BWD_SETS if dt != F32 or st == "nominal"]
+BWD_IDS = ["%s-%s-%s" % (dn(dt), st, sh) for sh, st, dt in BWD_CASES]
+
+
+def test_bwd_reference_is_the_definition():
+    """conv2cls_ref.conv2_bwd_f64 against the explicit transposed sums, and the class formulation against it: the member's input gradient
+    is the block sum of the full-resolution one, sum_t G_t W_t is that block sum, sum_pixels G_t q is the member's filter gradient."""
+    c = R.bwd_case("1x16x16", "nominal", BF)
+    dy, w = c.dy.double().permute(0, 3, 1, 2), c.w.double().permute(0, 3, 1, 2)
+    close(F.conv_transpose2d(dy, w, padding=1).permute(0, 2, 3, 1), c.ref["dx"], 1e-12)
+    x = torch.cat([up(t.double().permute(0, 3, 1, 2), f) if f > 1 else t.double().permute(0, 3, 1, 2) for t, f in zip(c.q, (8, 4, 2, 1))], 1)
+    dw = torch.nn.grad.conv2d_weight(x, w.shape, dy, padding=1).permute(0, 2, 3, 1)
+    close(dw, torch.cat([c.ref["dW5"], c.ref["dW4"], c.ref["dWm"]], 3), 1e-12)
+    for m, s in ((0, 8), (1, 4)):
+        n = "%d" % (5 - m)
+        close(R._block_sum(c.ref["dx"][..., m * 128: (m + 1) * 128], s), c.ref["dq" + n], 1e-12)
+        G = R.tap_direct(c.dy, s).ref
+        close(torch.einsum("bijto,otc->bijc", G, c.w[..., m * 128: (m + 1) * 128].double().reshape(256, 9, 128)), c.ref["dq" + n], 1e-12)
+        close(torch.einsum("bijto,bijc->otc", G, c.q[m].double()).reshape(256, 3, 3, 128), c.ref["dW" + n], 1e-12)
+    close(R._block_sum(c.ref["dx32"][..., :128], 2), c.ref["dq3"], 1e-12)
+    assert torch.equal(c.ref["dx32"][..., 128:], c.ref["dq2"])
+
+
+@pytest.mark.parametrize("shape,setname,dtype", [c for c in BWD_CASES if c[2] != F32], ids=[i for i, c in zip(BWD_IDS, BWD_CASES) if c[2] != F32])
+def test_bwd_inputs_are_fair(shape, setname, dtype):
+    """The inputs are the stated ones (quantised through the storage type, the stated ranges), the weight scale is the LARGEST power of
+    two that keeps every reference of a 16-bit stored output below 2^15 (one more doubling does not: an output reaches 2^15, or — the
+    tiny set in fp16 — the weights themselves leave the type), and the round-once model of the plain route passes the plain bound,
+    finite.  So whatever fails on these inputs is the class route's own doing."""
+    c = R.bwd_case(shape, setname, dtype)
+    for t in c.q + [c.w, c.dy]:
+        assert torch.equal(t, t.to(dtype).float()) and bool(torch.isfinite(t).all())
+    a = c.dy.abs()
+    if setname.startswith("scaled"):
+        A = float(setname[6:])
+        sgn = torch.where(torch.arange(256) % 2 == 0, 1.0, -1.0)
+        assert bool((c.dy * sgn > 0).all()) and 0.75 * A <= float(a.min()) and float(a.max()) < 1.25 * A <= 7680
+    elif setname == "tiny":
+        assert 2.0 ** -14 <= float(a.min()) and float(a.max()) <= 2.0 ** -10 and 0.4 < float((c.dy > 0).double().mean()) < 0.6
+    top = c.stored16_max()
+    assert top < 2.0 ** 15, top
+    k = R.BWD_WLOG2[setname, shape, dn(dtype)]
+    q, w2, dy = R.bwd_inputs(shape, setname, dtype, wlog2=k + 1)
+    if bool(torch.isfinite(w2).all()):
+        r2 = R.conv2_bwd_f64(q, w2, dy)
+        assert max(float(r2[n].abs().max()) for n in R.BWD_STORED16) >= 2.0 ** 15
+    else:
+        assert dtype == H16 and setname == "tiny"
+    got = R.plain_model(c)
+    assert all(bool(torch.isfinite(v).all()) for v in got.values())
+    R.check_bwd("conv2 bwd %s %s %s [round-once model of the plain route]" % (shape, setname, dn(dtype)), got, R.bwd_specs(c, "plain"), "cpu")
+
+
+@pytest.mark.parametrize("shape", list(R.BWD_SHAPES))
+def test_bwd_loss_scaled_sets_pass_fp16_where_stated(shape):
+    """What each amplitude is for: at 1536 the unscaled G8 (64 dy) passes 65504 while G4 and both P do not (the mid class of P8, 36 dy
+    of mean 1536, reaches 6.0e4: it passes from |dy| ~ 1820); at 6144 G4 and the mid class of P8 pass as well (P4's mid class of four
+    pixels cannot); G / s^2 and dy itself stay inside the type."""
+    top = {}
+    for st in ("scaled1536", "scaled6144"):
+        c = R.bwd_case(shape, st, H16)
+        for s in (8, 4):
+            top[st, "P", s] = float(R.reduce_terms(R.pool_terms(c.dy, s)).ref.abs().max())
+            top[st, "G", s] = float(R.tap_direct(c.dy, s).ref.abs().max())
+        assert float(c.dy.abs().max()) < 7680 and top[st, "G", 8] / 64 < 7680 and top[st, "G", 4] / 16 < 7680
+    assert top["scaled1536", "G", 8] > 65504 > max(top["scaled1536", "P", 8], top["scaled1536", "G", 4], top["scaled1536", "P", 4])
+    assert min(top["scaled6144", "G", 8], top["scaled6144", "G", 4], top["scaled6144", "P", 8]) > 65504 > top["scaled6144", "P", 4]
+
+
+@pytest.mark.parametrize("shape,setname,dtype", BWD_CASES, ids=BWD_IDS)
+def test_bwd_bound_accepts_the_fp32_model_and_rejects_faults(shape, setname, dtype):
+    c = R.bwd_case(shape, setname, dtype)
+    specs = R.bwd_specs(c, "class")
+    tag = "conv2 bwd %s %s %s " % (shape, setname, dn(dtype))
+    R.check_bwd(tag + "[fp32 model of the class route]", R.class_model(c), specs, "cpu")
+    if dtype != H16:
+        # nothing is scaled outside fp16: the faulty contracts are the contract itself
+        for f in R.BWD_FAULTS:
+            m, g = R.class_model(c, f), R.class_model(c)
+            assert all(torch.equal(m[k], g[k]) for k in R.BWD_OUTPUTS), f
+        return
+    for f in R.BWD_FAULTS:
+        got = R.class_model(c, f)
+        assert rejected(R.check_bwd, tag + f, got, specs, "cpu"), "%s not rejected" % f
+        if f == "parent" and setname.startswith("scaled"):
+            bad = [k for k in R.BWD_OUTPUTS if not bool(torch.isfinite(got[k]).all())]
+            assert bad == (["dq5", "dW5"] if setname == "scaled1536" else ["dq5", "dq4", "dW5", "dW4"]), bad
