@@ -305,6 +305,25 @@ int mpn_mse_heatmap_backward(const float* const* preds, float* const* dpreds, co
                              const int64_t* dpred_sP, const int32_t* pred_C, const float* gt, const float* wgt,
                              int64_t npix, const float* gscale, void* stream);
 int mpn_mse_chunks(int64_t npix);
+/* The two calls above with the person-segmentation term (the K + 1st output channel of the keypoint subnet): mask is the
+ * mask_all target, dense f32 [B,h,w] in [0, 1]; pred_C[j] the live channels of prediction j (18 or more).  For every level j
+ * with a nineteenth channel (pred_C[j] >= 19)
+ *   seg_j = mean over pixels of (pred_j[p, 18] - mask[p])^2 / 100,
+ * not weighted by wgt; total = heat-map total + sum_j seg_j.  out f32 [MPN_MSE_SEG_OUT]: [0..7] exactly what
+ * mpn_mse_heatmap_forward writes (the same two launches); [8..12] seg_j (0 for a level without the channel); [13] their sum;
+ * [14], [15] max / min of channel 18 of the final prediction (0 when it has 18 channels); [16] the total; the rest 0.
+ * seg_partial needs seg_chunks * 8 floats, seg_chunks = mpn_mse_seg_chunks(npix).
+ * Backward: channels < 18 as mpn_mse_heatmap_backward, bit for bit; dpred_j[p, 18] = gscale * 2 * (pred - mask) / (100 * npix)
+ * where pred_C[j] >= 19; channels above 18 are 0.  MPN_E_BADARG before any HIP call: a null or misaligned pointer (dpreds[j] and
+ * gscale may be null), npix outside 1..2^31 - 1, a chunk count that is not the function's, pred_C[j] < 18 or above its stride. */
+#define MPN_MSE_SEG_OUT 20
+int mpn_mse_seg_chunks(int64_t npix);
+int mpn_mse_heatmap_seg_forward(const float* const* preds, const int64_t* pred_sP, const int32_t* pred_C, const float* gt,
+                                const float* wgt, const float* mask, int64_t npix, float* partial, int chunks, float* seg_partial,
+                                int seg_chunks, float* out, void* stream);
+int mpn_mse_heatmap_seg_backward(const float* const* preds, float* const* dpreds, const int64_t* pred_sP, const int64_t* dpred_sP,
+                                 const int32_t* pred_C, const float* gt, const float* wgt, const float* mask, int64_t npix,
+                                 const float* gscale, void* stream);
 /* The recorded training step's form of the two calls above (replay.py): loss and gradients in ONE pass over the network's
  * internal tensors, with no exported f32 copies.  levels[0..3] = the intermediate maps k2..k5 (f32, [B, H>>s, W>>s, 32], s = 0..3:
  * posenet.py:243-257 up-samples them by nearest neighbours to the heat-map size, so pixel (y, x) reads level s at (y>>s, x>>s) and
@@ -317,6 +336,18 @@ int mpn_mse_train_blocks(int B, int H, int W);
 int mpn_mse_heatmap_train(const float* const* levels, void* const* dlevels, const int32_t* level_Cs, int dtype,
                           const float* gt, const float* wgt, int64_t g_sB, int64_t g_sC, int64_t g_sH,
                           int B, int H, int W, const float* gscale, float* partial, int blocks, float* out, void* stream);
+/* mpn_mse_heatmap_train with the person-segmentation term, for a recorded step with mask_all: the same launch in its seg-aware
+ * instantiation.  level_C[j] (18 .. 32) are the live channels of level j; on every level with a nineteenth channel lane 18 is live
+ * with w = 1, g = mask (f32 [B][1][H][W] dense, 16-byte aligned, read in place with 16-byte loads) and the scale
+ * 2 gscale / (100 B H W); it takes the same 8x8 cell walk, so dlevels[j][.., 18] is bit-identical to
+ * mpn_mse_heatmap_seg_backward + mpn_import_grad, and lanes 0..17 to mpn_mse_heatmap_train's.  A level without the channel keeps
+ * the zero in lane 18 and is not read there.  out f32 [MPN_MSE_SEG_OUT] as for mpn_mse_heatmap_seg_forward (its two finalize
+ * launches); partial needs blocks * 16 floats.  MPN_E_BADARG before any HIP call as for mpn_mse_heatmap_train, and for a null or
+ * misaligned mask, level_C outside 18..32, a dtype that is none of the three. */
+int mpn_mse_heatmap_seg_train(const float* const* levels, void* const* dlevels, const int32_t* level_Cs, const int32_t* level_C,
+                              int dtype, const float* gt, const float* wgt, const float* mask, int64_t g_sB, int64_t g_sC,
+                              int64_t g_sH, int B, int H, int W, const float* gscale, float* partial, int blocks, float* out,
+                              void* stream);
 /* focal + smooth-L1.  cls [B,A] f32 (post-sigmoid), reg [B,A,4], anchors [A,4], anno [B,maxN,5].
  * out[0] = cls loss, out[1] = reg loss (batch means).  per_img [B][4] scratch. */
 int mpn_focal_blocks(int A);   /* partial needs B * mpn_focal_blocks(A) * 4 floats */
@@ -501,6 +532,11 @@ int mpn_copy_bytes(void* dst, const void* src, int64_t nbytes, void* stream);
  * mpn_focal_forward (or NULL); logv[0..7] = kp8, [8] = cls + reg, [9] = cls, [10] = reg, [11] = loss (the sums the reference
  * forms with torch adds at posenet.py:387,421 and the combined step of SURVEY.md 8d) */
 int mpn_step_log(const float* kp8, const float* det2, float* logv, void* stream);
+/* mpn_step_log for a step with the person-segmentation term: kp is the MPN_MSE_SEG_OUT vector of mpn_mse_heatmap_seg_forward
+ * (required), logv f32 [MPN_STEP_LOG_SEG]: [0..12] keep mpn_step_log's meaning with [11] = kp[16] + the detection total ([12] is the
+ * gradient clip's), [13..17] the seg means, [18] their sum, [19] / [20] max / min of channel 18 of the final prediction. */
+#define MPN_STEP_LOG_SEG 21
+int mpn_step_log_seg(const float* kp, const float* det2, float* logv, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * conv2 of the keypoint head by position classes (network/posenet.py:311-315: conv2 over cat(up8(q5), up4(q4), up2(q3), q2)).
@@ -570,6 +606,12 @@ int mpn_augment_image(const uint8_t* src, int64_t src_bytes, const double* table
                       const float* mean_std, void* stream);
 int mpn_augment_mask(const uint8_t* src, int64_t src_bytes, const double* table, int B, float* out, int gh, int gw, int stride,
                      int crop_x, void* stream);
+/* mpn_augment_plane: mpn_augment_mask's sampling (the same table row with its MASK columns, the same mapping, the same single
+ *   4x4 cubic sample, clamp and / 255) of ANY uint8 plane, with an explicit value outside the canvas or the scaled image
+ *   (`outside`, in 0 .. 255, divided by 255 like a sample) and ONE output channel: out f32 [B][1][gh][gw].  For mask_all the
+ *   outside value is 0: nobody stands outside the image.                                                                    */
+int mpn_augment_plane(const uint8_t* src, int64_t src_bytes, const double* table, int B, float* out, int gh, int gw, int stride,
+                      int crop_x, float outside, void* stream);
 
 /* Boxes of the instance masks of a detection batch (ImageAugmentation.py:234-340 aug_*_bbox on the masks,
  * COCO_data_pipeline.py:382-405 get_ground_truth, :444-458 bbox_collater) without any warped mask.
@@ -678,6 +720,19 @@ int mpn_segm_mask_miss(const int64_t* imgs, int n_img, const int64_t* insts, con
                        int n_parts, const int32_t* verts, const int32_t* vpart, const int32_t* estart, int n_verts, int64_t n_steps,
                        const int32_t* toggles, int n_tog, int max_w, int max_h, uint8_t* out, int64_t out_bytes, void* workspace,
                        int64_t ws_bytes, void* stream);
+
+/* mask_miss AND mask_all of n_img images from the same tables, toggle launches and ONE compose launch (the compose kernel's
+ * second instantiation).  mask_all is the target of the keypoint subnet's person-segmentation channel: 255 where ANY of the
+ * image's person annotations covers the pixel (KEYPOINTS, NO_KEYPOINTS and CROWD alike: a plain union, independent of the
+ * order), else 0; an image without instances is all 0.  Every listed instance counts, so the caller must not drop the
+ * KEYPOINTS instances that cannot change mask_miss.
+ * out_miss, out_all: two buffers of out_bytes each; image b's planes lie at the SAME MPN_SEGM_OUT_OFF / MPN_SEGM_OUT_PITCH of
+ *   both, validated alike.  out_miss holds the bytes mpn_segm_mask_miss writes for the same arguments.
+ * MPN_E_BADARG before any HIP call: as for mpn_segm_mask_miss, and out_all null or closer than out_bytes to out_miss.                       */
+int mpn_segm_person_masks(const int64_t* imgs, int n_img, const int64_t* insts, const int32_t* kind, int n_inst, const int64_t* parts,
+                          int n_parts, const int32_t* verts, const int32_t* vpart, const int32_t* estart, int n_verts, int64_t n_steps,
+                          const int32_t* toggles, int n_tog, int max_w, int max_h, uint8_t* out_miss, uint8_t* out_all,
+                          int64_t out_bytes, void* workspace, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * PRN training pairs from raw COCO annotations (datasets/coco_data/prn_data_pipeline.py:33-111), one launch per batch.

@@ -83,6 +83,8 @@ SIGNATURES = {
     "mpn_segm_workspace_bytes": (_i64, [_i64]),
     "mpn_segm_rasterize": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _i64, _i, _vp, _vp, _i64, _vp]),
     "mpn_segm_mask_miss": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _i64, _vp, _i64, _vp]),
+    "mpn_segm_person_masks": (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i64, _vp, _i, _i, _i, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "mpn_augment_plane": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i, _i, _i, _f, _vp]),
     "mpn_prn_train_maps": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mpn_heatmap_peaks_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
     "mpn_heatmap_peaks": (_i, [_vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _f, ctypes.c_double, _i, _vp, _vp, _i, _vp, _vp]),
@@ -142,7 +144,11 @@ SIGNATURES = {
     "mpn_mse_chunks": (_i, [_i64]),
     "mpn_mse_heatmap_forward": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i, _vp, _vp]),
     "mpn_mse_heatmap_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "mpn_mse_seg_chunks": (_i, [_i64]),
+    "mpn_mse_heatmap_seg_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _vp, _i, _vp, _vp]),
+    "mpn_mse_heatmap_seg_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "mpn_mse_train_blocks": (_i, [_i, _i, _i]),
+    "mpn_mse_heatmap_seg_train": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "mpn_mse_heatmap_train": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "mpn_focal_blocks": (_i, [_i]),
     "mpn_focal_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -194,6 +200,7 @@ SIGNATURES = {
     "mpn_fill_f32": (_i, [_vp, _f, _i64, _vp]),
     "mpn_copy_bytes": (_i, [_vp, _vp, _i64, _vp]),
     "mpn_step_log": (_i, [_vp, _vp, _vp, _vp]),
+    "mpn_step_log_seg": (_i, [_vp, _vp, _vp, _vp]),
     "mpn_conv2cls_comb_elems": (_i64, [_i, _i]),
     "mpn_conv2cls_combine": (_i, [_vp, _vp, _i, _i, _vp]),
     "mpn_conv2cls_expand": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -213,7 +220,7 @@ SIGNATURES = {
 
 # entry points that return a count, not a status
 _COUNT_FUNCS = {"mpn_conv_stats_tiles", "mpn_conv_kernel_name", "mpn_conv_wgrad_chunks", "mpn_conv_wgrad_seg_plan", "mpn_conv_wgrad_kernel_id", "mpn_conv_wgrad_kernel_name", "mpn_bn_bwd_chunks", "mpn_channel_sum_chunks",
-                "mpn_mse_chunks", "mpn_mse_train_blocks", "mpn_focal_blocks", "mpn_focal_mc_blocks", "mpn_bce_chunks", "mpn_nms_workspace_bytes", "mpn_nms_batched_workspace_bytes", "mpn_class_filter_chunk", "mpn_class_filter_workspace_bytes", "mpn_nms_batched_classes_workspace_bytes", "mpn_heatmap_peaks_workspace_bytes", "mpn_augment_boxes_workspace_bytes", "mpn_segm_workspace_bytes", "mpn_conv2cls_comb_elems", "mpn_grad_absmax_workspace_bytes", "mpn_oks_eval_workspace_bytes", "mpn_box_eval_workspace_bytes", "mpn_version"}
+                "mpn_mse_chunks", "mpn_mse_seg_chunks", "mpn_mse_train_blocks", "mpn_focal_blocks", "mpn_focal_mc_blocks", "mpn_bce_chunks", "mpn_nms_workspace_bytes", "mpn_nms_batched_workspace_bytes", "mpn_class_filter_chunk", "mpn_class_filter_workspace_bytes", "mpn_nms_batched_classes_workspace_bytes", "mpn_heatmap_peaks_workspace_bytes", "mpn_augment_boxes_workspace_bytes", "mpn_segm_workspace_bytes", "mpn_conv2cls_comb_elems", "mpn_grad_absmax_workspace_bytes", "mpn_oks_eval_workspace_bytes", "mpn_box_eval_workspace_bytes", "mpn_version"}
 
 _lib = None
 

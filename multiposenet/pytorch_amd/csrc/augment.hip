@@ -146,13 +146,17 @@ __global__ void __launch_bounds__(256) augment_image_kernel(const uint8_t* __res
     for (int c = 0; c < 3; ++c) o[c * plane] = (bgr[2 - c] / 255.0f - nm.mean[c]) / nm.stdv[c];
 }
 
+// CH output channels, all holding the one sample: 18 for mask_miss (mpn_augment_mask, outside = 255), 1 for any other plane
+// (mpn_augment_plane, the outside value of the caller's).
+template <int CH>
 __global__ void __launch_bounds__(256) augment_mask_kernel(const uint8_t* __restrict__ src, long src_bytes, const double* __restrict__ table,
-                                                           float* __restrict__ out, int gh, int gw, double stride, double flip_w) {
+                                                           float* __restrict__ out, int gh, int gw, double stride, double flip_w,
+                                                           float outside) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.z;
     if (c >= gh * gw) return;
     const int j = c % gw, i = c / gw;
     const Geo g = load_geo(table + (long)b * MPN_AUG_COLS, true, src_bytes, 1);
-    float val = 255.0f;
+    float val = outside;
     if (!g.ok) {
         val = __builtin_nanf("");
     } else {
@@ -169,9 +173,9 @@ __global__ void __launch_bounds__(256) augment_mask_kernel(const uint8_t* __rest
     }
     val = val / 255.0f;
     const long cells = (long)gh * gw;
-    float* o = out + (long)b * 18 * cells + c;
+    float* o = out + (long)b * CH * cells + c;
 #pragma unroll
-    for (int k = 0; k < 18; ++k) o[k * cells] = val;
+    for (int k = 0; k < CH; ++k) o[k * cells] = val;
 }
 
 // ---- boxes of instance masks (mpn_augment_boxes) -------------------------------------------------------------------------------
@@ -312,15 +316,28 @@ extern "C" int mpn_augment_image(const uint8_t* src, int64_t src_bytes, const do
     return mpn_launch_status();
 }
 
-extern "C" int mpn_augment_mask(const uint8_t* src, int64_t src_bytes, const double* table, int B, float* out, int gh, int gw, int stride,
-                                int crop_x, void* stream) {
+template <int CH>
+static int launch_augment_mask(const uint8_t* src, int64_t src_bytes, const double* table, int B, float* out, int gh, int gw, int stride,
+                               int crop_x, float outside, void* stream) {
     MPN_CHECK_ARG(src && table && out && src_bytes > 0 && B > 0 && B <= 65535 && gh > 0 && gw > 0 && stride > 0 && crop_x > 0);
     MPN_CHECK_ARG((long)gh * gw <= 0x7fffffffL);
     dim3 grid((unsigned)(((long)gh * gw + 255) / 256), 1u, (unsigned)B);
     // the mask crop is crop_x + 1 wide (ImageAugmentation.py:93): its flip maps x to (crop_x + 1) - 1 - x
-    hipLaunchKernelGGL(augment_mask_kernel, grid, dim3(256), 0, (hipStream_t)stream, src, (long)src_bytes, table, out, gh, gw,
-                       (double)stride, (double)crop_x);
+    hipLaunchKernelGGL(augment_mask_kernel<CH>, grid, dim3(256), 0, (hipStream_t)stream, src, (long)src_bytes, table, out, gh, gw,
+                       (double)stride, (double)crop_x, outside);
     return mpn_launch_status();
+}
+
+extern "C" int mpn_augment_mask(const uint8_t* src, int64_t src_bytes, const double* table, int B, float* out, int gh, int gw, int stride,
+                                int crop_x, void* stream) {
+    return launch_augment_mask<18>(src, src_bytes, table, B, out, gh, gw, stride, crop_x, 255.0f, stream);
+}
+
+extern "C" int mpn_augment_plane(const uint8_t* src, int64_t src_bytes, const double* table, int B, float* out, int gh, int gw, int stride,
+                                 int crop_x, float outside, void* stream) {
+    MPN_CHECK_ARG(outside >= 0.0f && outside <= 255.0f);                  // also refuses NaN
+    MPN_CHECK_ARG((uintptr_t)table % 8 == 0 && (uintptr_t)out % 4 == 0);
+    return launch_augment_mask<1>(src, src_bytes, table, B, out, gh, gw, stride, crop_x, outside, stream);
 }
 
 // 64 x BOX_TILE_Y tiles over the (crop_y + 1) x (crop_x + 1) mask frame: the scan's grid, one partial record per tile

@@ -29,6 +29,7 @@ __device__ __forceinline__ float wave_min(float v) {
 
 struct PredPtrs { const float* p[5]; long sP[5]; };
 struct DPredPtrs { float* p[5]; long sP[5]; int C[5]; };
+struct SegC { int C[5]; };              // live channels of the five predictions: a level has the person-segmentation channel iff C >= 19
 
 // partial[block][8] = {sum_j (5), unused, max, min}
 __global__ void mse_fwd_kernel(PredPtrs pr, const float* __restrict__ gt, const float* __restrict__ wgt, long nelem,
@@ -108,9 +109,19 @@ __device__ __forceinline__ float mse_grad(float k, float w, float g, float pv) {
     return kw * d;
 }
 
-// one thread per (pixel, channel < Cmax); dpred_j[pix*sP + c] = gs*2*w*(p*w - w*g)/N, 0 for c >= 18
+// d(total)/d(pred_j[.., 18]) of the person-segmentation term mean((P - M)^2) / 100: ks = gs * 2 / (100 * npix).  Contraction off
+// for the same reason as above.
+__device__ __forceinline__ float seg_grad(float ks, float m, float pv) {
+#pragma clang fp contract(off)
+    const float d = pv - m;
+    return ks * d;
+}
+
+// one thread per (pixel, channel < Cmax); dpred_j[pix*sP + c] = gs*2*w*(p*w - w*g)/N, 0 for c >= 18.  SEG (the sibling with a
+// mask_all target, mask [npix]): channel 18 of every level that has one carries the seg term's gradient instead of 0.
+template <bool SEG>
 __global__ void mse_bwd_kernel(PredPtrs pr, DPredPtrs dp, const float* __restrict__ gt, const float* __restrict__ wgt,
-                               long npix, int Cmax, const float* __restrict__ gscale) {
+                               const float* __restrict__ mask, long npix, int Cmax, const float* __restrict__ gscale) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= npix * Cmax) return;
     const long pix = i / Cmax; const int c = (int)(i - pix * Cmax);
@@ -118,109 +129,40 @@ __global__ void mse_bwd_kernel(PredPtrs pr, DPredPtrs dp, const float* __restric
     const float k = gs * 2.0f / (float)((double)npix * 18.0);
     float w = 0.f, g = 0.f;
     if (c < 18) { w = wgt[pix * 18 + c]; g = gt[pix * 18 + c]; }
+    float ks = 0.f, m = 0.f;
+    if (SEG && c == 18) { ks = gs * 2.0f / (float)((double)npix * 100.0); m = mask[pix]; }
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
         if (c >= dp.C[j] || dp.p[j] == nullptr) continue;
         float v = 0.f;
         if (c < 18) v = mse_grad(k, w, g, pr.p[j][pix * pr.sP[j] + c]);
+        else if (SEG && c == 18) v = seg_grad(ks, m, pr.p[j][pix * pr.sP[j] + 18]);
         dp.p[j][pix * dp.sP[j] + c] = v;
     }
 }
 
-// ---- recorded training step: loss AND gradients in one pass over the INTERNAL tensors (no exported f32 copies) --------------
-// Levels 0..3 are the intermediate maps k2..k5 at 1, 1/2, 1/4, 1/8 of the heat-map resolution (posenet.py:243-257 up-samples them
-// with nearest neighbours, so a full-resolution pixel (y, x) reads level s at (y >> s, x >> s) and the gradient of a coarse cell is
-// the sum over its 4^s children); level 4 is the final prediction.  One thread owns (8x8 pixel cell, channel): it walks its 64
-// pixels in row-major order, which is the order import_grad_kernel sums children in, so the coarse gradients round identically.
-// Block = 8 cells x 32 channel lanes; lanes >= 18 write the zero padding of the gradient tensors.
-struct TrainPtrs { const float* p[5]; void* d[5]; int Cs[5]; };
-
-template <typename T>
-__global__ void __launch_bounds__(256) mse_train_kernel(TrainPtrs tp, const float* __restrict__ gt, const float* __restrict__ wgt,
-                                                        long g_sB, long g_sC, long g_sH, int B, int H, int W, long ncell,
-                                                        const float* __restrict__ gscale, float* __restrict__ partial) {
+// ---- the person-segmentation term of the API forward: seg_j = mean_pix((P_j[pix, 18] - M[pix])^2) / 100 for every level with a
+// nineteenth channel (C[j] >= 19), 0 for the others.  One lane per pixel, 16 pixels per lane and block sums as mse_fwd_kernel's;
+// partial[block][8] = {sum_j (5), unused, max, min of channel 18 of the final prediction (-inf / +inf without one)}.
+constexpr int SEG_CHUNK = 256 * 16;     // pixels per block
+__global__ void mse_seg_fwd_kernel(PredPtrs pr, SegC sc, const float* __restrict__ mask, long npix, float* __restrict__ partial) {
     __shared__ float sh[4][8];
-    const int c = threadIdx.x & 31;
-    const long cell = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
     float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
     float mx = -INFINITY, mn = INFINITY;
-    if (cell < ncell) {
-        const int cw = W >> 3, ch = H >> 3;
-        const int cx = (int)(cell % cw);
-        const int cy = (int)((cell / cw) % ch);
-        const int b = (int)(cell / ((long)cw * ch));
-        const int y0 = cy * 8, x0 = cx * 8;
-        const float gs = gscale ? gscale[0] : 1.f;
-        const float k = gs * 2.0f / (float)((double)B * H * W * 18.0);
-        const bool live = c < 18;
-        T* d0 = (T*)tp.d[0]; T* d1 = (T*)tp.d[1]; T* d2 = (T*)tp.d[2]; T* d3 = (T*)tp.d[3]; T* d4 = (T*)tp.d[4];
-        float pv1[4] = {0.f, 0.f, 0.f, 0.f}, pv2[2] = {0.f, 0.f}, pv3 = 0.f;
-        float a1[4], a2[2], a3 = 0.f;
-        if (live) pv3 = tp.p[3][(((long)b * ch + cy) * cw + cx) * tp.Cs[3] + c];
-        for (int r = 0; r < 8; ++r) {
-            const int y = y0 + r;
-            float g[8], w[8];
-            if (live) {
-                const float* gp = gt + b * g_sB + c * g_sC + y * g_sH + x0;
-                const float* wp = wgt + b * g_sB + c * g_sC + y * g_sH + x0;
-                const float4 ga = *(const float4*)gp, gb = *(const float4*)(gp + 4);
-                const float4 wa = *(const float4*)wp, wb = *(const float4*)(wp + 4);
-                g[0] = ga.x; g[1] = ga.y; g[2] = ga.z; g[3] = ga.w; g[4] = gb.x; g[5] = gb.y; g[6] = gb.z; g[7] = gb.w;
-                w[0] = wa.x; w[1] = wa.y; w[2] = wa.z; w[3] = wa.w; w[4] = wb.x; w[5] = wb.y; w[6] = wb.z; w[7] = wb.w;
-                if ((r & 1) == 0) {
-                    const float* q = tp.p[1] + (((long)b * (H >> 1) + (y >> 1)) * (W >> 1) + (x0 >> 1)) * tp.Cs[1] + c;
+    const long base = (long)blockIdx.x * SEG_CHUNK;
+    for (int it = 0; it < 16; ++it) {
+        const long pix = base + it * 256 + threadIdx.x;
+        if (pix < npix) {
+            const float m = mask[pix];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) { pv1[i] = q[(long)i * tp.Cs[1]]; a1[i] = 0.f; }
-                }
-                if ((r & 3) == 0) {
-                    const float* q = tp.p[2] + (((long)b * (H >> 2) + (y >> 2)) * (W >> 2) + (x0 >> 2)) * tp.Cs[2] + c;
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) { pv2[i] = q[(long)i * tp.Cs[2]]; a2[i] = 0.f; }
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { g[i] = 0.f; w[i] = 0.f; }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) a1[i] = 0.f;
-                a2[0] = a2[1] = 0.f;
-            }
-            const long row = ((long)b * H + y) * W + x0;
-#pragma unroll
-            for (int px = 0; px < 8; ++px) {
-                float v0 = 0.f, v4 = 0.f;
-                if (live) {
-                    const float p0 = tp.p[0][(row + px) * tp.Cs[0] + c];
-                    const float p4 = tp.p[4][(row + px) * tp.Cs[4] + c];
-                    const float wv = w[px], gv = g[px];
-                    const float wg = wv * gv;
-                    float e;
-                    e = p0 * wv - wg;      s[0] += e * e;
-                    e = pv1[px >> 1] * wv - wg; s[1] += e * e;
-                    e = pv2[px >> 2] * wv - wg; s[2] += e * e;
-                    e = pv3 * wv - wg;     s[3] += e * e;
-                    e = p4 * wv - wg;      s[4] += e * e;
-                    mx = fmaxf(mx, p4); mn = fminf(mn, p4);
-                    v0 = 0.f + mse_grad(k, wv, gv, p0);
-                    v4 = 0.f + mse_grad(k, wv, gv, p4);
-                    a1[px >> 1] += mse_grad(k, wv, gv, pv1[px >> 1]);
-                    a2[px >> 2] += mse_grad(k, wv, gv, pv2[px >> 2]);
-                    a3 += mse_grad(k, wv, gv, pv3);
-                }
-                Elem<T>::st(d0 + (row + px) * tp.Cs[0] + c, v0);
-                Elem<T>::st(d4 + (row + px) * tp.Cs[4] + c, v4);
-            }
-            if (r & 1) {
-                T* q = d1 + (((long)b * (H >> 1) + (y >> 1)) * (W >> 1) + (x0 >> 1)) * tp.Cs[1] + c;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) Elem<T>::st(q + (long)i * tp.Cs[1], a1[i]);
-            }
-            if ((r & 3) == 3) {
-                T* q = d2 + (((long)b * (H >> 2) + (y >> 2)) * (W >> 2) + (x0 >> 2)) * tp.Cs[2] + c;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) Elem<T>::st(q + (long)i * tp.Cs[2], a2[i]);
+            for (int j = 0; j < 5; ++j) {
+                if (sc.C[j] < 19) continue;
+                const float pv = pr.p[j][pix * pr.sP[j] + 18];
+                const float d = pv - m;
+                s[j] += d * d;
+                if (j == 4) { mx = fmaxf(mx, pv); mn = fminf(mn, pv); }
             }
         }
-        Elem<T>::st(d3 + (((long)b * ch + cy) * cw + cx) * tp.Cs[3] + c, a3);
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -239,6 +181,200 @@ __global__ void __launch_bounds__(256) mse_train_kernel(TrainPtrs tp, const floa
         o[5] = 0.f;
         o[6] = fmaxf(fmaxf(sh[0][6], sh[1][6]), fmaxf(sh[2][6], sh[3][6]));
         o[7] = fminf(fminf(sh[0][7], sh[1][7]), fminf(sh[2][7], sh[3][7]));
+    }
+}
+
+// out[MPN_MSE_SEG_OUT]: [0..7] the heat-map vector mse_finalize_kernel has written; [8..12] seg means, [13] their sum, [14] / [15]
+// max / min of channel 18 of the final prediction (0 / 0 without one), [16] = out[5] + out[13], the total.  Sums in float64.
+__global__ void mse_seg_finalize_kernel(const float* __restrict__ partial, int chunks, double npix, int final_has_seg,
+                                        float* __restrict__ out) {
+    __shared__ double sh[256][5];
+    __shared__ float shm[256][2];
+    double s[5] = {0, 0, 0, 0, 0};
+    float mx = -INFINITY, mn = INFINITY;
+    for (int i = threadIdx.x; i < chunks; i += 256) {
+        const float* o = partial + (long)i * 8;
+        for (int j = 0; j < 5; ++j) s[j] += (double)o[j];
+        mx = fmaxf(mx, o[6]); mn = fminf(mn, o[7]);
+    }
+    for (int j = 0; j < 5; ++j) sh[threadIdx.x][j] = s[j];
+    shm[threadIdx.x][0] = mx; shm[threadIdx.x][1] = mn;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot[5] = {0, 0, 0, 0, 0};
+        for (int i = 0; i < 256; ++i) {
+            for (int j = 0; j < 5; ++j) tot[j] += sh[i][j];
+            mx = fmaxf(mx, shm[i][0]); mn = fminf(mn, shm[i][1]);
+        }
+        float total = 0.f;
+        for (int j = 0; j < 5; ++j) { const float l = (float)(tot[j] / (npix * 100.0)); out[8 + j] = l; total += l; }
+        out[13] = total;
+        out[14] = final_has_seg ? mx : 0.f;
+        out[15] = final_has_seg ? mn : 0.f;
+        out[16] = out[5] + total;
+        for (int j = 17; j < MPN_MSE_SEG_OUT; ++j) out[j] = 0.f;
+    }
+}
+
+// ---- recorded training step: loss AND gradients in one pass over the INTERNAL tensors (no exported f32 copies) --------------
+// Levels 0..3 are the intermediate maps k2..k5 at 1, 1/2, 1/4, 1/8 of the heat-map resolution (posenet.py:243-257 up-samples them
+// with nearest neighbours, so a full-resolution pixel (y, x) reads level s at (y >> s, x >> s) and the gradient of a coarse cell is
+// the sum over its 4^s children); level 4 is the final prediction.  One thread owns (8x8 pixel cell, channel): it walks its 64
+// pixels in row-major order, which is the order import_grad_kernel sums children in, so the coarse gradients round identically.
+// Block = 8 cells x 32 channel lanes; lanes >= 18 write the zero padding of the gradient tensors.
+struct TrainPtrs { const float* p[5]; void* d[5]; int Cs[5]; };
+
+// SEG (mpn_mse_heatmap_seg_train): lane 18 is live on every level with a nineteenth channel, with w = 1, g = M (the mask_all plane,
+// [B][1][H][W] dense, read with the same two 16-byte loads per row) and its own scale 2 gs / (100 B H W).  With w = 1 the heat
+// term's expressions ARE the seg term's (p * 1 - 1 * g = p - M, (k * 1) * d = k d: multiplying by 1 is exact), so the lane takes
+// the same cell walk and its coarse sums round as import_grad's; its sums, max and min leave through seg_partial.  On a level
+// without the channel lane 18 reads nothing and writes the zero it always wrote.  With SEG false every `on` is `live` and the
+// kernel is mpn_mse_heatmap_train's as it was.
+template <typename T, bool SEG>
+__global__ void __launch_bounds__(256) mse_train_kernel(TrainPtrs tp, const float* __restrict__ gt, const float* __restrict__ wgt,
+                                                        long g_sB, long g_sC, long g_sH, int B, int H, int W, long ncell,
+                                                        const float* __restrict__ gscale, float* __restrict__ partial,
+                                                        const float* __restrict__ mask, SegC sc, float* __restrict__ seg_partial) {
+    __shared__ float sh[4][SEG ? 16 : 8];
+    const int c = threadIdx.x & 31;
+    const long cell = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
+    float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float mx = -INFINITY, mn = INFINITY;
+    const bool live = c < 18;
+    const bool segl = SEG && c == 18;
+    if (cell < ncell) {
+        const int cw = W >> 3, ch = H >> 3;
+        const int cx = (int)(cell % cw);
+        const int cy = (int)((cell / cw) % ch);
+        const int b = (int)(cell / ((long)cw * ch));
+        const int y0 = cy * 8, x0 = cx * 8;
+        const float gs = gscale ? gscale[0] : 1.f;
+        const float k = segl ? gs * 2.0f / (float)((double)B * H * W * 100.0) : gs * 2.0f / (float)((double)B * H * W * 18.0);
+        const bool act = live || segl;
+        const bool on0 = live || (segl && sc.C[0] >= 19), on1 = live || (segl && sc.C[1] >= 19), on2 = live || (segl && sc.C[2] >= 19),
+                   on3 = live || (segl && sc.C[3] >= 19), on4 = live || (segl && sc.C[4] >= 19);
+        T* d0 = (T*)tp.d[0]; T* d1 = (T*)tp.d[1]; T* d2 = (T*)tp.d[2]; T* d3 = (T*)tp.d[3]; T* d4 = (T*)tp.d[4];
+        float pv1[4] = {0.f, 0.f, 0.f, 0.f}, pv2[2] = {0.f, 0.f}, pv3 = 0.f;
+        float a1[4], a2[2], a3 = 0.f;
+        if (on3) pv3 = tp.p[3][(((long)b * ch + cy) * cw + cx) * tp.Cs[3] + c];
+        for (int r = 0; r < 8; ++r) {
+            const int y = y0 + r;
+            float g[8], w[8];
+            if (act) {
+                if (segl) {
+                    const float* mp = mask + ((long)b * H + y) * W + x0;
+                    const float4 ga = *(const float4*)mp, gb = *(const float4*)(mp + 4);
+                    g[0] = ga.x; g[1] = ga.y; g[2] = ga.z; g[3] = ga.w; g[4] = gb.x; g[5] = gb.y; g[6] = gb.z; g[7] = gb.w;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) w[i] = 1.f;
+                } else {
+                    const float* gp = gt + b * g_sB + c * g_sC + y * g_sH + x0;
+                    const float* wp = wgt + b * g_sB + c * g_sC + y * g_sH + x0;
+                    const float4 ga = *(const float4*)gp, gb = *(const float4*)(gp + 4);
+                    const float4 wa = *(const float4*)wp, wb = *(const float4*)(wp + 4);
+                    g[0] = ga.x; g[1] = ga.y; g[2] = ga.z; g[3] = ga.w; g[4] = gb.x; g[5] = gb.y; g[6] = gb.z; g[7] = gb.w;
+                    w[0] = wa.x; w[1] = wa.y; w[2] = wa.z; w[3] = wa.w; w[4] = wb.x; w[5] = wb.y; w[6] = wb.z; w[7] = wb.w;
+                }
+                if ((r & 1) == 0) {
+                    const float* q = tp.p[1] + (((long)b * (H >> 1) + (y >> 1)) * (W >> 1) + (x0 >> 1)) * tp.Cs[1] + c;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) { pv1[i] = on1 ? q[(long)i * tp.Cs[1]] : 0.f; a1[i] = 0.f; }
+                }
+                if ((r & 3) == 0) {
+                    const float* q = tp.p[2] + (((long)b * (H >> 2) + (y >> 2)) * (W >> 2) + (x0 >> 2)) * tp.Cs[2] + c;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) { pv2[i] = on2 ? q[(long)i * tp.Cs[2]] : 0.f; a2[i] = 0.f; }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { g[i] = 0.f; w[i] = 0.f; }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) a1[i] = 0.f;
+                a2[0] = a2[1] = 0.f;
+            }
+            const long row = ((long)b * H + y) * W + x0;
+#pragma unroll
+            for (int px = 0; px < 8; ++px) {
+                float v0 = 0.f, v4 = 0.f;
+                if (act) {
+                    const float wv = w[px], gv = g[px];
+                    const float wg = wv * gv;
+                    float e;
+                    if (on0) {
+                        const float p0 = tp.p[0][(row + px) * tp.Cs[0] + c];
+                        e = p0 * wv - wg;      s[0] += e * e;
+                        v0 = 0.f + mse_grad(k, wv, gv, p0);
+                    }
+                    if (on1) { e = pv1[px >> 1] * wv - wg; s[1] += e * e; a1[px >> 1] += mse_grad(k, wv, gv, pv1[px >> 1]); }
+                    if (on2) { e = pv2[px >> 2] * wv - wg; s[2] += e * e; a2[px >> 2] += mse_grad(k, wv, gv, pv2[px >> 2]); }
+                    if (on3) { e = pv3 * wv - wg;     s[3] += e * e; a3 += mse_grad(k, wv, gv, pv3); }
+                    if (on4) {
+                        const float p4 = tp.p[4][(row + px) * tp.Cs[4] + c];
+                        e = p4 * wv - wg;      s[4] += e * e;
+                        mx = fmaxf(mx, p4); mn = fminf(mn, p4);
+                        v4 = 0.f + mse_grad(k, wv, gv, p4);
+                    }
+                }
+                Elem<T>::st(d0 + (row + px) * tp.Cs[0] + c, v0);
+                Elem<T>::st(d4 + (row + px) * tp.Cs[4] + c, v4);
+            }
+            if (r & 1) {
+                T* q = d1 + (((long)b * (H >> 1) + (y >> 1)) * (W >> 1) + (x0 >> 1)) * tp.Cs[1] + c;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) Elem<T>::st(q + (long)i * tp.Cs[1], a1[i]);
+            }
+            if ((r & 3) == 3) {
+                T* q = d2 + (((long)b * (H >> 2) + (y >> 2)) * (W >> 2) + (x0 >> 2)) * tp.Cs[2] + c;
+#pragma unroll
+                for (int i = 0; i < 2; ++i) Elem<T>::st(q + (long)i * tp.Cs[2], a2[i]);
+            }
+        }
+        Elem<T>::st(d3 + (((long)b * ch + cy) * cw + cx) * tp.Cs[3] + c, a3);
+    }
+    // lane 18's sums are the seg term's: they leave the heat sums before the wave folds
+    float ss[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float smx = -INFINITY, smn = INFINITY;
+    if (segl) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) { ss[j] = s[j]; s[j] = 0.f; }
+        smx = mx; smn = mn; mx = -INFINITY; mn = INFINITY;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) s[j] = wave_sum(s[j]);
+    mx = wave_max(mx); mn = wave_min(mn);
+    if (SEG) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) ss[j] = wave_sum(ss[j]);
+        smx = wave_max(smx); smn = wave_min(smn);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) sh[wave][j] = s[j];
+        sh[wave][6] = mx; sh[wave][7] = mn;
+        if (SEG) {
+#pragma unroll
+            for (int j = 0; j < 5; ++j) sh[wave][(SEG ? 8 : 0) + j] = ss[j];
+            sh[wave][SEG ? 14 : 6] = smx; sh[wave][SEG ? 15 : 7] = smn;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float* o = partial + (long)blockIdx.x * 8;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) o[j] = sh[0][j] + sh[1][j] + sh[2][j] + sh[3][j];
+        o[5] = 0.f;
+        o[6] = fmaxf(fmaxf(sh[0][6], sh[1][6]), fmaxf(sh[2][6], sh[3][6]));
+        o[7] = fminf(fminf(sh[0][7], sh[1][7]), fminf(sh[2][7], sh[3][7]));
+        if (SEG) {
+            constexpr int S0 = SEG ? 8 : 0;
+            float* q = seg_partial + (long)blockIdx.x * 8;
+#pragma unroll
+            for (int j = 0; j < 5; ++j) q[j] = sh[0][S0 + j] + sh[1][S0 + j] + sh[2][S0 + j] + sh[3][S0 + j];
+            q[5] = 0.f;
+            q[6] = fmaxf(fmaxf(sh[0][S0 + 6], sh[1][S0 + 6]), fmaxf(sh[2][S0 + 6], sh[3][S0 + 6]));
+            q[7] = fminf(fminf(sh[0][S0 + 7], sh[1][S0 + 7]), fminf(sh[2][S0 + 7], sh[3][S0 + 7]));
+        }
     }
 }
 
@@ -855,7 +991,52 @@ extern "C" int mpn_mse_heatmap_backward(const float* const* preds, float* const*
         if (pred_C[j] > cmax) cmax = pred_C[j];
     }
     const long n = (long)npix * cmax;
-    hipLaunchKernelGGL(mse_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pr, dp, gt, wgt, (long)npix, cmax, gscale);
+    hipLaunchKernelGGL(mse_bwd_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pr, dp, gt, wgt,
+                       (const float*)nullptr, (long)npix, cmax, gscale);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_mse_seg_chunks(int64_t npix) { return (int)((npix + SEG_CHUNK - 1) / SEG_CHUNK); }
+
+extern "C" int mpn_mse_heatmap_seg_forward(const float* const* preds, const int64_t* pred_sP, const int32_t* pred_C, const float* gt,
+                                           const float* wgt, const float* mask, int64_t npix, float* partial, int chunks,
+                                           float* seg_partial, int seg_chunks, float* out, void* stream) {
+    MPN_CHECK_ARG(preds && pred_sP && pred_C && gt && wgt && mask && partial && seg_partial && out && npix > 0 && npix <= 0x7fffffffL);
+    MPN_CHECK_ARG(chunks == mpn_mse_chunks(npix) && seg_chunks == mpn_mse_seg_chunks(npix));
+    MPN_CHECK_ARG(((uintptr_t)gt | (uintptr_t)wgt | (uintptr_t)mask | (uintptr_t)partial | (uintptr_t)seg_partial | (uintptr_t)out) % 4 == 0);
+    PredPtrs pr; SegC sc;
+    for (int j = 0; j < 5; ++j) {
+        MPN_CHECK_ARG(preds[j] != nullptr && (uintptr_t)preds[j] % 4 == 0 && pred_C[j] >= 18 && pred_sP[j] >= pred_C[j]);
+        pr.p[j] = preds[j]; pr.sP[j] = (long)pred_sP[j]; sc.C[j] = pred_C[j];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // the heat term: mpn_mse_heatmap_forward's two launches, so out[0..7] are its bits
+    hipLaunchKernelGGL(mse_fwd_kernel, dim3((unsigned)chunks), dim3(256), 0, st, pr, gt, wgt, (long)npix * 18, partial);
+    hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)partial, chunks, (double)npix * 18.0, out);
+    hipLaunchKernelGGL(mse_seg_fwd_kernel, dim3((unsigned)seg_chunks), dim3(256), 0, st, pr, sc, mask, (long)npix, seg_partial);
+    hipLaunchKernelGGL(mse_seg_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)seg_partial, seg_chunks, (double)npix,
+                       sc.C[4] >= 19 ? 1 : 0, out);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_mse_heatmap_seg_backward(const float* const* preds, float* const* dpreds, const int64_t* pred_sP,
+                                            const int64_t* dpred_sP, const int32_t* pred_C, const float* gt, const float* wgt,
+                                            const float* mask, int64_t npix, const float* gscale, void* stream) {
+    MPN_CHECK_ARG(preds && dpreds && pred_sP && dpred_sP && pred_C && gt && wgt && mask && npix > 0 && npix <= 0x7fffffffL);
+    MPN_CHECK_ARG(((uintptr_t)gt | (uintptr_t)wgt | (uintptr_t)mask | (uintptr_t)gscale) % 4 == 0);
+    PredPtrs pr; DPredPtrs dp; int cmax = 0;
+    for (int j = 0; j < 5; ++j) {
+        // a level that gets a gradient is read at channel c < pred_C[j] of both tensors
+        MPN_CHECK_ARG(preds[j] != nullptr && (uintptr_t)preds[j] % 4 == 0 && (uintptr_t)dpreds[j] % 4 == 0 && pred_C[j] >= 0 && pred_C[j] <= 32);
+        MPN_CHECK_ARG(dpreds[j] == nullptr || (pred_C[j] >= 18 && pred_sP[j] >= pred_C[j] && dpred_sP[j] >= pred_C[j]));
+        pr.p[j] = preds[j]; pr.sP[j] = (long)pred_sP[j];
+        dp.p[j] = dpreds[j]; dp.sP[j] = (long)dpred_sP[j]; dp.C[j] = pred_C[j];
+        if (pred_C[j] > cmax) cmax = pred_C[j];
+    }
+    MPN_CHECK_ARG(cmax >= 18);
+    const long n = (long)npix * cmax;
+    hipLaunchKernelGGL(mse_bwd_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, pr, dp, gt, wgt, mask,
+                       (long)npix, cmax, gscale);
     return mpn_launch_status();
 }
 
@@ -873,10 +1054,36 @@ extern "C" int mpn_mse_heatmap_train(const float* const* levels, void* const* dl
         tp.p[j] = levels[j]; tp.d[j] = dlevels[j]; tp.Cs[j] = level_Cs[j];
     }
     const long ncell = (long)B * (H / 8) * (W / 8);
-    MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((mse_train_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tp, gt, wgt,
-                                             (long)g_sB, (long)g_sC, (long)g_sH, B, H, W, ncell, gscale, partial));
+    MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((mse_train_kernel<T, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tp, gt, wgt,
+                                             (long)g_sB, (long)g_sC, (long)g_sH, B, H, W, ncell, gscale, partial, (const float*)nullptr, SegC(),
+                                             (float*)nullptr));
     hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, blocks,
                        (double)B * H * W * 18.0, out);
+    return mpn_launch_status();
+}
+
+extern "C" int mpn_mse_heatmap_seg_train(const float* const* levels, void* const* dlevels, const int32_t* level_Cs, const int32_t* level_C,
+                                         int dtype, const float* gt, const float* wgt, const float* mask, int64_t g_sB, int64_t g_sC,
+                                         int64_t g_sH, int B, int H, int W, const float* gscale, float* partial, int blocks, float* out,
+                                         void* stream) {
+    MPN_CHECK_ARG(levels && dlevels && level_Cs && level_C && gt && wgt && mask && partial && out && B > 0);
+    MPN_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && blocks == mpn_mse_train_blocks(B, H, W) && (long)B * H * W <= 0x7fffffffL);
+    MPN_CHECK_ARG(g_sH % 4 == 0 && g_sC % 4 == 0 && g_sB % 4 == 0 && ((uintptr_t)gt & 15) == 0 && ((uintptr_t)wgt & 15) == 0);
+    MPN_CHECK_ARG(((uintptr_t)mask & 15) == 0 && (((uintptr_t)partial | (uintptr_t)out | (uintptr_t)gscale) & 3) == 0);
+    MPN_CHECK_ARG(dtype == MPN_F32 || dtype == MPN_BF16 || dtype == MPN_F16);
+    TrainPtrs tp; SegC sc;
+    for (int j = 0; j < 5; ++j) {
+        MPN_CHECK_ARG(levels[j] && dlevels[j] && level_Cs[j] == 32 && level_C[j] >= 18 && level_C[j] <= 32 && ((uintptr_t)levels[j] & 3) == 0);
+        tp.p[j] = levels[j]; tp.d[j] = dlevels[j]; tp.Cs[j] = level_Cs[j]; sc.C[j] = level_C[j];
+    }
+    const long ncell = (long)B * (H / 8) * (W / 8);
+    float* seg_partial = partial + (long)blocks * 8;                     // partial: blocks * 16 floats, the heat records first
+    MPN_DISPATCH_T(dtype, hipLaunchKernelGGL((mse_train_kernel<T, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tp, gt, wgt,
+                                             (long)g_sB, (long)g_sC, (long)g_sH, B, H, W, ncell, gscale, partial, mask, sc, seg_partial));
+    hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partial, blocks,
+                       (double)B * H * W * 18.0, out);
+    hipLaunchKernelGGL(mse_seg_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)seg_partial, blocks,
+                       (double)B * H * W, sc.C[4] >= 19 ? 1 : 0, out);
     return mpn_launch_status();
 }
 
@@ -990,6 +1197,26 @@ __global__ void step_log_kernel(const float* __restrict__ kp8, const float* __re
 extern "C" int mpn_step_log(const float* kp8, const float* det2, float* logv, void* stream) {
     MPN_CHECK_ARG(logv && (kp8 || det2));
     hipLaunchKernelGGL(step_log_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kp8, det2, logv);
+    return mpn_launch_status();
+}
+
+// The step log with the person-segmentation term (kp = the MPN_MSE_SEG_OUT vector of mpn_mse_heatmap_seg_forward): [0..12] keep their
+// meaning ([11] loss = kp[16] + detection total, [12] is the clip's), [13..17] seg means, [18] seg total, [19] / [20] max / min of
+// channel 18 of the final prediction.
+__global__ void step_log_seg_kernel(const float* __restrict__ kp, const float* __restrict__ det2, float* __restrict__ logv) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    for (int i = 0; i < 8; ++i) { logv[i] = kp[i]; logv[13 + i] = kp[8 + i]; }
+    float det_total = 0.f;
+    if (det2) {
+        det_total = det2[0] + det2[1];
+        logv[8] = det_total; logv[9] = det2[0]; logv[10] = det2[1];
+    }
+    logv[11] = det2 ? kp[16] + det_total : kp[16];
+}
+
+extern "C" int mpn_step_log_seg(const float* kp, const float* det2, float* logv, void* stream) {
+    MPN_CHECK_ARG(logv && kp && ((uintptr_t)logv | (uintptr_t)kp | (uintptr_t)det2) % 4 == 0);
+    hipLaunchKernelGGL(step_log_seg_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, kp, det2, logv);
     return mpn_launch_status();
 }
 

@@ -269,20 +269,25 @@ __device__ __forceinline__ unsigned long long bit_range(int lo, int hi) {
 // instance's parts (or_part_words, image column x = rectangle column x - rx0, cells outside the rectangle read 0) and only then
 // applies the kind.  ~miss goes column-major -> row-major through LDS (4 KiB) and is stored as 0 / 255 along rows, four bytes per lane
 // where the plane's rows are 4-byte aligned.  No atomics: the bytes are the same on every run.
+//
+// ALL (mpn_segm_person_masks): the same walk also keeps `uni`, the union of EVERY instance whatever its kind (all | crowds), and stores
+// it as a second plane, mask_all, at the same offset and pitch of out_all: 255 where anyone stands.  With ALL false `uni`, its slab
+// and its stores do not exist and the kernel is mpn_segm_mask_miss's as it always was.
+template <bool ALL>
 __global__ void __launch_bounds__(256) segm_mask_miss_kernel(const int64_t* __restrict__ imgs, const int64_t* __restrict__ insts, int n_inst,
                                                              const int32_t* __restrict__ kind, const int64_t* __restrict__ parts, int n_parts,
                                                              const unsigned long long* __restrict__ ws, long ws_words,
-                                                             uint8_t* __restrict__ out, long out_bytes) {
+                                                             uint8_t* __restrict__ out, uint8_t* __restrict__ out_all, long out_bytes) {
     constexpr int NW = SEG_KC / 4;                                       // words per wave
-    __shared__ unsigned long long slab[SEG_KC][64];
+    __shared__ unsigned long long slab[ALL ? 2 : 1][SEG_KC][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const SegImg im = load_img(imgs + (long)blockIdx.z * MPN_SEGM_COLS, n_inst, out_bytes);
     const int x0 = blockIdx.x * 64, k0 = blockIdx.y * SEG_KC;
     if (!im.ok || x0 >= im.w || k0 * 64 >= im.h) return;                 // the same for the whole workgroup
     const int kw = k0 + wave * NW;                                       // this wave's first word
-    unsigned long long all[NW], miss[NW];
+    unsigned long long all[NW], miss[NW], uni[NW];
 #pragma unroll
-    for (int j = 0; j < NW; ++j) all[j] = miss[j] = 0;
+    for (int j = 0; j < NW; ++j) all[j] = miss[j] = uni[j] = 0;
     for (int i = im.i0; i < im.i1; ++i) {
         const SegInst in = load_inst(insts + (long)i * MPN_SEGI_COLS, n_parts, -1);
         const int kd = kind[i];
@@ -304,6 +309,7 @@ __global__ void __launch_bounds__(256) segm_mask_miss_kernel(const int64_t* __re
 #pragma unroll
         for (int j = 0; j < NW; ++j) {
             const unsigned long long mj = m[j] & bit_range(in.ry0 - (kw + j) * 64, in.ry0 + in.rh - (kw + j) * 64);
+            if (ALL) uni[j] |= mj;
             if (kd == MPN_SEGK_CROWD) {
                 miss[j] |= mj & ~all[j];
             } else {
@@ -313,33 +319,39 @@ __global__ void __launch_bounds__(256) segm_mask_miss_kernel(const int64_t* __re
         }
     }
 #pragma unroll
-    for (int j = 0; j < NW; ++j) slab[wave * NW + j][lane] = ~miss[j];
+    for (int j = 0; j < NW; ++j) {
+        slab[0][wave * NW + j][lane] = ~miss[j];
+        if (ALL) slab[ALL ? 1 : 0][wave * NW + j][lane] = uni[j];
+    }
     __syncthreads();
     // rows: a lane holds four consecutive columns, 16 lanes are the 64 bytes of one row, a wave stores four rows at a time; wave v
     // stores rows 16 v .. 16 v + 15 of every word
     const int cg = (lane & 15) * 4, x = x0 + cg;
-    uint8_t* plane = out + im.off;
-    const bool wide = (((uintptr_t)plane | (uintptr_t)im.pitch) & 3) == 0 && x + 3 < im.w;
+#pragma unroll
+    for (int pl = 0; pl < (ALL ? 2 : 1); ++pl) {
+        uint8_t* plane = (pl == 0 ? out : out_all) + im.off;
+        const bool wide = (((uintptr_t)plane | (uintptr_t)im.pitch) & 3) == 0 && x + 3 < im.w;
 #pragma unroll 1
-    for (int j = 0; j < SEG_KC; ++j) {
-        if ((k0 + j) * 64 >= im.h) break;
-        unsigned long long wd[4];
+        for (int j = 0; j < SEG_KC; ++j) {
+            if ((k0 + j) * 64 >= im.h) break;
+            unsigned long long wd[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) wd[t] = slab[j][cg + t];
+            for (int t = 0; t < 4; ++t) wd[t] = slab[pl][j][cg + t];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int b = wave * 16 + r * 4 + (lane >> 4), y = (k0 + j) * 64 + b;
-            if (y >= im.h || x >= im.w) continue;
-            uint32_t v = 0;
+            for (int r = 0; r < 4; ++r) {
+                const int b = wave * 16 + r * 4 + (lane >> 4), y = (k0 + j) * 64 + b;
+                if (y >= im.h || x >= im.w) continue;
+                uint32_t v = 0;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) v |= (0u - (uint32_t)((wd[t] >> b) & 1) & 0xffu) << (8 * t);
-            uint8_t* q = plane + (long)y * im.pitch + x;
-            if (wide) {
-                *reinterpret_cast<uint32_t*>(q) = v;
-            } else {
+                for (int t = 0; t < 4; ++t) v |= (0u - (uint32_t)((wd[t] >> b) & 1) & 0xffu) << (8 * t);
+                uint8_t* q = plane + (long)y * im.pitch + x;
+                if (wide) {
+                    *reinterpret_cast<uint32_t*>(q) = v;
+                } else {
 #pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    if (x + t < im.w) q[t] = (uint8_t)(v >> (8 * t));
+                    for (int t = 0; t < 4; ++t)
+                        if (x + t < im.w) q[t] = (uint8_t)(v >> (8 * t));
+                }
             }
         }
     }
@@ -399,10 +411,11 @@ extern "C" int mpn_segm_rasterize(const int64_t* insts, int n_inst, const int64_
     return mpn_launch_status();
 }
 
-extern "C" int mpn_segm_mask_miss(const int64_t* imgs, int n_img, const int64_t* insts, const int32_t* kind, int n_inst, const int64_t* parts,
-                                  int n_parts, const int32_t* verts, const int32_t* vpart, const int32_t* estart, int n_verts, int64_t n_steps,
-                                  const int32_t* toggles, int n_tog, int max_w, int max_h, uint8_t* out, int64_t out_bytes, void* workspace,
-                                  int64_t ws_bytes, void* stream) {
+// what mpn_segm_mask_miss and mpn_segm_person_masks share: out_all null = the one-plane form
+static int segm_compose(const int64_t* imgs, int n_img, const int64_t* insts, const int32_t* kind, int n_inst, const int64_t* parts,
+                        int n_parts, const int32_t* verts, const int32_t* vpart, const int32_t* estart, int n_verts, int64_t n_steps,
+                        const int32_t* toggles, int n_tog, int max_w, int max_h, uint8_t* out, uint8_t* out_all, int64_t out_bytes,
+                        void* workspace, int64_t ws_bytes, void* stream) {
     MPN_CHECK_ARG(imgs && out && n_img >= 1 && n_img <= 65535 && n_inst >= 0 && (n_inst == 0 || kind));
     MPN_CHECK_ARG(max_w >= 1 && max_w <= 65536 && max_h >= 1 && max_h <= 65536 && out_bytes >= 1 && out_bytes <= (1L << 40));
     MPN_CHECK_ARG((uintptr_t)imgs % 8 == 0 && (uintptr_t)kind % 4 == 0);
@@ -411,7 +424,30 @@ extern "C" int mpn_segm_mask_miss(const int64_t* imgs, int n_img, const int64_t*
                                      ws_bytes, st);
     if (rc != 0) return rc;
     dim3 grid((unsigned)((max_w + 63) / 64), (unsigned)((max_h + 64 * SEG_KC - 1) / (64 * SEG_KC)), (unsigned)n_img);
-    hipLaunchKernelGGL(segm_mask_miss_kernel, grid, dim3(256), 0, st, imgs, insts, n_inst, kind, parts, n_parts,
-                       (const unsigned long long*)workspace, (long)(ws_bytes / 8), out, (long)out_bytes);
+    if (out_all)
+        hipLaunchKernelGGL(segm_mask_miss_kernel<true>, grid, dim3(256), 0, st, imgs, insts, n_inst, kind, parts, n_parts,
+                           (const unsigned long long*)workspace, (long)(ws_bytes / 8), out, out_all, (long)out_bytes);
+    else
+        hipLaunchKernelGGL(segm_mask_miss_kernel<false>, grid, dim3(256), 0, st, imgs, insts, n_inst, kind, parts, n_parts,
+                           (const unsigned long long*)workspace, (long)(ws_bytes / 8), out, (uint8_t*)nullptr, (long)out_bytes);
     return mpn_launch_status();
+}
+
+extern "C" int mpn_segm_mask_miss(const int64_t* imgs, int n_img, const int64_t* insts, const int32_t* kind, int n_inst, const int64_t* parts,
+                                  int n_parts, const int32_t* verts, const int32_t* vpart, const int32_t* estart, int n_verts, int64_t n_steps,
+                                  const int32_t* toggles, int n_tog, int max_w, int max_h, uint8_t* out, int64_t out_bytes, void* workspace,
+                                  int64_t ws_bytes, void* stream) {
+    return segm_compose(imgs, n_img, insts, kind, n_inst, parts, n_parts, verts, vpart, estart, n_verts, n_steps, toggles, n_tog, max_w,
+                        max_h, out, nullptr, out_bytes, workspace, ws_bytes, stream);
+}
+
+extern "C" int mpn_segm_person_masks(const int64_t* imgs, int n_img, const int64_t* insts, const int32_t* kind, int n_inst,
+                                     const int64_t* parts, int n_parts, const int32_t* verts, const int32_t* vpart, const int32_t* estart,
+                                     int n_verts, int64_t n_steps, const int32_t* toggles, int n_tog, int max_w, int max_h, uint8_t* out_miss,
+                                     uint8_t* out_all, int64_t out_bytes, void* workspace, int64_t ws_bytes, void* stream) {
+    // the two planes of an image lie at one offset of two buffers of out_bytes each: the buffers must not overlap
+    MPN_CHECK_ARG(out_all && out_miss && out_bytes >= 1 && out_bytes <= (1L << 40));
+    MPN_CHECK_ARG((out_all > out_miss ? out_all - out_miss : out_miss - out_all) >= out_bytes);
+    return segm_compose(imgs, n_img, insts, kind, n_inst, parts, n_parts, verts, vpart, estart, n_verts, n_steps, toggles, n_tog, max_w,
+                        max_h, out_miss, out_all, out_bytes, workspace, ws_bytes, stream);
 }

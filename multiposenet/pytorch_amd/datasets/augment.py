@@ -368,6 +368,16 @@ def augment_mask(src, table, gh, gw, stride, crop_x):
     return out
 
 
+def augment_plane(src, table, gh, gw, stride, crop_x, outside=0.0):
+    """mpn_augment_plane: packed uint8 planes (device) at the table's MASK columns -> float32 [B, 1, gh, gw], sampled as
+    :func:`augment_mask` samples, ``outside`` / 255 where the cell lies outside the canvas or the scaled image."""
+    B = table.shape[0]
+    out = torch.empty((B, 1, gh, gw), dtype=torch.float32, device=src.device)
+    call("mpn_augment_plane", ops.ptr(src), src.numel(), ops.ptr(table), B, ops.ptr(out), gh, gw, stride, crop_x, float(outside),
+         ops.stream_ptr())
+    return out
+
+
 def augment_boxes(src, table, row_inst, B, N, crop_y, crop_x):
     """mpn_augment_boxes: packed instance-mask rectangles (uint8, device; None when there is no instance) + instance table
     [n_inst, 24] float64 + row map int32 [B * N] (instance of each output row, -1 = padding) -> float32 [B, N, 5]."""
@@ -448,6 +458,22 @@ def mask_source(samples):
     if len(kinds) > 1:
         raise MpnError("either every sample of a batch has a mask_miss or none has")
     return kinds.pop() if kinds else None
+
+
+def check_mask_all(samples, source):
+    """What ``DeviceAugmenter(mask_all=True)`` asks of a batch, before any dice are drawn: a mask source (``source`` from
+    :func:`mask_source`), and on a ``"mask_miss"`` batch a uint8 [H, W] ``"mask_all"`` plane in every sample."""
+    if source is None:
+        raise MpnError("mask_all needs a batch with 'person_anns' or with 'mask_miss' and 'mask_all' planes")
+    if source == "person_anns":
+        return
+    for s in samples:
+        if s.get("mask_all") is None:
+            raise MpnError("with mask_all every 'mask_miss' sample also carries a 'mask_all' plane")
+        _check_u8(s["mask_all"], "mask_all", 2)
+        img = s.get("img")
+        if isinstance(img, torch.Tensor) and img.dim() == 3 and tuple(s["mask_all"].shape) != tuple(img.shape[:2]):
+            raise MpnError("mask_all must have the image's [H, W]")
 
 
 def segmentation_pack(sample, H, W, strict=True):
@@ -532,7 +558,7 @@ class _Augmenter(object):
 
 
 class DeviceAugmenter(_Augmenter):
-    """``DeviceAugmenter(inp_size, feat_stride)(samples)`` -> ``(img, heatmaps, heat_mask, meta)``: the reference's training triple
+    """``DeviceAugmenter(inp_size, feat_stride, params=None, mask_all=False)(samples)`` -> ``(img, heatmaps, heat_mask, meta)``: the reference's training triple
     for ``keypoint_subnet`` (float32, contiguous, on the current device) plus the host-side geometry of every sample.
 
     A sample is a dict with the decoded image and the reference's meta fields::
@@ -548,13 +574,25 @@ class DeviceAugmenter(_Augmenter):
     is read and no H x W plane is uploaded; ``segm_strict`` applies (:func:`mask_source` states what a batch may mix).  (The ``aug_*_bbox`` chain of the
     detection loader is NOT this chain with the mask left out: it never rotates ``objpos`` and so crops elsewhere; see
     :func:`augment_meta_bbox` and :class:`DeviceBBoxAugmenter`.)  ``dice`` [B, 6] makes the draws explicit; otherwise they come from ``rng``
-    (a ``random.Random``; default the ``random`` module, as in the reference) through :func:`draw_dice`."""
+    (a ``random.Random``; default the ``random`` module, as in the reference) through :func:`draw_dice`.
+
+    ``mask_all=True`` adds the target of the person-segmentation channel: ``(img, heatmaps, heat_mask, mask_all, meta)`` with
+    ``mask_all`` float32 [B, 1, grid, grid] in [0, 1], ``mask_miss``'s sampling of the union of the image's person annotations with
+    0 outside the image (``mpn_augment_plane``).  On a ``"person_anns"`` batch both planes come from the one
+    compose launch (:func:`..segm.person_masks_batch`); on a ``"mask_miss"`` batch every sample also carries a uint8 [H, W]
+    ``"mask_all"`` plane.  An image-only batch, a missing, mis-shaped or non-uint8 plane raise before any dice are drawn."""
+
+    def __init__(self, inp_size, feat_stride, params=None, mask_all=False):
+        super(DeviceAugmenter, self).__init__(inp_size, feat_stride, params)
+        self.mask_all = bool(mask_all)
 
     def geometry(self, samples, dice=None, rng=None, mask_frame=False):
         """Part 1 for a batch: list of per-sample dicts of :func:`augment_meta` with the final (``remove_illegal_joint``) joints
         under ``joint_self_out`` / ``joint_others_out``.  Needs no GPU.  ``mask_frame`` asks for the ``crop + 1`` slice test of
         the masks even when the batch carries no ``mask_miss`` (instance masks take the same slices)."""
         source = mask_source(samples)                                  # before the dice are drawn: a refused batch leaves rng alone
+        if self.mask_all:
+            check_mask_all(samples, source)
         dice, sizes = _batch_front(samples, dice, rng, self.params)
         frame = source is not None or mask_frame
         metas = []
@@ -584,7 +622,8 @@ class DeviceAugmenter(_Augmenter):
         return self._run(samples, dice, rng, False)
 
     def call_with_boxes(self, samples, dice=None, rng=None):
-        """For ``train_both``: ``(img, heatmaps, heat_mask, bbox, metas)``.  The samples also carry ``instances`` / ``iscrowd`` — or
+        """For ``train_both``: ``(img, heatmaps, heat_mask, bbox, metas)``, with ``mask_all`` after ``heat_mask`` when the augmenter was
+        built with ``mask_all=True``.  The samples also carry ``instances`` / ``iscrowd`` — or
         ``segmentations`` / ``iscrowd`` — as for :class:`DeviceBBoxAugmenter`; the boxes are read under THIS chain's geometry (rotated
         ``objpos``), through the same kernel."""
         return self._run(samples, dice, rng, True)
@@ -605,6 +644,7 @@ class DeviceAugmenter(_Augmenter):
         # the table carries the masks' offsets with or without a mask buffer, as it always has
         mask_off = _aligned_offsets([g["H"] * g["W"] for g in metas])[0]
         stage_m = _pack_pinned([s["mask_miss"] for s in samples])[0] if source == "mask_miss" else None
+        stage_a = _pack_pinned([s["mask_all"] for s in samples])[0] if source == "mask_miss" and self.mask_all else None
         table = _pinned(B * T_COLS, torch.float64).view(B, T_COLS)
         maxP = max(1 + g["joint_others_out"].shape[0] for g in metas)
         joints = _pinned(B * maxP * 18 * 3, torch.float64).view(B, maxP, 18, 3).zero_()
@@ -619,25 +659,30 @@ class DeviceAugmenter(_Augmenter):
         d_img = stage_i.to(dev, non_blocking=True)
         d_table = table.to(dev, non_blocking=True)
         img = augment_image(d_img, d_table, S, S)
-        heat_mask = None
+        heat_mask = mask_all = d_all = None
         if source is not None:
             grid = int(S / self.stride)                               # COCO_data_pipeline.py:206-207
             if source == "person_anns":
                 # the planes are composed on the device at the offsets and pitch W the table rows carry
-                d_mask = segm.mask_miss_batch([s["person_anns"] for s in samples], [(g["H"], g["W"]) for g in metas], mask_off,
-                                              self.segm_strict, dev)[0]
+                compose = segm.person_masks_batch if self.mask_all else segm.mask_miss_batch
+                planes = compose([s["person_anns"] for s in samples], [(g["H"], g["W"]) for g in metas], mask_off, self.segm_strict, dev)
+                d_mask, d_all = planes[0], planes[1] if self.mask_all else None
             else:
                 d_mask = stage_m.to(dev, non_blocking=True)
+                d_all = stage_a.to(dev, non_blocking=True) if self.mask_all else None
             heat_mask = augment_mask(d_mask, d_table, grid, grid, self.stride, S)
+            if self.mask_all:
+                mask_all = augment_plane(d_all, d_table, grid, grid, self.stride, S, 0.0)      # nobody stands outside the image
         heatmaps = put_gaussian_maps(joints.to(dev, non_blocking=True), num.to(dev, non_blocking=True), S, S, self.stride,
                                      self.params["sigma"])
         # the pinned staging buffers may go out of scope here: torch's caching host allocator records the stream of a non_blocking
         # copy and hands a block out again only after that copy has finished
+        front = (img, heatmaps, heat_mask, mask_all) if self.mask_all else (img, heatmaps, heat_mask)
         if kind == "segmentations":
-            return img, heatmaps, heat_mask, _segm_boxes(metas, S, 1, dev)[0], metas
+            return front + (_segm_boxes(metas, S, 1, dev)[0], metas)
         if boxes:
-            return img, heatmaps, heat_mask, boxes_from_rects(rects, metas, S, 1, dev)[0], metas
-        return img, heatmaps, heat_mask, metas
+            return front + (boxes_from_rects(rects, metas, S, 1, dev)[0], metas)
+        return front + (metas,)
 
 
 class DeviceBBoxAugmenter(_Augmenter):

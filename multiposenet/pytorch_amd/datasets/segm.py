@@ -21,6 +21,11 @@ as a PNG written by a MATLAB step (``COCO_data_pipeline.py:244-250``) — comes 
 
 With at most one crowd per image this is what the known scripts compute; they refuse, or leave undefined, more than one crowd, and
 here every crowd contributes as above.  No instance mask is ever in memory (:func:`mask_miss_batch`).
+
+``mask_all`` — the target of the keypoint subnet's person-segmentation channel, which the reference would have read from the same
+MATLAB step — is the plain union: 255 where ANY person annotation (with keypoints, without, or a crowd) covers the pixel, else 0;
+independent of the order, all 0 for an empty list.  The compose launch's second instantiation (mpn_segm_person_masks) writes both
+planes from the registers it holds (:func:`person_masks_batch`).
 """
 import math
 
@@ -303,16 +308,17 @@ def annotation_kind(ann):
     return KIND_NO_KEYPOINTS if n <= 0 else KIND_KEYPOINTS
 
 
-def pack_mask_miss(anns, H, W, strict=True):
+def pack_mask_miss(anns, H, W, strict=True, keep_all=False):
     """The person annotations of one H x W image, in json order -> (:class:`SegmPack`, ``kinds`` int32 [n]) for mpn_segm_mask_miss.
 
     A KIND_KEYPOINTS annotation after the image's last crowd cannot change the result (``all`` is read by crowds only) and is
     dropped here, before anything is uploaded: most COCO images have no crowd, so only their KIND_NO_KEYPOINTS annotations get
-    rasterised.  Refusals: those of :func:`pack_segmentations`, an annotation without ``segmentation``, and the one of
+    rasterised.  ``keep_all`` (the two-plane form, mpn_segm_person_masks) drops nothing: everyone is part of ``mask_all``.
+    Refusals: those of :func:`pack_segmentations`, an annotation without ``segmentation``, and the one of
     :func:`annotation_kind`."""
     kinds = [annotation_kind(a) for a in anns]
     last_crowd = max([i for i, k in enumerate(kinds) if k == KIND_CROWD] or [-1])
-    keep = [i for i, k in enumerate(kinds) if k != KIND_KEYPOINTS or i < last_crowd]
+    keep = [i for i, k in enumerate(kinds) if keep_all or k != KIND_KEYPOINTS or i < last_crowd]
     segms = []
     for i in keep:
         if anns[i].get("segmentation") is None:
@@ -321,13 +327,14 @@ def pack_mask_miss(anns, H, W, strict=True):
     return pack_segmentations(segms, H, W, strict), np.asarray([kinds[i] for i in keep], dtype=np.int32)
 
 
-def pack_mask_miss_batch(list_of_anns, sizes, offsets=None, strict=True):
+def pack_mask_miss_batch(list_of_anns, sizes, offsets=None, strict=True, keep_all=False):
     """The host side of :func:`mask_miss_batch`: the images' packs as one, their kinds, and the int64 image table [B, 6] (H, W, the
-    image's instances [i0, i1), byte offset of its plane, row pitch W) -> (pack, kinds, imgs, offsets, bytes of the output)."""
+    image's instances [i0, i1), byte offset of its plane, row pitch W) -> (pack, kinds, imgs, offsets, bytes of the output).
+    ``keep_all``: as for :func:`pack_mask_miss` (the host side of :func:`person_masks_batch`)."""
     if len(list_of_anns) == 0 or len(list_of_anns) != len(sizes) or len(sizes) > MAX_INSTANCES:
         raise MpnError("a batch needs 1..%d images and one (H, W) for each" % MAX_INSTANCES)
     sizes = [(int(H), int(W)) for H, W in sizes]
-    packed = [pack_mask_miss(anns, H, W, strict) for anns, (H, W) in zip(list_of_anns, sizes)]
+    packed = [pack_mask_miss(anns, H, W, strict, keep_all) for anns, (H, W) in zip(list_of_anns, sizes)]
     if offsets is None:
         from .augment import _aligned_offsets
         offsets = _aligned_offsets([H * W for H, W in sizes])[0]
@@ -343,30 +350,57 @@ def pack_mask_miss_batch(list_of_anns, sizes, offsets=None, strict=True):
     return concat_packs([pk for pk, _ in packed]), np.concatenate([k for _, k in packed]), imgs, offsets, nbytes
 
 
-def mask_miss_batch(list_of_anns, sizes, offsets=None, strict=True, dev=None):
-    """``mask_miss`` of every image of a batch (``list_of_anns[b]`` the person annotations of image ``b`` in json order, an empty
-    list allowed; ``sizes[b]`` its (H, W)) -> (uint8 device buffer, byte offsets): image ``b`` is the row-major H x W plane at
-    ``offsets[b]`` (default: consecutive planes, each starting on a 16-byte boundary, the layout ``mpn_augment_mask`` reads); the
-    bytes between planes hold nothing.  One pinned upload and two launches for the whole batch; nothing waits for the device."""
+def _compose(list_of_anns, sizes, offsets, strict, dev, two):
+    """The device side of :func:`mask_miss_batch` (``two`` False) and :func:`person_masks_batch` (True): one pinned upload, the
+    toggle launches and one compose launch -> ([plane buffers], offsets)."""
     dev = _device() if dev is None else dev
-    pack, kinds, imgs, offsets, nbytes = pack_mask_miss_batch(list_of_anns, sizes, offsets, strict)
-    out = torch.empty(max((nbytes + 15) // 16 * 16, 16), dtype=torch.uint8, device=dev)
+    pack, kinds, imgs, offsets, nbytes = pack_mask_miss_batch(list_of_anns, sizes, offsets, strict, keep_all=two)
+    outs = [torch.empty(max((nbytes + 15) // 16 * 16, 16), dtype=torch.uint8, device=dev) for _ in range(2 if two else 1)]
     (insts, parts, verts, vpart, estart, toggles, d_imgs, d_kinds), _ = _upload(pack, dev, (imgs, kinds))
     ws_bytes = int(call("mpn_segm_workspace_bytes", pack.words))
     if ws_bytes <= 0:
         raise MpnError("mpn_segm_workspace_bytes refused %d words" % pack.words)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     n, npt, nv, nt = pack.n, int(pack.parts.shape[0]), int(pack.verts.shape[0]), int(pack.toggles.shape[0])
-    call("mpn_segm_mask_miss", ops.ptr(d_imgs), int(imgs.shape[0]), ops.ptr(insts) if n else None, ops.ptr(d_kinds) if n else None, n,
+    call("mpn_segm_person_masks" if two else "mpn_segm_mask_miss",
+         ops.ptr(d_imgs), int(imgs.shape[0]), ops.ptr(insts) if n else None, ops.ptr(d_kinds) if n else None, n,
          ops.ptr(parts) if npt else None, npt, ops.ptr(verts) if nv else None, ops.ptr(vpart) if nv else None, ops.ptr(estart), nv,
          int(pack.estart[-1]), ops.ptr(toggles) if nt else None, nt, int(imgs[:, M_W].max()), int(imgs[:, M_H].max()),
-         ops.ptr(out), out.numel(), ops.ptr(ws), ws_bytes, ops.stream_ptr())
-    return out, offsets
+         *([ops.ptr(o) for o in outs] + [outs[0].numel(), ops.ptr(ws), ws_bytes, ops.stream_ptr()]))
+    return outs, offsets
+
+
+def mask_miss_batch(list_of_anns, sizes, offsets=None, strict=True, dev=None):
+    """``mask_miss`` of every image of a batch (``list_of_anns[b]`` the person annotations of image ``b`` in json order, an empty
+    list allowed; ``sizes[b]`` its (H, W)) -> (uint8 device buffer, byte offsets): image ``b`` is the row-major H x W plane at
+    ``offsets[b]`` (default: consecutive planes, each starting on a 16-byte boundary, the layout ``mpn_augment_mask`` reads); the
+    bytes between planes hold nothing.  One pinned upload and two launches for the whole batch; nothing waits for the device."""
+    outs, offsets = _compose(list_of_anns, sizes, offsets, strict, dev, False)
+    return outs[0], offsets
+
+
+def person_masks_batch(list_of_anns, sizes, offsets=None, strict=True, dev=None):
+    """``mask_miss`` AND ``mask_all`` of every image of a batch, arguments as for :func:`mask_miss_batch`
+    -> (miss buffer, all buffer, byte offsets): two uint8 device buffers with image ``b``'s planes at ``offsets[b]`` of both.
+
+    ``mask_all`` is the target of the keypoint subnet's person-segmentation channel: 255 where ANY of the image's person
+    annotations covers the pixel — people with keypoints, people without, crowds — else 0; a plain union, independent of the
+    order; all 0 for an empty list.  Both planes leave the ONE compose launch (mpn_segm_person_masks) from the registers it
+    holds, so every annotation is packed here: the dropping rule of :func:`pack_mask_miss` does not apply.  The ``mask_miss``
+    bytes are those of :func:`mask_miss_batch`."""
+    outs, offsets = _compose(list_of_anns, sizes, offsets, strict, dev, True)
+    return outs[0], outs[1], offsets
 
 
 def mask_miss_from_annotations(anns, H, W):
     """``mask_miss`` of one H x W image from its person annotations in json order -> uint8 [H, W] on the device."""
     out, _ = mask_miss_batch([anns], [(H, W)])
+    return out[:int(H) * int(W)].view(int(H), int(W))
+
+
+def mask_all_from_annotations(anns, H, W):
+    """``mask_all`` of one H x W image from its person annotations -> uint8 [H, W] on the device (:func:`person_masks_batch`)."""
+    _, out, _ = person_masks_batch([anns], [(H, W)])
     return out[:int(H) * int(W)].view(int(H), int(W))
 
 

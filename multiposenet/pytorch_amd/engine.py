@@ -945,7 +945,7 @@ class Engine(object):
             cat = self.concat_up(ctx, [q5, q4, q3, q2], Ho, Wo)
             h, _ = self.conv(ctx, cat, m.conv2, act=1)
         pr, _ = self.conv(ctx, h, m.convfin, out_f32=True)
-        pred = self.export_internal(ctx, pr, "pred") if internal else self.export(ctx, pr, 18, Ho, Wo, "pred")
+        pred = self.export_internal(ctx, pr, "pred") if internal else self.export(ctx, pr, m.convfin.out_channels, Ho, Wo, "pred")
         return pred, saved
 
     def join_forward_side(self, ctx, device):

@@ -263,7 +263,7 @@ class Tester(object):
         with torch.no_grad():
             heatmaps, (scores, classification, transformed_anchors) = self.model([img_input, 'both'])
         param = {'thre1': 0.1, 'thre2': 0.05, 'thre3': 0.5}
-        joint_list = get_joint_list(img_resized, param, heatmaps[0].permute(1, 2, 0), scale, bool_gaussian_filt=self.params.gaussian_filt)
+        joint_list = get_joint_list(img_resized, param, heatmaps[0, :18].permute(1, 2, 0), scale, bool_gaussian_filt=self.params.gaussian_filt)
         bboxs = self._boxes(scores, classification, transformed_anchors, scale)
         return self.prn_process(self._body_joints(joint_list), bboxs, file_name, image_id)
 
@@ -320,6 +320,7 @@ class Tester(object):
     def _finish_batch(self, item, out, file_names, image_ids, post):
         """Detections, peaks and the PRN assignment of one batch whose network has been enqueued (infer_images_batched)."""
         idx, scales, heat, anchors, cls, keep, ev = item
+        heat = heat[:, :18]                                         # a person_seg model's channel 18 is the mask, not a heat-map
         if post is not None:
             post.wait_event(ev)
             with torch.cuda.stream(post):
@@ -499,7 +500,7 @@ class Tester(object):
             im_data = resnet_preprocess(im_cropped)[None]
             with torch.no_grad():
                 heatmaps, (scores, classification, transformed_anchors) = self.model([im_data, 'both'])
-            hm = heatmaps[0].permute(1, 2, 0)[:int(im_cropped.shape[0] / 4), :int(im_cropped.shape[1] / 4), :]
+            hm = heatmaps[0, :18].permute(1, 2, 0)[:int(im_cropped.shape[0] / 4), :int(im_cropped.shape[1] / 4), :]
             hm = resize(hm, (hm.shape[0] * 4, hm.shape[1] * 4), cubic=True)
             hm = hm[0:real_shape[0], 0:real_shape[1], :]
             hm = resize(hm, (H, W), cubic=True)
@@ -557,7 +558,7 @@ class Tester(object):
                     alive.append(keep)
                     heat = torch.cat([heat, heat1])
             hq, wq = int(hp / 4), int(wp / 4)
-            heat = heat[:, :, :hq, :wq]
+            heat = heat[:, :18, :hq, :wq]
             pair_maps.append(tta_upsample(heat, min(h, 4 * hq), min(w, 4 * wq)))       # only the region that survives the crop
             alive += [x, heat]
         return img, tta_merge(pair_maps, H, W), det, alive + pair_maps

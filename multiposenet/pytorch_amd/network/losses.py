@@ -60,6 +60,44 @@ def mse_backward_raw(pm, heat, wgt, gs, need):
     return grads
 
 
+SEG_OUT = 20        # MPN_MSE_SEG_OUT: the seg-aware result vector (include/mpn.h states its layout)
+
+
+def mse_seg_forward_raw(pm, heat_nhwc, wgt_nhwc, mask):
+    """:func:`mse_forward_raw` with the person-segmentation term: ``mask`` dense f32 [B,H,W] (mask_all), every prediction with a
+    nineteenth channel gets seg_j = mean((P_j[..,18] - mask)^2) / 100.  Returns out[SEG_OUT]: [0..7] as mse_forward_raw, [8..12]
+    the seg means, [13] their sum, [14] / [15] max / min of channel 18 of the final prediction, [16] the total."""
+    B, H, W, _ = pm[0].shape
+    npix = B * H * W
+    dev = pm[0].device
+    chunks, seg_chunks = call("mpn_mse_chunks", npix), call("mpn_mse_seg_chunks", npix)
+    part = ops.workspace((chunks + seg_chunks) * 8 * 4, dev, slot=5)
+    out = torch.empty(SEG_OUT, dtype=torch.float32, device=dev)
+    call("mpn_mse_heatmap_seg_forward", _vpx5(*[p.data_ptr() for p in pm]), _i64x5(*[p.stride(2) for p in pm]),
+         _i32x5(*[p.shape[3] for p in pm]), ops.ptr(heat_nhwc), ops.ptr(wgt_nhwc), ops.ptr(mask), npix, ops.ptr(part), chunks,
+         ctypes.c_void_p(part.data_ptr() + chunks * 8 * 4), seg_chunks, ops.ptr(out), ops.stream_ptr())
+    return out
+
+
+def mse_seg_backward_raw(pm, heat, wgt, mask, gs, need):
+    """:func:`mse_backward_raw` with the seg term: channel 18 of every needed level that has one carries
+    gs * 2 * (P - mask) / (100 * B*H*W) instead of 0; channels < 18 are the same bits."""
+    B, H, W, _ = pm[0].shape
+    npix = B * H * W
+    grads, gptr, gsp, gc = [], [], [], []
+    for j, p in enumerate(pm):
+        if need[j]:
+            g = torch.empty((B, H, W, p.shape[3]), dtype=torch.float32, device=p.device)
+            grads.append(g.permute(0, 3, 1, 2))
+            gptr.append(g.data_ptr()); gsp.append(g.stride(2)); gc.append(p.shape[3])
+        else:
+            grads.append(None)
+            gptr.append(None); gsp.append(0); gc.append(0)
+    call("mpn_mse_heatmap_seg_backward", _vpx5(*[p.data_ptr() for p in pm]), _vpx5(*gptr), _i64x5(*[p.stride(2) for p in pm]),
+         _i64x5(*gsp), _i32x5(*gc), ops.ptr(heat), ops.ptr(wgt), ops.ptr(mask), npix, ops.ptr(gs), ops.stream_ptr())
+    return grads
+
+
 def mse_train_supported(levels, heat, wgt=None):
     """The one-pass form needs every intermediate level at an exact power-of-two fraction of a heat-map whose sides are multiples
     of 8 (true of the reference's 480x480 / 384x384 training crops), and dense NCHW f32 targets.  The kernel reads the weights with
@@ -96,6 +134,35 @@ def mse_train_raw(levels, heat, wgt, gs, dtype):
     return out, grads
 
 
+def mse_seg_train_supported(levels, heat, wgt, mask):
+    """:func:`mse_train_supported`, and ``mask`` a dense f32 [B,1,H,W] on a 16-byte boundary (the kernel reads it with 16-byte loads)."""
+    if not mse_train_supported(levels, heat, wgt):
+        return False
+    B, _, H, W = heat.shape
+    return (mask.dtype == torch.float32 and tuple(mask.shape) == (B, 1, H, W) and mask.is_contiguous() and mask.data_ptr() % 16 == 0
+            and mask.device == heat.device and all(18 <= a.C <= 32 for a in levels))
+
+
+def mse_seg_train_raw(levels, heat, wgt, mask, gs, dtype):
+    """:func:`mse_train_raw` with the person-segmentation term (mpn_mse_heatmap_seg_train): lane 18 of every level with a nineteenth
+    channel is live against ``mask`` (f32 [B,1,H,W], read in place).  Returns (out[SEG_OUT] as mse_seg_forward_raw, five internal
+    gradient activations of ``dtype``); the gradients are bit-identical to mse_seg_backward_raw + ops.import_grad."""
+    if not mse_seg_train_supported(levels, heat, wgt, mask):
+        from .._lib import MpnError
+        raise MpnError("one-pass heat-map + seg loss: levels or targets do not fit the kernel (see mse_seg_train_supported); heat %s %s, "
+                       "wgt %s %s, mask %s %s" % (tuple(heat.shape), heat.dtype, tuple(wgt.shape), wgt.dtype, tuple(mask.shape), mask.dtype))
+    B, _, H, W = heat.shape
+    dev = heat.device
+    blocks = call("mpn_mse_train_blocks", B, H, W)
+    part = ops.workspace(blocks * 16 * 4, dev, slot=5)
+    out = torch.empty(SEG_OUT, dtype=torch.float32, device=dev)
+    grads = [ops.Act(torch.empty(a.t.shape, dtype=dtype, device=dev), a.C) for a in levels]
+    call("mpn_mse_heatmap_seg_train", _vpx5(*[a.t.data_ptr() for a in levels]), _vpx5(*[g.t.data_ptr() for g in grads]),
+         _i32x5(*[a.Cs for a in levels]), _i32x5(*[a.C for a in levels]), ops.dtype_code(dtype), ops.ptr(heat), ops.ptr(wgt), ops.ptr(mask),
+         heat.stride(0), heat.stride(1), heat.stride(2), B, H, W, ops.ptr(gs), ops.ptr(part), blocks, ops.ptr(out), ops.stream_ptr())
+    return out, grads
+
+
 class _HeatmapMSE(torch.autograd.Function):
     """sum_j mean(((pred_j[:, :18] * w) - (w * gt))^2)   (posenet.py:376-387)."""
 
@@ -114,6 +181,27 @@ class _HeatmapMSE(torch.autograd.Function):
         gs = gtotal.detach().reshape(1).float().contiguous()
         grads = mse_backward_raw(ctx.pm, heat, wgt, gs, [ctx.needs_input_grad[2 + j] for j in range(len(ctx.pm))])
         return (None, None) + tuple(grads)
+
+
+class _HeatmapSegMSE(torch.autograd.Function):
+    """_HeatmapMSE + sum_j mean((pred_j[:, 18] - mask_all)^2) / 100 over the predictions with a nineteenth channel (the reference's
+    commented-out loss2, posenet.py:374-401)."""
+
+    @staticmethod
+    def forward(ctx, heat_nhwc, wgt_nhwc, mask, *preds):
+        pm = [_pixel_major(p.detach()) for p in preds]
+        out = mse_seg_forward_raw(pm, heat_nhwc, wgt_nhwc, mask)
+        ctx.pm = pm
+        ctx.gt = (heat_nhwc, wgt_nhwc, mask)
+        ctx.mark_non_differentiable(out)
+        return out[16].clone(), out
+
+    @staticmethod
+    def backward(ctx, gtotal, _gout):
+        heat, wgt, mask = ctx.gt
+        gs = gtotal.detach().reshape(1).float().contiguous()
+        grads = mse_seg_backward_raw(ctx.pm, heat, wgt, mask, gs, [ctx.needs_input_grad[3 + j] for j in range(len(ctx.pm))])
+        return (None, None, None) + tuple(grads)
 
 
 class _LazyVec(object):
@@ -269,12 +357,46 @@ def _check_heatmap_targets(preds, heat_temp, heat_weight):
     return out
 
 
-def build_keypoint_loss(saved_for_loss, heat_temp, heat_weight):
-    """posenet.py:367-403: returns (total_loss tensor with grad, OrderedDict of floats)."""
+def _check_mask_all(preds, mask_all):
+    from .._lib import MpnError
+    p0 = preds[0]
+    B, _, H, W = p0.shape
+    if not isinstance(mask_all, torch.Tensor) or tuple(mask_all.shape) != (B, 1, H, W):
+        raise MpnError("heat-map loss: mask_all has shape %s, expected [%d, 1, %d, %d]"
+                       % (tuple(mask_all.shape) if isinstance(mask_all, torch.Tensor) else type(mask_all).__name__, B, H, W))
+    if mask_all.device != p0.device:
+        raise MpnError("heat-map loss: mask_all is on %s, the predictions on %s" % (mask_all.device, p0.device))
+    return mask_all.detach().float().contiguous()              # [B,1,H,W] dense is [B,H,W] pixel-major
+
+
+def build_keypoint_loss(saved_for_loss, heat_temp, heat_weight, mask_all=None):
+    """posenet.py:367-403: returns (total_loss tensor with grad, OrderedDict of floats).
+
+    ``mask_all`` (f32 [B,1,H,W] in [0, 1], the person-segmentation target) adds the reference's commented-out seg term: for every
+    prediction with a nineteenth channel ``seg = mean((pred[:, 18] - mask_all)^2) / 100``, not weighted by ``heat_weight``, summed
+    into the total.  The log then follows build_names(): ``heatmap_loss_k2, seg_loss_k2, ..., heatmap_loss``, ``seg_loss`` (only
+    when the final prediction has the channel, a ``person_seg`` model), ``max_ht, min_ht`` and, for such a model, ``max_mask,
+    min_mask``.  Without it the path below runs as it always has, and channel 18 gets a zero gradient."""
     names = build_names()
     heat_temp, heat_weight = _check_heatmap_targets(saved_for_loss[:5], heat_temp, heat_weight)
+    mask = None if mask_all is None else _check_mask_all(saved_for_loss[:5], mask_all)
     heat = ops.nchw_to_nhwc_f32(heat_temp.detach().float())
     wgt = ops.nchw_to_nhwc_f32(heat_weight.detach().float())
+    if mask is not None:
+        total, out = _HeatmapSegMSE.apply(heat, wgt, mask, *saved_for_loss[:5])
+        vals = _log_values(out)
+        person_seg = saved_for_loss[4].shape[1] >= 19
+        log = OrderedDict()
+        for j in range(5):
+            log[names[j * 2]] = vals[j]
+            if j < 4 or person_seg:
+                log[names[j * 2 + 1]] = vals[8 + j]
+        log['max_ht'] = vals[6]
+        log['min_ht'] = vals[7]
+        if person_seg:
+            log['max_mask'] = vals[14]
+            log['min_mask'] = vals[15]
+        return total, log
     total, out = _HeatmapMSE.apply(heat, wgt, *saved_for_loss[:5])
     vals = _log_values(out)         # one asynchronous D2H copy instead of the reference's seven .item() syncs
     log = OrderedDict()

@@ -140,8 +140,14 @@ class _NetFn(torch.autograd.Function):
 
 
 class poseNet(nn.Module):
-    def __init__(self, layers, prn_node_count=1024, prn_coeff=2, compute_dtype=torch.bfloat16, device=None, num_classes=1):
+    def __init__(self, layers, prn_node_count=1024, prn_coeff=2, compute_dtype=torch.bfloat16, device=None, num_classes=1,
+                 person_seg=False):
+        """``person_seg=True`` gives the final ``convfin`` the nineteenth output the intermediate ``convfin_k*`` already have: the
+        person-segmentation mask of the MultiPoseNet paper's keypoint subnet, trained from ``mask_all`` (build_keypoint_loss).
+        ``model([img, 'keypoint_subnet'])`` and ``forward_heat`` then return 19 channels, channel 18 being the mask.  It changes the
+        shape of ``convfin`` in the ``state_dict``, hence opt-in; an 18-row checkpoint does not load into it."""
         super(poseNet, self).__init__()
+        self.person_seg = bool(person_seg)
         if layers == 101:
             self.fpn = FPN101()
         elif layers == 50:
@@ -166,7 +172,7 @@ class poseNet(nn.Module):
         self.upsample3 = nn.Upsample(scale_factor=2, mode='nearest', align_corners=None)
         self.concat = Concat()
         self.conv2 = _conv(512, 256, 3, 1)
-        self.convfin = _conv(256, 18, 1)
+        self.convfin = _conv(256, 19 if self.person_seg else 18, 1)
         # detection subnet (posenet.py:188-194)
         self.regressionModel = RegressionModel(256)
         self.classificationModel = ClassificationModel(256, num_classes=num_classes, device="meta")     # the reference pins 1
@@ -565,13 +571,14 @@ class poseNet(nn.Module):
         """posenet.py:352-364."""
         subnet_name = args[0]
         if subnet_name == 'keypoint_subnet':
-            return build_keypoint_loss(saved_for_loss, args[1], args[2])
+            # an optional fourth element: mask_all, the person-segmentation target
+            return build_keypoint_loss(saved_for_loss, args[1], args[2], args[3] if len(args) > 3 else None)
         elif subnet_name == 'detection_subnet':
             return build_detection_loss(saved_for_loss, args[1])
         elif subnet_name == 'prn_subnet':
             return build_prn_loss(saved_for_loss, args[1])
         elif subnet_name == 'train_both':
-            kp_loss, kp_log = build_keypoint_loss(saved_for_loss[0], args[1], args[2])
+            kp_loss, kp_log = build_keypoint_loss(saved_for_loss[0], args[1], args[2], args[4] if len(args) > 4 else None)
             det_loss, det_log = build_detection_loss(saved_for_loss[1], args[3])
             log = OrderedDict(kp_log)
             log.update(det_log)

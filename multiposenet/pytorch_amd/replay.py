@@ -30,6 +30,8 @@ the optimizer's device vector: changing ``step.max_grad_norm`` does not re-recor
 The parameters after a step are bit-identical to the eager step's (same kernels, same order, same scratch sizes; the heat-map
 loss runs as one launch over the internal tensors whose gradients round exactly as the API path's export -> loss -> import chain,
 and whose logged loss values agree to f32 summation order: tests/test_replay_gpu.py).
+A step with ``mask_all`` (one more tensor after the subnet's own, part of the signature) runs that launch in its seg-aware
+instantiation, or the seg-aware forward / backward pair where it does not fit (tests/test_person_seg_gpu.py).
 Re-recorded when the model moves, the set of trainable parameters / BN modes / compute dtype changes, or a new input
 signature arrives.
 
@@ -124,33 +126,46 @@ class ReplayedTrainStep(object):
         # heat-map loss: one launch over the network's internal tensors where the geometry allows (losses.mse_train_supported),
         # else the API path's export -> loss -> import chain.  Both produce the same gradient bits.
         fused_mse = False
+        # mask_all, the person-segmentation target: one more tensor after the subnet's own (its presence is part of the key); the
+        # one-pass kernel's seg-aware instantiation reads it in place, the API path's chain below takes it where that does not fit
+        n_own = 3 if subnet == "train_both" else 2
+        mask = tensors[n_own] if want_kp and len(tensors) > n_own else None
         if want_kp:
             hp = kp_feats[0]
+            if mask is not None and tuple(mask.shape) != (hp.B, 1, hp.H, hp.W):
+                raise _lib.MpnError("recorded train step: mask_all has shape %s, expected [%d, 1, %d, %d]"
+                                    % (tuple(mask.shape), hp.B, hp.H, hp.W))
             fused_mse = self.fused_mse and tensors[0].shape == (hp.B, 18, hp.H, hp.W) and hp.H % 8 == 0 and hp.W % 8 == 0 \
-                and tensors[0].shape == tensors[1].shape
+                and tensors[0].shape == tensors[1].shape and (mask is None or mask.data_ptr() % 16 == 0)
         pred, saved, cls, reg = m._heads(ctx, kp_feats, det_feats, True, internal=fused_mse)
-        if fused_mse and not losses.mse_train_supported(saved + [pred], tensors[0], tensors[1]):
+        if fused_mse and not (losses.mse_train_supported(saved + [pred], tensors[0], tensors[1]) if mask is None
+                              else losses.mse_seg_train_supported(saved + [pred], tensors[0], tensors[1], mask)):
             raise _lib.MpnError("recorded train step: the keypoint head's internal geometry does not fit the one-pass loss kernel; "
                                 "construct ReplayedTrainStep(..., fused_mse=False)")
         dev = img.device
         ones = self._ones(dev)
         if want_kp and fused_mse:      # d(total)/d(heat-map total) = 1, known before the loss value is: gradients in the same pass
-            kp8, kgrads = losses.mse_train_raw(saved + [pred], tensors[0], tensors[1], ones, eng.cdt)
+            if mask is None:
+                kp8, kgrads = losses.mse_train_raw(saved + [pred], tensors[0], tensors[1], ones, eng.cdt)
+            else:
+                kp8, kgrads = losses.mse_seg_train_raw(saved + [pred], tensors[0], tensors[1], mask, ones, eng.cdt)
             grads.update(zip(("k0", "k1", "k2", "k3", "pred"), kgrads))
         elif want_kp:
             heat = ops.nchw_to_nhwc_f32(tensors[0].detach().float())
             wgt = ops.nchw_to_nhwc_f32(tensors[1].detach().float())
             pm = [losses._pixel_major(p) for p in saved + [pred]]
-            kp8 = losses.mse_forward_raw(pm, heat, wgt)
+            kp8 = losses.mse_forward_raw(pm, heat, wgt) if mask is None else losses.mse_seg_forward_raw(pm, heat, wgt, mask)
         if want_det:
             anno = tensors[2] if want_kp else tensors[0]
             det2, fsaved = losses.focal_forward_raw(cls, reg, m.anchors(img), anno)
         clip = self.max_grad_norm is not None
-        logv = torch.zeros(13 if clip else 12, dtype=torch.float32, device=dev)
-        _lib.call("mpn_step_log", ops.ptr(kp8), ops.ptr(det2), ops.ptr(logv), ops.stream_ptr())
+        logv = torch.zeros(21 if mask is not None else (13 if clip else 12), dtype=torch.float32, device=dev)
+        _lib.call("mpn_step_log" if mask is None else "mpn_step_log_seg", ops.ptr(kp8), ops.ptr(det2), ops.ptr(logv), ops.stream_ptr())
         self.opt.zero_grad()
         if want_kp and not fused_mse:      # d(total)/d(heat-map total) = 1 (posenet.py:387 sums the level losses; the combined step adds the two totals)
-            for slot, g in zip(("k0", "k1", "k2", "k3", "pred"), losses.mse_backward_raw(pm, heat, wgt, ones, [True] * 5)):
+            kgrads = losses.mse_backward_raw(pm, heat, wgt, ones, [True] * 5) if mask is None \
+                else losses.mse_seg_backward_raw(pm, heat, wgt, mask, ones, [True] * 5)
+            for slot, g in zip(("k0", "k1", "k2", "k3", "pred"), kgrads):
                 grads[slot] = g
         if want_det:     # d(total)/d(cls loss) = d(total)/d(reg loss) = 1 (posenet.py:417-421)
             grads["cls"], grads["reg"] = losses.focal_backward_raw(fsaved, ones)
@@ -165,6 +180,8 @@ class ReplayedTrainStep(object):
                 total = self.opt.clip_grad_norm_inf_(self.max_grad_norm)
                 _lib.call("mpn_copy_bytes", ctypes.c_void_p(logv.data_ptr() + 4 * 12), ops.ptr(total), 4, ops.stream_ptr())
             self.opt.step()
+        if mask is not None:
+            want_kp = "seg19" if m.convfin.out_channels >= 19 else "seg"
         return logv, want_kp, want_det
 
     @property
@@ -192,7 +209,14 @@ class ReplayedTrainStep(object):
         names = []
         if want_kp == "prn":
             return [("PRN loss", 11)]
-        if want_kp:
+        if want_kp in ("seg", "seg19"):       # a step with mask_all: build_keypoint_loss's keys, from mpn_step_log_seg's vector
+            kn = losses.build_names()
+            for j in range(5):
+                names.append((kn[j * 2], j))
+                if j < 4 or want_kp == "seg19":
+                    names.append((kn[j * 2 + 1], 13 + j))
+            names += [("max_ht", 6), ("min_ht", 7)] + ([("max_mask", 19), ("min_mask", 20)] if want_kp == "seg19" else [])
+        elif want_kp:
             kn = losses.build_names()
             names += [(kn[j * 2], j) for j in range(5)] + [("max_ht", 6), ("min_ht", 7)]
         if want_det:
@@ -240,6 +264,12 @@ class ReplayedTrainStep(object):
             ai = 2 if subnet == "train_both" else 0
             if ai < len(tensors) and tensors[ai].dim() == 3:
                 tensors[ai] = self._bucket_annotations(tensors[ai])
+        n_own = {"keypoint_subnet": 2, "train_both": 3}.get(subnet)
+        if n_own is not None and len(tensors) > n_own:         # mask_all: [B, 1, H, W] next to the [B, 18, H, W] heat-maps, before any launch
+            want = (tensors[0].shape[0], 1) + tuple(tensors[0].shape[2:])
+            if tensors[n_own].dim() != 4 or tuple(tensors[n_own].shape) != want or tensors[n_own].device != tensors[0].device:
+                raise _lib.MpnError("recorded train step: mask_all has shape %s on %s, expected %s on %s"
+                                    % (tuple(tensors[n_own].shape), tensors[n_own].device, want, tensors[0].device))
         key = (subnet, tuple(img.shape), img.dtype, tuple((tuple(t.shape), t.dtype) for t in tensors))
         if prn:
             # host half of the device-seeded dropout, outside the launch list: the seed word is (re)uploaded when the host's mirror

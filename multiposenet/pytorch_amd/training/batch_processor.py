@@ -25,18 +25,22 @@ def batch_processor(state, batch):
     grad_ctx = torch.enable_grad() if state.model.training else torch.no_grad()
     with grad_ctx:
         if subnet_name == 'keypoint_subnet':
-            inp, heat_temp, heat_weight = batch
+            inp, heat_temp, heat_weight = batch[:3]
             input_var = inp.to(dev, non_blocking=True)
             gts = [subnet_name, heat_temp.to(dev, non_blocking=True), heat_weight.to(dev, non_blocking=True)]
+            if len(batch) > 3:                  # mask_all [B, 1, h, w]: the person-segmentation target (build_keypoint_loss)
+                gts.append(batch[3].to(dev, non_blocking=True))
         elif subnet_name == 'detection_subnet':
             inp, anno = batch                   # anno: [x1, y1, x2, y2, category_id], padded with -1
             input_var = inp.to(dev, non_blocking=True)
             gts = [subnet_name, anno.to(dev, non_blocking=True)]
         elif subnet_name == 'train_both':       # SURVEY.md 8d combined step
-            inp, heat_temp, heat_weight, anno = batch
+            inp, heat_temp, heat_weight, anno = batch[:4]
             input_var = inp.to(dev, non_blocking=True)
             gts = [subnet_name, heat_temp.to(dev, non_blocking=True), heat_weight.to(dev, non_blocking=True),
                    anno.to(dev, non_blocking=True)]
+            if len(batch) > 4:                  # mask_all, after the annotations
+                gts.append(batch[4].to(dev, non_blocking=True))
         else:                                   # 'prn_subnet'
             inp, label = batch
             input_var = inp.to(dev, non_blocking=True).float()
