@@ -840,6 +840,87 @@ typedef struct MpnTtaScale {
 int mpn_tta_merge(const MpnTtaScale* scales, int n_scales, const int32_t* swap, float* out, int H, int W, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Person masks at inference: channel 18 of a person_seg model's maps -> an image-sized binary mask, and its score against
+ * mask_all (csrc/seg_infer.hip; evaluate/tester.py: return_masks, Tester.seg_eval).  The reference never ran this channel, so the
+ * definitions are this project's own; they are the op sequences the unfused Tester paths use for channels 0..17.
+ *
+ * q is channel 18 of the exported float32 maps of one image, thr a float32.
+ *
+ * Single scale (infer_image, infer_images_batched).  The image is H x W, D = max(H, W); it was zero-padded at the bottom and right
+ * to D x D and resized to S x S, so q is [S/4, S/4].  The plane is
+ *     P = resize(q[:, :, None], (D, D), cubic=True)[:H, :W, 0]
+ * with resize the dsize form of mpn_resize, scale (S/4) / D on both axes; only the H x W corner of the D x D grid is computed.
+ *
+ * Multi-scale + flip (infer_image_multiscale and its fused forms): _get_outputs applied to channel 18.  Per scale: q[:hp/4, :wp/4],
+ * x4 up-sampling with the cubic mpn_resize (scale 0.25 exactly), crop to the unpadded (h, w), cubic mpn_resize to (H, W) in the
+ * dsize form, times float32(1 / n), added into a float64 accumulator.  The pass over the mirrored image is accumulated separately
+ * and read back at column W - 1 - x; a mask has no left/right twin, so no channel is permuted.
+ *     P = float32((a_o + a_f) / 2)
+ *
+ * Mask.  M = 255 where P > thr, else 0, uint8.  The comparison is strict; a NaN gives 0.
+ *
+ * Score.  A byte is ON when it is non-zero.  Per image three int64 counts: inter, pred, gt; union = pred + gt - inter.  The summary is
+ * formed on the host in float64 from the exact integers (evaluate/seg_eval.py: summarize_counts):
+ *     iou = sum(inter) / sum(union);   mean_iou = mean of inter / union over the images with union > 0 (the others: n_empty);
+ *     precision = sum(inter) / sum(pred);   recall = sum(inter) / sum(gt);   pixel_acc = sum(N - union + inter) / sum(N), N = H * W.
+ *
+ * The image table of mpn_segm_rasterize owns the MPN_SEGI_ prefix; the view table of mpn_seg_masks is MPN_SEGV_.
+ * -------------------------------------------------------------------------------------------*/
+
+/* mpn_seg_masks: mask (and optionally plane) of every image of a single-scale batch in one launch.
+ * src: float32; the [Hs][Ws] map of image b is element (y, x) at src[SRC_OFF + y*sY + x*sX]; src_floats: floats readable from src.
+ * imgs: int64 [n_img][MPN_SEGV_COLS] (device): float offset of the image's map in src; D, H, W; byte offset and row pitch of its
+ *   H x W uint8 mask in `out`; float offset of its dense [H][W] plane in `planes` (ignored when planes is null).
+ * out: uint8, out_bytes long.  planes: float32, plane_floats long, or null with plane_floats 0.
+ * Grid: 64-column tiles up to max_w, 16-row tiles up to max_h, images.  A lane produces four consecutive pixels of a row and stores
+ * their mask bytes as one word where the plane start and the pitch are multiples of 4 and the four lie inside the row, byte by byte
+ * otherwise.  Every byte of every H x W plane is written, nothing between planes.  A row whose map leaves src, whose mask leaves
+ * out, whose plane leaves planes, with D < max(H, W), H > max_h or W > max_w is skipped, never dereferenced.
+ * MPN_E_BADARG before any HIP call: null or misaligned pointer, non-positive size or stride, n_img outside 1..65535, max_w / max_h
+ * outside 1..65536, out_bytes / src_floats / plane_floats outside 1..2^40 (plane_floats != 0 without planes), src_floats too small for
+ * one [Hs][Ws] map, or two of src, out, planes overlapping.  Nothing is allocated or synchronised. */
+#define MPN_SEGV_SRC_OFF 0
+#define MPN_SEGV_D 1
+#define MPN_SEGV_H 2
+#define MPN_SEGV_W 3
+#define MPN_SEGV_OUT_OFF 4
+#define MPN_SEGV_OUT_PITCH 5
+#define MPN_SEGV_PLANE_OFF 6
+#define MPN_SEGV_COLS 7
+int mpn_seg_masks(const float* src, int64_t sY, int64_t sX, int Hs, int Ws, int64_t src_floats, const int64_t* imgs, int n_img,
+                  int max_w, int max_h, float thr, uint8_t* out, int64_t out_bytes, float* planes, int64_t plane_floats,
+                  void* stream);
+
+/* mpn_tta_merge_mask: the multi-scale + flip merge of channel 18 in one launch.  scales: the HOST table of mpn_tta_merge with seg
+ * pair maps: element (y, x, ch) at u[y*pitch + x*2 + ch], ch 0 from the pass over the original image, ch 1 from the pass over the
+ * mirrored one, pitch >= 2 * rw, 1..8 scales.  With R and r as for mpn_tta_merge:
+ *   a_o = sum over the table, in order, of (double)(R(U_s, y, x, 0) * r);   a_f = ... of (double)(R(U_s, y, W - 1 - x, 1) * r)
+ *   P[y][x] = (float)((a_o + a_f) / 2);   M[y][x] = P[y][x] > thr ? 255 : 0
+ * plane: dense float32 [H][W] or null; mask: uint8, row pitch mask_pitch >= W, or null; not both null.  No accumulator plane in
+ * memory.  MPN_E_BADARG before any HIP call for a null table, both outputs null, n_scales outside 1..8, H or W outside 1..65536, a
+ * pitch below 2 * rw, mask_pitch < W, or plane and mask overlapping. */
+int mpn_tta_merge_mask(const MpnTtaScale* scales, int n_scales, int H, int W, float thr, float* plane, uint8_t* mask,
+                       int64_t mask_pitch, void* stream);
+
+/* mpn_mask_iou: counts[b] = (inter, pred, gt) of image b: the bytes that are non-zero in both planes, in the prediction, in the
+ * ground truth.  imgs: int64 [n_img][MPN_MIOU_COLS] (device): H, W, then byte offset and row pitch of the plane in pred and in gt.
+ * counts: int64 [n_img][3]; the call zeroes it on the stream and writes every element.  Lanes read 16 bytes where both plane starts
+ * and pitches are multiples of 16, 8 where of 8, single bytes otherwise and in a row's tail.  Integer sums in registers, the wave,
+ * LDS, then one integer atomic add per workgroup (32 rows of an image) and counter: the counts are identical on every run.
+ * A row whose plane leaves its buffer or with H > max_h is skipped (its counts stay 0), never dereferenced.
+ * MPN_E_BADARG before any HIP call: null or misaligned pointer, n_img outside 1..65535, max_h outside 1..65536, pred_bytes / gt_bytes
+ * outside 1..2^40, counts overlapping pred or gt.  Nothing is allocated or synchronised. */
+#define MPN_MIOU_H 0
+#define MPN_MIOU_W 1
+#define MPN_MIOU_PRED_OFF 2
+#define MPN_MIOU_PRED_PITCH 3
+#define MPN_MIOU_GT_OFF 4
+#define MPN_MIOU_GT_PITCH 5
+#define MPN_MIOU_COLS 6
+int mpn_mask_iou(const uint8_t* pred, int64_t pred_bytes, const uint8_t* gt, int64_t gt_bytes, const int64_t* imgs, int n_img,
+                 int max_h, int64_t* counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Pose-residual-network person assignment, device half (evaluate/tester.py:333-513; crop/gaussian helpers
  * datasets/coco_data/prn_gaussian.py:2,134-158).
  * mpn_prn_build_maps: for nboxes boxes (x, y, w, h doubles; box_img[b] = image of box b) and the heat-map peaks of their

@@ -93,6 +93,9 @@ SIGNATURES = {
     "mpn_resize": (_i, [_vp, _i64, _i64, _i64, _i, _i, _i, _vp, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),
     "mpn_tta_input": (_i, [_vp, _i64, _i64, _i64, _i, _i, _vp, _i, _i, _i, _i, ctypes.c_double, _vp]),
     "mpn_tta_merge": (_i, [ctypes.POINTER(TtaScale), _i, ctypes.POINTER(ctypes.c_int32), _vp, _i, _i, _vp]),
+    "mpn_seg_masks": (_i, [_vp, _i64, _i64, _i, _i, _i64, _vp, _i, _i, _i, _f, _vp, _i64, _vp, _i64, _vp]),
+    "mpn_tta_merge_mask": (_i, [ctypes.POINTER(TtaScale), _i, _i, _i, _f, _vp, _vp, _i64, _vp]),
+    "mpn_mask_iou": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _vp]),
     "mpn_prn_build_maps": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     "mpn_prn_scores": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mpn_prn_scores_compact": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

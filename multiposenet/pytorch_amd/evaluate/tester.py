@@ -60,6 +60,7 @@ class TestParams(object):
     gaussian_filt = False             # NMS(..., bool_gaussian_filt=True): smooth every up-sampled peak patch (sigma 3) before its arg-max
     category_ids = [1]                # detect_images / coco_eval_bbox: class index of the detection head -> COCO category id
     tta_fused = False                 # coco_eval: the fused, flip-paired test-time augmentation (infer_images_multiscale; same results)
+    mask_thresh = 0.5                 # return_masks / person_masks / seg_eval: mask = 255 where the channel-18 plane > mask_thresh (not in the reference)
     nms_per_class = False             # detect_images / coco_eval_bbox: every (anchor, class) score is a candidate, NMS per class (not in the reference)
 
 
@@ -143,6 +144,80 @@ def tta_merge(pair_maps, H, W, swap=SWAP_HEAT):
     return out
 
 
+def _thr32(thr):
+    return float(np.float32(thr))       # the threshold is a float32: the same value for the tensor library's compare and the kernels
+
+
+def _mask_views(sizes, dev):
+    """One uint8 buffer for the H x W masks of ``sizes``, every plane starting on a 16-byte boundary, pitch W -> (buffer, offsets, views)."""
+    from ..datasets.augment import _aligned_offsets
+    offsets, total = _aligned_offsets([int(H) * int(W) for H, W in sizes])
+    buf = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+    return buf, offsets, [buf[o:o + int(H) * int(W)].view(int(H), int(W)) for o, (H, W) in zip(offsets, sizes)]
+
+
+def seg_masks(heat, geometry, thr, planes=False):
+    """mpn_seg_masks: the person masks of a single-scale batch in one launch.  heat: float32 CUDA [B, 19, hq, wq] maps of a person_seg
+    model (any positive strides; channel 18 is read in place); geometry: the (H, W) of every image — it was zero-padded to D x D,
+    D = max(H, W), before the resize to the network input.  -> list of uint8 [H, W] masks (views of one buffer, 16-byte-aligned starts,
+    pitch W), 255 where ``resize(q[:, :, None], (D, D), cubic=True)[:H, :W, 0] > thr``; with ``planes`` also the list of those float32
+    planes."""
+    B = int(heat.shape[0])
+    if heat.dtype != torch.float32 or heat.dim() != 4 or heat.shape[1] < 19 or len(geometry) != B or B < 1:
+        raise ValueError("seg_masks: float32 [B, 19, hq, wq] maps and one (H, W) per image expected")
+    if min(heat.stride(2), heat.stride(3)) <= 0 or (B > 1 and heat.stride(0) <= 0):
+        raise ValueError("seg_masks: maps with positive strides expected")
+    sizes = [(int(H), int(W)) for H, W in geometry]
+    buf, offsets, views = _mask_views(sizes, heat.device)
+    q = heat[:, 18]
+    table = np.zeros((B, 7), dtype=np.int64)
+    poff = 0
+    for b, ((H, W), off) in enumerate(zip(sizes, offsets)):
+        table[b] = (b * heat.stride(0), max(H, W), H, W, off, W, poff)
+        poff += H * W
+    pl = torch.empty(poff, dtype=torch.float32, device=heat.device) if planes else None
+    hq, wq = int(heat.shape[2]), int(heat.shape[3])
+    span = (B - 1) * heat.stride(0) + (hq - 1) * heat.stride(2) + (wq - 1) * heat.stride(3) + 1
+    d_table = torch.from_numpy(table).to(heat.device)
+    call("mpn_seg_masks", ops.ptr(q), heat.stride(2), heat.stride(3), hq, wq, span, ops.ptr(d_table), B, max(W for _, W in sizes),
+         max(H for H, _ in sizes), _thr32(thr), ops.ptr(buf), buf.numel(), ops.ptr(pl) if planes else None, poff if planes else 0,
+         ops.stream_ptr())
+    if not planes:
+        return views
+    return views, [pl[o:o + H * W].view(H, W) for o, (H, W) in zip(table[:, 6].tolist(), sizes)]
+
+
+def tta_seg_upsample(heat, rh, rw):
+    """The seg pair map of one scale: channel 18 of heat [2, 19, hq, wq], read in place as one two-channel image (channel stride =
+    heat.stride(0)), the first rh x rw of its x4 INTER_CUBIC map -> float32 [rh, rw, 2].  One mpn_resize."""
+    u = torch.empty((rh, rw, 2), dtype=torch.float32, device=heat.device)
+    call("mpn_resize", ops.ptr(heat[:, 18]), heat.stride(2), heat.stride(3), heat.stride(0), int(heat.shape[2]), int(heat.shape[3]), 2, ops.ptr(u),
+         rh, rw, 1, 0.25, 0.25, ops.stream_ptr())
+    return u
+
+
+def tta_merge_mask(seg_pair_maps, H, W, thr, plane=False, out=None):
+    """mpn_tta_merge_mask: the uint8 [H, W] person mask from the seg pair maps ([rh, rw, 2], channel 0 the original pass, channel 1 the
+    mirrored one) of every scale — ``_get_outputs`` for both passes on channel 18, the mirror, the halving, one rounding to float32 and
+    the threshold in one launch.  ``out``: a uint8 [H, W] view with dense columns to write instead of a new tensor; with ``plane`` the
+    float32 [H, W] plane is returned as well."""
+    n = len(seg_pair_maps)
+    table = (TtaScale * max(n, 1))()
+    for s, u in enumerate(seg_pair_maps):
+        if u.dtype != torch.float32 or u.dim() != 3 or u.shape[2] != 2 or u.stride(2) != 1 or u.stride(1) != 2:
+            raise ValueError("seg pair map %d: float32 [rh, rw, 2] with dense pixels expected" % s)
+        table[s].u, table[s].rh, table[s].rw, table[s].pitch = u.data_ptr(), int(u.shape[0]), int(u.shape[1]), int(u.stride(0))
+    dev = seg_pair_maps[0].device
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (H, W) or (W > 1 and out.stride(1) != 1):
+        raise ValueError("tta_merge_mask: out must be a uint8 [%d, %d] tensor with dense columns" % (H, W))
+    pl = torch.empty((H, W), dtype=torch.float32, device=dev) if plane else None
+    call("mpn_tta_merge_mask", table, n, H, W, _thr32(thr), ops.ptr(pl) if plane else None, ops.ptr(out), int(out.stride(0)) if H > 1 else W,
+         ops.stream_ptr())
+    return (out, pl) if plane else out
+
+
 def _to_device_image(img, dev):
     if isinstance(img, np.ndarray):
         img = torch.from_numpy(np.ascontiguousarray(img))
@@ -160,6 +235,7 @@ class Tester(object):
         self.model = model
         self.last_eval = None             # coco_eval(..., annotations=...): the KeypointEval result dict
         self.last_box_eval = None         # coco_eval_bbox(...): the BoxEval result dict
+        self.last_seg_eval = None         # seg_eval(...): the person-mask IoU result dict
         if self.params.ckpt is not None:
             self._load_ckpt(self.params.ckpt)
             logger.info('Load ckpt from {}'.format(self.params.ckpt))
@@ -246,11 +322,23 @@ class Tester(object):
                 joints.append(joint)
         return joints
 
+    def _need_person_seg(self):
+        from .._lib import MpnError
+        if not getattr(self.model, 'person_seg', False):
+            raise MpnError("return_masks needs a person_seg model: a plain model has no channel 18")
+
+    def _threshold_plane(self, plane):
+        """M = 255 where P > mask_thresh, else 0 (strict; a NaN gives 0) with the tensor library's ops: the unfused yardstick."""
+        return (plane > _thr32(self.params.mask_thresh)).to(torch.uint8) * 255
+
     def prn_process(self, kps, bbox_list, file_name, image_id=0):
         return prn_process(self.model, kps, bbox_list, file_name, image_id, coeff=self.params.coeff, in_thres=self.params.in_thres)
 
     # ------------------------------------------------------------------ single scale (Tester.test, :194-245)
-    def infer_image(self, img, file_name='', image_id=0):
+    def infer_image(self, img, file_name='', image_id=0, return_masks=False):
+        """``return_masks`` (person_seg models): -> (results, [mask]) with the uint8 [H, W] person mask composed from existing ops."""
+        if return_masks:
+            self._need_person_seg()
         img = _to_device_image(img, self.dev)
         shape_dst = max(img.shape[0], img.shape[1])
         scale = float(shape_dst) / self.params.inp_size
@@ -265,9 +353,16 @@ class Tester(object):
         param = {'thre1': 0.1, 'thre2': 0.05, 'thre3': 0.5}
         joint_list = get_joint_list(img_resized, param, heatmaps[0, :18].permute(1, 2, 0), scale, bool_gaussian_filt=self.params.gaussian_filt)
         bboxs = self._boxes(scores, classification, transformed_anchors, scale)
-        return self.prn_process(self._body_joints(joint_list), bboxs, file_name, image_id)
+        results = self.prn_process(self._body_joints(joint_list), bboxs, file_name, image_id)
+        if not return_masks:
+            return results
+        H, W = int(img.shape[0]), int(img.shape[1])
+        plane = resize(heatmaps[0, 18][:, :, None], (shape_dst, shape_dst), cubic=True)[:H, :W, 0]
+        _, _, views = _mask_views([(H, W)], self.dev)
+        views[0].copy_(self._threshold_plane(plane))
+        return results, views
 
-    def infer_images_batched(self, images, file_names=None, image_ids=None, batch=64, pipeline=True):
+    def infer_images_batched(self, images, file_names=None, image_ids=None, batch=64, pipeline=True, return_masks=False):
         """``infer_image`` for many images with the network, the peak extraction and the PRN assignment running on whole batches:
         every image is padded to a square and resized to inp_size x inp_size (tester.py:203-213), so images of any size share a
         forward; per-image scales are applied to peaks and boxes afterwards.  Same result dicts, image by image, as
@@ -276,7 +371,13 @@ class Tester(object):
         ``pipeline`` (round 6): the network of batch k + 1 is enqueued BEFORE batch k is post-processed, and the post-processing
         launches (NMS, peaks, PRN forward, candidate compaction) go to a second stream that waits for batch k's network only — the
         host's numpy work and its device reads run under the next batch's network instead of leaving the GPU idle (2 - 5 ms of a 33 ms
-        batch at 640 x 640 x 64).  Results are identical (same launches on the same data)."""
+        batch at 640 x 640 x 64).  Results are identical (same launches on the same data).
+
+        ``return_masks`` (person_seg models): -> (results, masks), one uint8 [H, W] person mask per image, the masks of a batch views of
+        one buffer written by ONE mpn_seg_masks on the network's stream, before the event the post-processing stream waits for."""
+        if return_masks:
+            self._need_person_seg()
+        masks = []
         n = len(images)
         file_names = file_names if file_names is not None else [''] * n
         image_ids = image_ids if image_ids is not None else [0] * n
@@ -288,17 +389,20 @@ class Tester(object):
             nxt = None
             if i0 is not None:
                 idx = list(range(i0, min(n, i0 + batch)))
-                xs, scales = [], []
+                xs, scales, sizes = [], [], []
                 for i in idx:
                     img = _to_device_image(images[i], self.dev)
                     shape_dst = max(img.shape[0], img.shape[1])
                     scales.append(float(shape_dst) / S)
+                    sizes.append((int(img.shape[0]), int(img.shape[1])))
                     pad = abs(img.shape[1] - img.shape[0])
                     sq = torch.zeros((img.shape[0] + pad, img.shape[1] + pad, 3), dtype=torch.float32, device=self.dev)
                     sq[:img.shape[0], :img.shape[1]] = img
                     xs.append(resnet_preprocess(resize(sq[:shape_dst, :shape_dst], (S, S), cubic=False)))
                 with torch.no_grad():
                     heat, anchors, cls, keep = self.model.forward_padded_begin(torch.stack(xs))
+                if return_masks:
+                    masks.extend(seg_masks(heat, sizes, self.params.mask_thresh))
                 ev = None
                 if post is not None:
                     ev = torch.cuda.Event()
@@ -310,7 +414,7 @@ class Tester(object):
             if pending is not None:
                 self._finish_batch(pending, out, file_names, image_ids, post)
             pending = nxt
-        return out
+        return (out, masks) if return_masks else out
 
     def _post_stream(self):
         if getattr(self, '_post', None) is None:
@@ -489,10 +593,12 @@ class Tester(object):
         """tester.py:256-262."""
         return [x * self.params.inp_size / float(img.shape[0]) for x in [0.5, 1., 1.5, 2, 2.5]]
 
-    def _get_outputs(self, multiplier, img):
-        """tester.py:264-313: heat-maps of every scale resized back to the image and averaged; boxes per scale."""
+    def _get_outputs(self, multiplier, img, seg=False):
+        """tester.py:264-313: heat-maps of every scale resized back to the image and averaged; boxes per scale.  ``seg``: the same
+        steps on channel 18 as well, into a float64 [H, W, 1] accumulator returned third."""
         H, W = img.shape[0], img.shape[1]
         heatmap_avg = torch.zeros((H, W, 18), dtype=torch.float64, device=self.dev)       # np.zeros(...) accumulator: float64 (tester.py:266)
+        seg_avg = torch.zeros((H, W, 1), dtype=torch.float64, device=self.dev) if seg else None
         bbox_all = []
         for scale in multiplier:
             inp_size = scale * H
@@ -505,22 +611,37 @@ class Tester(object):
             hm = hm[0:real_shape[0], 0:real_shape[1], :]
             hm = resize(hm, (H, W), cubic=True)
             heatmap_avg = heatmap_avg + hm / len(multiplier)
+            if seg:
+                sm = heatmaps[0, 18:19].permute(1, 2, 0)[:int(im_cropped.shape[0] / 4), :int(im_cropped.shape[1] / 4), :]
+                sm = resize(sm, (sm.shape[0] * 4, sm.shape[1] * 4), cubic=True)
+                sm = sm[0:real_shape[0], 0:real_shape[1], :]
+                sm = resize(sm, (H, W), cubic=True)
+                seg_avg = seg_avg + sm / len(multiplier)
             bbox_all.append(self._boxes(scores, classification, transformed_anchors, 1.0 / im_scale))
-        return heatmap_avg, bbox_all
+        return (heatmap_avg, bbox_all, seg_avg) if seg else (heatmap_avg, bbox_all)
 
     @staticmethod
     def _handle_heat(normal_heat, flipped_heat):
         """tester.py:315-331."""
         return (normal_heat + flipped_heat.flip(1)[:, :, SWAP_HEAT]) / 2.
 
-    def infer_image_multiscale(self, img, file_name='', image_id=0):
+    def infer_image_multiscale(self, img, file_name='', image_id=0, return_masks=False):
         """tester.py:143-175 for one image.  The float64 averaged maps are rounded to float32 once before the peak kernel; with
         ``params.gaussian_filt`` the smoothing then follows the float32 semantics of ``NMS`` (float32 up-sampled patch, float64 sums,
-        one float32 rounding per axis), where the reference would filter a float64 patch."""
+        one float32 rounding per axis), where the reference would filter a float64 patch.
+
+        ``return_masks`` (person_seg models): -> (results, [mask]); the mask comes from ``_get_outputs``' steps on channel 18 of both
+        passes, the mirrored one flipped back (no channel swap), halved, rounded to float32 once and thresholded."""
+        if return_masks:
+            self._need_person_seg()
         img = _to_device_image(img, self.dev)
         multiplier = self._get_multiplier(img)
-        orig_heat, orig_bbox_all = self._get_outputs(multiplier, img)
-        flipped_heat, _ = self._get_outputs(multiplier, img.flip(1).contiguous())
+        if return_masks:
+            orig_heat, orig_bbox_all, seg_o = self._get_outputs(multiplier, img, seg=True)
+            flipped_heat, _, seg_f = self._get_outputs(multiplier, img.flip(1).contiguous(), seg=True)
+        else:
+            orig_heat, orig_bbox_all = self._get_outputs(multiplier, img)
+            flipped_heat, _ = self._get_outputs(multiplier, img.flip(1).contiguous())
         heatmaps = self._handle_heat(orig_heat, flipped_heat)
         param = {'thre1': 0.1, 'thre2': 0.05, 'thre3': 0.5}
         # the averaged maps are float64 as in the reference (np.zeros accumulator); the peak kernel takes float32, so they are
@@ -530,19 +651,26 @@ class Tester(object):
         for result in results:                                    # tester.py:167-175: COCO keypoint order
             kp = result['keypoints']
             result['keypoints'] = [kp[COCO_ORDER[i] * 3 + j] for i in range(17) for j in range(3)]
-        return results
+        if not return_masks:
+            return results
+        plane = ((seg_o + seg_f.flip(1)) / 2.).float()[:, :, 0]
+        _, _, views = _mask_views([(int(img.shape[0]), int(img.shape[1]))], self.dev)
+        views[0].copy_(self._threshold_plane(plane))
+        return results, views
 
     # ------------------------------------------------------------------ the same, fused and flip-paired (params.tta_fused)
-    def _tta_enqueue(self, img, pair=True):
+    def _tta_enqueue(self, img, pair=True, mask_out=None):
         """Everything of ``infer_image_multiscale`` up to the averaged maps, enqueued on the current stream without a host read: per
         scale ONE mpn_tta_input (the original and the mirrored network input), ONE forward over the pair — keypoint-only except for
         scale index 1, the only scale whose boxes are used (tester.py:169) — and ONE mpn_resize (the x4 up-sampling of both maps,
         only the region that survives the crop); then ONE mpn_tta_merge.  ``pair=False``: the two images of a pair go through the
-        network one at a time.  Returns the item ``_tta_finish`` takes; it owns every tensor another stream may still read."""
+        network one at a time.  ``mask_out`` (a uint8 [H, W] view): per scale one more mpn_resize (channel 18 of both images of the pair, in
+        place) and ONE mpn_tta_merge_mask that writes the person mask into it, on this stream.  Returns the item ``_tta_finish`` takes;
+        it owns every tensor another stream may still read."""
         img = _to_device_image(img, self.dev)
         H, W = int(img.shape[0]), int(img.shape[1])
         multiplier = self._get_multiplier(img)
-        alive, det, pair_maps = [img], None, []
+        alive, det, pair_maps, seg_maps = [img], None, [], []
         for si, scale in enumerate(multiplier):
             im_scale, h, w, hp, wp = scale_geometry(H, W, scale * H, 32)
             x = tta_input(img, h, w, hp, wp, 1.0 / im_scale)
@@ -558,10 +686,14 @@ class Tester(object):
                     alive.append(keep)
                     heat = torch.cat([heat, heat1])
             hq, wq = int(hp / 4), int(wp / 4)
+            if mask_out is not None:
+                seg_maps.append(tta_seg_upsample(heat[:, :, :hq, :wq], min(h, 4 * hq), min(w, 4 * wq)))
             heat = heat[:, :18, :hq, :wq]
             pair_maps.append(tta_upsample(heat, min(h, 4 * hq), min(w, 4 * wq)))       # only the region that survives the crop
             alive += [x, heat]
-        return img, tta_merge(pair_maps, H, W), det, alive + pair_maps
+        if mask_out is not None:
+            tta_merge_mask(seg_maps, H, W, self.params.mask_thresh, out=mask_out)
+        return img, tta_merge(pair_maps, H, W), det, alive + pair_maps + seg_maps
 
     def _tta_finish(self, item, file_name, image_id):
         """Boxes of scale index 1 (image 0 of the pair), peaks of the averaged maps, PRN assignment, COCO order — on the current stream."""
@@ -585,18 +717,28 @@ class Tester(object):
             result['keypoints'] = [kp[COCO_ORDER[i] * 3 + j] for i in range(17) for j in range(3)]
         return results
 
-    def infer_image_multiscale_fused(self, img, file_name='', image_id=0, pair=True):
+    def infer_image_multiscale_fused(self, img, file_name='', image_id=0, pair=True, return_masks=False):
         """``infer_image_multiscale`` with the same result dicts, value for value, from 5 paired forwards instead of 10 single ones
         (one detection head instead of ten) and two fused element-wise kernels around them (csrc/tta.hip); the only host reads are
-        those of the detections, the peaks and the PRN assignment."""
-        return self._tta_finish(self._tta_enqueue(img, pair), file_name, image_id)
+        those of the detections, the peaks and the PRN assignment.  ``return_masks`` (person_seg models): -> (results, [mask]), the mask
+        of ``infer_image_multiscale`` from five more mpn_resize and one mpn_tta_merge_mask."""
+        if not return_masks:
+            return self._tta_finish(self._tta_enqueue(img, pair), file_name, image_id)
+        self._need_person_seg()
+        _, _, views = _mask_views([(int(img.shape[0]), int(img.shape[1]))], self.dev)
+        return self._tta_finish(self._tta_enqueue(img, pair, views[0]), file_name, image_id), views
 
-    def infer_images_multiscale(self, images, file_names=None, image_ids=None, pipeline=True, pair=True):
+    def infer_images_multiscale(self, images, file_names=None, image_ids=None, pipeline=True, pair=True, return_masks=False):
         """``infer_image_multiscale_fused`` over many images.  ``pipeline``: the launches of image k + 1 up to and including its merge are
         enqueued BEFORE image k's detections, peaks and PRN assignment are read; those go to the post-processing stream behind an event,
-        as in ``infer_images_batched``.  Same launches on the same data: results identical to ``pipeline=False``."""
+        as in ``infer_images_batched``.  Same launches on the same data: results identical to ``pipeline=False``.
+        ``return_masks`` (person_seg models): -> (results, masks); the masks are views of one buffer, each written before its image's event."""
         images = list(images)
         n = len(images)
+        views = [None] * n
+        if return_masks:
+            self._need_person_seg()
+            _, _, views = _mask_views([(int(im.shape[0]), int(im.shape[1])) for im in images], self.dev)
         file_names = file_names if file_names is not None else [''] * n
         image_ids = image_ids if image_ids is not None else [0] * n
         out = [None] * n
@@ -605,7 +747,7 @@ class Tester(object):
         for i in list(range(n)) + [None]:
             nxt = None
             if i is not None:
-                item = self._tta_enqueue(images[i], pair)
+                item = self._tta_enqueue(images[i], pair, views[i])
                 if post is None:
                     out[i] = self._tta_finish(item, file_names[i], image_ids[i])
                 else:
@@ -619,4 +761,51 @@ class Tester(object):
                     out[k] = self._tta_finish(item, file_names[k], image_ids[k])
                 torch.cuda.current_stream(self.dev).wait_stream(post)      # the item's tensors return to this stream's allocator pool
             pending = nxt
-        return out
+        return (out, views) if return_masks else out
+
+    # ------------------------------------------------------------------ person masks and their score (not in the reference)
+    def person_masks(self, images, multiscale=False, batch=64):
+        """The uint8 [H, W] person mask (255 where channel 18's image-sized plane > ``params.mask_thresh``) of every decoded image:
+        ``infer_images_batched`` (single scale) or ``infer_images_multiscale`` (5 scales x flip) with ``return_masks``."""
+        images = list(images)
+        if multiscale:
+            return self.infer_images_multiscale(images, return_masks=True)[1]
+        return self.infer_images_batched(images, batch=batch, return_masks=True)[1]
+
+    def seg_eval(self, images, annotations, multiscale=False, batch=64):
+        """IoU of the predicted person masks against ``mask_all`` on the device.  ``images`` yields (image_id, file_name, [H, W, 3] BGR
+        array) as for ``coco_eval``; ``annotations`` is the annotation json's ``annotations`` list (person annotations, category 1).
+        Per chunk of ``batch`` images: the masks (``person_masks``), ``mask_all`` of the chunk (datasets/segm.py: person_masks_batch on
+        each image's annotations in json order) and the counts (mpn_mask_iou) into one device array; ONE host read at the end.  The
+        summary lines are logged; the dict (seg_eval.summarize_counts plus ``inter``, ``pred``, ``gt``, ``pixels``, ``image_ids``) is kept
+        in ``self.last_seg_eval`` and returned."""
+        from ..datasets.segm import person_masks_batch
+        from .seg_eval import mask_iou_counts, summarize_counts
+        self._need_person_seg()
+        images = list(images)
+        by_img = {}
+        for a in annotations:
+            if int(a.get('category_id', 1)) == 1:
+                by_img.setdefault(a['image_id'], []).append(a)
+        n = len(images)
+        counts = torch.zeros((max(n, 1), 3), dtype=torch.int64, device=self.dev)
+        sizes = [(int(arr.shape[0]), int(arr.shape[1])) for _, _, arr in images]
+        for i0 in range(0, n, batch):
+            chunk, csz = images[i0:i0 + batch], sizes[i0:i0 + batch]
+            masks = self.person_masks([arr for _, _, arr in chunk], multiscale=multiscale, batch=batch)
+            base = masks[0].storage_offset()              # the chunk's masks are views of one buffer, the first at its start
+            pred_buf = torch.empty(0, dtype=torch.uint8, device=self.dev).set_(masks[0].untyped_storage())[base:]
+            _, gt_buf, gt_off = person_masks_batch([by_img.get(image_id, []) for image_id, _, _ in chunk], csz, dev=self.dev)
+            table = np.array([(H, W, m.storage_offset() - base, W, go, W) for (H, W), m, go in zip(csz, masks, gt_off)], dtype=np.int64)
+            mask_iou_counts(pred_buf, gt_buf, table, out=counts[i0:i0 + len(chunk)])
+        c = counts[:n].cpu().numpy()
+        pixels = np.array([H * W for H, W in sizes], dtype=np.int64)
+        ev = summarize_counts(c, pixels)
+        ev.update({'inter': c[:, 0].copy(), 'pred': c[:, 1].copy(), 'gt': c[:, 2].copy(), 'pixels': pixels,
+                   'image_ids': [image_id for image_id, _, _ in images]})
+        mode = 'multi-scale' if multiscale else 'single scale'
+        for key in ('iou', 'mean_iou', 'precision', 'recall', 'pixel_acc'):
+            logger.info(' Person mask %-9s (%s, thr %.3f) = %0.3f' % (key, mode, self.params.mask_thresh, ev[key]))
+        logger.info(' Person mask images = %d, without any ON pixel in either mask = %d' % (ev['n_images'], ev['n_empty']))
+        self.last_seg_eval = ev
+        return ev
